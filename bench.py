@@ -2,7 +2,7 @@
 """Training-step benchmark of the binarized-network hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config wide|mlp|cnn|small] [--batch B]
-                    [--exchange]
+                    [--exchange] [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as one process per GPU (torch.distributed.run, RCCL).
 A "step" = one training step of the reference loop (mnist-dist2.py:118-137) on one batch of
@@ -16,13 +16,19 @@ Default workload = BASELINE config 5 (the one the metric's 1/2/4/8-GPU curve is 
 wide binarized MLP 784-8192x3-10, batch 65536 per GPU.
 
 Timing: W untimed warmup steps, then K steps between barrier + synchronize on both sides with
-NO per-kernel instrumentation (``value``); the max over ranks.  Afterwards (outside the timed
+NO per-kernel instrumentation (``value``, ``ms_per_step``); the max over ranks.  A plain run does
+no more than that: set up, warm up, time the K steps, write the last step's results with
+--dump-outputs (inputs, initial weights and dropout seeds are seeded: the same arguments give the
+same step sequence), print the line.  Everything else is measured with --full only.  With it,
+afterwards (outside the timed
 region) a few instrumented steps time every libbnn launch with HIP events on its stream for the
 ``roofline`` object, whose ``achieved`` is ALGORITHMIC work (2*M*N*K ops per GEMM launch,
 SURVEY §8(d); the digit passes that emulate fp32 operands on the int8 MFMA are not work) or
 algorithmic bytes (HBM-bound kernels) per launch over the average launch time.
 
-Prints ONE JSON line (rank 0) with the contract fields plus ``roofline``, ``cpu_baseline`` (the
+Prints ONE JSON line (rank 0) with the contract fields plus, with --full, ``kernels``,
+``binary_gemm_tops``, ``dropin`` (the unchanged-script path timed on the same batch), ``roofline``,
+``cpu_baseline`` (the
 oracle's torch-CPU restatement of the reference path on this box's host cores, N = 1 only:
 the bench config itself, plus BASELINE configs 1 and 2) and ``gpu_torch_fp32`` (the same
 restatement run on this GPU with torch's fp32 kernels: the naive-GPU comparator).
@@ -124,6 +130,14 @@ def parse():
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-gpu-torch", action="store_true", help="skip the torch-fp32-on-GPU comparator")
     ap.add_argument("--timing-steps", type=int, default=3, help="instrumented steps for the roofline")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baselines, the instrumented "
+                         "steps (kernels / roofline / binary_gemm_tops), the drop-in path's timing and the "
+                         "torch-fp32-on-GPU comparator (each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): its "
+                         "loss and log-probabilities, and every parameter / buffer after its update with the "
+                         "gradient it consumed (seeded samples of the large ones)")
     return ap.parse_args()
 
 
@@ -149,16 +163,20 @@ def build_dropin(cfg, dropin_bn=False):
     return nets.MODELS[name](dropin_bn=True) if dropin_bn else nets.MODELS[name]()
 
 
-def dropin_step_fn(model, x, y, lr):
+def dropin_step_fn(model, x, y, lr, last=None):
     """mnist-dist2.py:118-137 unchanged: zero_grad, forward, nn.CrossEntropyLoss, backward, then the
-    .org restore -> torch.optim.Adam.step -> clamp loop (optim.org_protocol_step)."""
+    .org restore -> torch.optim.Adam.step -> clamp loop (optim.org_protocol_step).  ``last``: a dict
+    that keeps the newest step's model output (for --dump-outputs)."""
     from bnn_amd.optim import org_protocol_step
     opt = torch.optim.Adam(model.parameters(), lr=lr)
     crit = torch.nn.CrossEntropyLoss()
 
     def step():
         opt.zero_grad()
-        loss = crit(model(x), y)
+        out = model(x)
+        if last is not None:
+            last["out"] = out.detach()
+        loss = crit(out, y)
         loss.backward()
         org_protocol_step(model, opt)
         return loss
@@ -190,9 +208,11 @@ def time_dropin(cfg, batch, dev, lr, steps, warmup, dropin_bn=False):
     return out
 
 
-def _dropin_with_exchange(model, x, y, opt, exchange):
+def _dropin_with_exchange(model, x, y, opt, exchange, last):
     from bnn_amd.optim import org_protocol_step
-    loss = torch.nn.CrossEntropyLoss()(model(x), y)
+    out = model(x)
+    last["out"] = out.detach()
+    loss = torch.nn.CrossEntropyLoss()(out, y)
     loss.backward()
     exchange.finish()
     org_protocol_step(model, opt)
@@ -320,6 +340,40 @@ def roofline_of(ksum, steps):
     return r
 
 
+DUMP_MAX_ELEMS = 1 << 20     # per array: 4 MiB of float32; a larger tensor is sampled
+
+
+def dump_outputs(path, model, loss, out):
+    """What the last timed step handed its caller, as ``path/<name>.npy`` (float32): ``loss``,
+    ``log_probs`` (the model's output), and the model's state after that step's update --
+    ``param.<name>``, ``buffer.<name>`` and ``grad.<name>`` (the gradient the update consumed).  A
+    tensor of more than DUMP_MAX_ELEMS elements is written as its elements at sorted flat indices
+    drawn from a generator seeded by the tensor's name and size, the same in every run, so the
+    files of two builds line up element for element (about 30 MB in all for the wide MLP)."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def put(name, t):
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), t.numel()])
+            idx = np.sort(rng.integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+    put("loss", loss)
+    if out is not None:
+        put("log_probs", out)
+    for name, p in model.named_parameters():
+        put("param." + name, p)
+        if p.grad is not None:
+            put("grad." + name, p.grad)
+    for name, b in model.named_buffers():
+        put("buffer." + name, b)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -330,7 +384,7 @@ def main():
     if world != args.gpus:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}; using WORLD_SIZE", file=sys.stderr)
     cpu_main, cpu_extra = None, []
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_main, cpu_extra = cpu_baselines(args.config, args.cpu_budget)   # before any GPU work
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -364,15 +418,16 @@ def main():
     dstep = BF.DeviceStep(dev).activate() if args.graph else None
     as_u8 = args.config != "cnn" and not args.fp32_input and not args.dropin
     x, y = synthetic_mnist(batch, seed=1234 + rank, device=dev, as_u8=as_u8)
+    last = {}     # the newest step's model output (its log-probabilities), for --dump-outputs
     if args.dropin:
         # the unchanged reference loop on the drop-in module (its torch.optim.Adam + .org loop);
         # the exchange's hooks and finish() bracket it as DDP's would
-        inner = dropin_step_fn(model, x, y, args.lr)
+        inner = dropin_step_fn(model, x, y, args.lr, last)
 
         def step():
             if exchange is not None:
                 exchange.zero_grad()
-            loss = inner() if exchange is None else _dropin_with_exchange(model, x, y, inner_opt, exchange)
+            loss = inner() if exchange is None else _dropin_with_exchange(model, x, y, inner_opt, exchange, last)
             return loss
         inner_opt = torch.optim.Adam(model.parameters(), lr=args.lr) if exchange is not None else None
     else:
@@ -386,7 +441,9 @@ def main():
             else:
                 for p in model.parameters():
                     p.grad = None
-            loss = crit(model(x), y)
+            out = model(x)
+            last["out"] = out.detach()
+            loss = crit(out, y)
             loss.backward()
             if exchange is not None:
                 exchange.finish()
@@ -434,10 +491,12 @@ def main():
                                               exchange.collectives / max(1, args.warmup + args.steps)
                                               if exchange is not None else None)}
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss, last.get("out"))
 
     # instrumented steps (outside the timed region): per-launch HIP events -> roofline
     ksum, tsteps = {}, 0
-    if not args.no_kernel_timing and args.timing_steps > 0:
+    if args.full and not args.no_kernel_timing and args.timing_steps > 0:
         timer = BF.KernelTimer()
         with BF.timing(timer):
             for _ in range(args.timing_steps):
@@ -503,7 +562,7 @@ def main():
     if cpu_main:
         result["cpu_baselines_other"] = cpu_extra
         result["speedup_vs_cpu"] = round(result["value"] / cpu_main["value"], 1)
-    if rank == 0 and world == 1 and not args.dropin and not args.no_dropin and not args.graph:
+    if args.full and rank == 0 and world == 1 and not args.dropin and not args.no_dropin and not args.graph:
         # the unchanged-script path (models.binarized_modules drop-in + the reference's loop) on the
         # same GPU and batch, timed after the main measurement: what a user of mnist-dist2.py gets
         try:
@@ -516,7 +575,7 @@ def main():
                 result["dropin_bn"] = time_dropin(args.config, batch, dev, args.lr, steps=5, warmup=2, dropin_bn=True)
             except RuntimeError as e:
                 result["dropin_bn"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_gpu_torch and args.config in CPU_WIDTHS:
+    if args.full and rank == 0 and world == 1 and not args.no_gpu_torch and args.config in CPU_WIDTHS:
         try:
             gb = min(batch, 16384) if args.config == "wide" else batch
             result["gpu_torch_fp32"] = gpu_torch_baseline(args.config, gb)
