@@ -61,6 +61,9 @@ SIGNATURES = {
     "bnn_row_sums": (I32, [P, I64, I64, I64, P, P]),
     "bnn_gemm_fp4": (I32, [P, I64, P, I64, P, P, I64, I64, I64, I64, P]),
     "bnn_gemm_fp4_i16": (I32, [P, I64, P, I64, P, I64, I64, I64, I64, P]),
+    "bnn_gemm_fp4_bnsign": (I32, [P, I64, P, I64, P, P, P, P, P, P, I64, I64, I64, I64, P]),
+    "bnn_gemm_i8_affine_bnsign": (I32, [P, I64, P, I64, P, P, P, ctypes.c_double, P, P, P, P, P, I64, I64, I64, I64,
+                                        P]),
     "bnn_gemm_set_variant": (I32, [I32]),
     "bnn_gemm_set_raster": (I32, [I32]),
     "bnn_adam_pack_set_tile256": (I32, [I32]),
@@ -104,6 +107,7 @@ SIGNATURES = {
     "bnn_dropout_mask": (I32, [I64, F32, U64, P, P]),
     "bnn_bn_head_workspace": (I64, [I64, I64, I32]),
     "bnn_bn_head_fwd": (I32, [P, I64, I64, P, P, P, P, P, F32, U64, P, P, I32, P, P, P]),
+    "bnn_bn_head_eval": (I32, [P, P, P, I64, I64, P, P, P, P, P, I32, P, P, P]),
     "bnn_bn_head_bwd_q6": (I32, [P, P, P, I32, I64, I64, P, P, P, P, P, F32, U64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "bnn_bn_apply_pack": (I32, [P, I64, I64, P, P, P, P, P, I32, P, I64, P, I64, I32, P]),
     "bnn_bn_fwd_train_i16": (I32, [P, P, I64, I64, P, P, P, P, F32, F32, P, P, P, F32, U64, P, P, P]),

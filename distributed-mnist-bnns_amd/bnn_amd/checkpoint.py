@@ -87,3 +87,18 @@ def load_checkpoint(path, model, optimizer=None, map_location=None):
     if optimizer is not None and blob.get("optimizer") is not None:
         optimizer.load_state_dict(blob["optimizer"])
     return blob["epoch"]
+
+
+def save_frozen(path, frozen):
+    """Write a ``bnn_amd.inference.FrozenMLP`` -- packed tensors plus widths and the pixel Normalize --
+    for inference without the float model.  Atomic, as ``save_checkpoint``."""
+    tmp = f"{path}.tmp"
+    torch.save(frozen.state_dict(), tmp)
+    os.replace(tmp, path)
+
+
+def load_frozen(path, map_location=None):
+    """The ``FrozenMLP`` written by ``save_frozen`` (on ``map_location``, default: where it was saved)."""
+    from .inference import FrozenMLP
+    state = torch.load(path, map_location=map_location, weights_only=True)
+    return FrozenMLP.from_state(state)

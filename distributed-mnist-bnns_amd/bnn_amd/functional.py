@@ -2254,3 +2254,104 @@ def bn_hardtanh_binary_linear(z, bn, fc, backend="fp4", emit_z16=False, emit_sta
     return BNHardtanhBinaryLinearFunction.apply(z, bn.weight, bn.bias, rm, rv, bn_training, factor, bn.eps,
                                                 fc.weight, fc.bias, backend, bool(emit_z16),
                                                 emit_stats if isinstance(emit_stats, tuple) else bool(emit_stats))
+
+
+# ----------------------------------------------------------------------------- frozen-model inference
+# In eval mode BatchNorm -> Hardtanh -> Binarize of the next layer is a per-column function of the
+# GEMM's sum, so the hidden GEMMs of a frozen network (bnn_amd.inference) write the next layer's FP4
+# operand from their epilogue and nothing else.  No autograd.
+def _q4_out(M, N, out, device):
+    if out is None:
+        return torch.empty((M, round_up(N, 256) // 2), dtype=torch.uint8, device=device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape[0] == M
+    return out
+
+
+def bnsign_ok(N):
+    """Whether the BN-sign GEMMs take an N-column layer (else: the GEMM + bn_apply_pack pair)."""
+    return N % 4 == 0
+
+
+def gemm_fp4_bnsign(A4, B4, M, N, bias, mean, invstd, gamma=None, beta=None, k_true=None, out=None):
+    """FP4 rows [M, round_up(N, 256) / 2] of sign(BN(A.B^T + bias)) with eval-mode BatchNorm vectors:
+    gemm_fp4 + bn_apply_pack in one kernel, bit-identical to the pair (bnn_gemm_fp4_bnsign)."""
+    Kb = A4.shape[-1]
+    assert B4.shape[-1] == Kb and Kb % ALIGN == 0
+    _check(bias, mean, invstd, gamma, beta)
+    q4 = _q4_out(M, N, out, A4.device)
+    if M == 0:
+        return q4
+    k_true = 2 * Kb if k_true is None else k_true
+    with _timed("gemm_fp4_bnsign_k", 2.0 * M * N * k_true, (M + N) * Kb + q4.numel()):
+        L.call("bnn_gemm_fp4_bnsign", L.ptr(A4), Kb, L.ptr(B4), Kb, L.ptr(bias), L.ptr(mean), L.ptr(invstd),
+               L.ptr(gamma), L.ptr(beta), L.ptr(q4), q4.shape[1], M, N, Kb, L.stream())
+    return q4
+
+
+def gemm_i8_affine_bnsign(A, B, M, N, b_scale, bias, col_off, off_mul, mean, invstd, gamma=None, beta=None,
+                          k_true=None, out=None):
+    """The same on the u8-pixel layer's (1,1) int8 GEMM (gemm_i8_affine with b_scale / bias / col_off /
+    off_mul as binary_linear_pixels passes them): bnn_gemm_i8_affine_bnsign."""
+    K = A.shape[-1]
+    assert B.shape[-1] == K and K % ALIGN == 0 and (col_off is None or col_off.dtype == torch.int64)
+    _check(b_scale, bias, mean, invstd, gamma, beta)
+    q4 = _q4_out(M, N, out, A.device)
+    if M == 0:
+        return q4
+    k_true = K if k_true is None else k_true
+    with _timed("gemm_i8_bnsign_k [pixels]", 2.0 * M * N * k_true, (M + N) * K + q4.numel()):
+        L.call("bnn_gemm_i8_affine_bnsign", L.ptr(A), K, L.ptr(B), K, L.ptr(b_scale), L.ptr(bias), L.ptr(col_off),
+               float(off_mul), L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), L.ptr(q4), q4.shape[1],
+               M, N, K, L.stream())
+    return q4
+
+
+def head_eval_fusable(C, fc):
+    """bn -> htanh -> fc as the fused head on running statistics: C % 128 == 0 and a 10-way fc."""
+    return C % 128 == 0 and fc.out_features == HEAD_NOUT and fc.in_features == C
+
+
+def bn_hardtanh_linear_eval(z, bn, fc, invstd=None, out=None):
+    """fc(hardtanh(bn(z))) in eval mode, without autograd: the fused head on the running statistics
+    -- mean = running_mean, invstd = (running_var + eps).rsqrt(), no dropout -- when
+    head_eval_fusable; otherwise bnn_bn_fwd_eval + F.linear.  The fused form is bnn_bn_head_eval:
+    bnn_bn_head_fwd[_i16]'s kernel with the logits accumulated in double (that kernel's fp32 chain
+    measured 1.2e-6 against float64 where F.linear has 3.3e-7: DESIGN.md §11).
+
+    z: fp32 [M, C], or the pair (int16 dot products [M, C], fp32 bias [C]) of gemm_fp4_i16 (fused head
+    only).  bn / fc: modules or any objects with running_mean, running_var, eps, weight, bias /
+    weight, bias, in_features, out_features.  invstd: (running_var + eps).rsqrt() when the caller
+    already holds it."""
+    z16 = isinstance(z, (tuple, list))
+    x = z[0] if z16 else _c2d(z)
+    _check(x, dtype=torch.int16 if z16 else torch.float32)
+    if bn.running_mean is None or bn.running_var is None:
+        raise ValueError("bn_hardtanh_linear_eval needs a BatchNorm with running statistics")
+    M, C = x.shape
+    gw = bn.weight.detach() if bn.weight is not None else None
+    gb = bn.bias.detach() if bn.bias is not None else None
+    w4 = fc.weight.detach()
+    w4 = w4 if w4.is_contiguous() else w4.contiguous()
+    b4 = fc.bias.detach() if fc.bias is not None else None
+    rm = bn.running_mean
+    if head_eval_fusable(C, fc):
+        if invstd is None:
+            invstd = (bn.running_var + bn.eps).rsqrt()
+        y4 = torch.empty((M, HEAD_NOUT), dtype=torch.float32, device=x.device) if out is None else out
+        if M == 0:
+            return y4
+        with _timed("bn_head_fwd [eval]", 0, (2 if z16 else 4) * M * C + 4 * M * HEAD_NOUT):
+            L.call("bnn_bn_head_eval", None if z16 else L.ptr(x), L.ptr(x) if z16 else None,
+                   L.ptr(z[1]) if z16 else None, M, C, L.ptr(rm), L.ptr(invstd), L.ptr(gw), L.ptr(gb), L.ptr(w4),
+                   HEAD_NOUT, L.ptr(b4), L.ptr(y4), L.stream())
+        return y4
+    if z16:
+        raise ValueError("bn_hardtanh_linear_eval: an int16 pre-activation needs the fused head "
+                         "(head_eval_fusable)")
+    if M == 0:
+        return torch.empty((0, fc.out_features), dtype=torch.float32, device=x.device)
+    h = torch.empty_like(x)
+    with _timed("bn_fwd_eval", 0, 8 * M * C):
+        L.call("bnn_bn_fwd_eval", L.ptr(x), M, C, L.ptr(gw), L.ptr(gb), L.ptr(rm), L.ptr(bn.running_var),
+               float(bn.eps), L.ptr(h), 1, L.ptr(_bn_ws(M, C, x.device)), L.stream())
+    return torch.nn.functional.linear(h, w4, b4)

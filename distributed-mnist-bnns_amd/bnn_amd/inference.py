@@ -1,0 +1,318 @@
+"""Frozen-model inference for the binarized MLPs (nets.MLP and its Net / SmallNet / WideNet widths).
+
+``freeze(model)`` snapshots a trained network once -- fc1's int8 weight rows and their row sums, fc2
+and fc3's FP4 weight rows, every bias, each BatchNorm's running mean / invstd / gamma / beta, fc4 --
+and ``FrozenMLP.forward`` runs it without the float model or autograd:
+
+    u8 pixels -> pixels_pack -> fc1 GEMM [BN1-sign epilogue] -> fc2 GEMM [BN2-sign epilogue]
+              -> fc3 GEMM -> BN3 + Hardtanh + fc4 head on the running statistics -> log-softmax
+
+In eval mode BatchNorm -> Hardtanh -> Binarize of the next layer is a per-column function of the
+GEMM's sum (Hardtanh keeps the sign), so the hidden GEMMs write the next layer's FP4 operand from
+their epilogue (bnn_gemm_i8_affine_bnsign, bnn_gemm_fp4_bnsign): 0.5 B per hidden activation and no
+fp32 hidden activation at all.  The operands are bit-identical to ``model.eval()``'s GEMM +
+bn_apply_pack pair; the head accumulates its logits in double.
+
+The forward has no host synchronisation and keeps its buffers per batch size, so it can be captured
+in ``torch.cuda.graph``.  On CPU tensors it runs a plain-torch restatement of the same layer math
+(for checking a snapshot without a GPU; it is not a serving path).
+"""
+import torch
+import torch.nn.functional as tF
+
+from . import _lib as L
+from . import functional as BF
+from . import nets
+
+__all__ = ["freeze", "FrozenMLP"]
+
+FORMAT = "bnn_amd.frozen/1"
+_K1 = 28 * 28
+
+
+def _tsign(w):
+    """Ternary sign as libbnn's tsign(): int8 +1 / -1 / 0 (NaN -> 0)."""
+    return (w > 0).to(torch.int8) - (w < 0).to(torch.int8)
+
+
+def _pack_i8_rows(w):
+    """[N, K] fp32 -> int8 sign rows [N, round_up(K, 64)] (the layout of bnn_sign_pack_i8)."""
+    N, K = w.shape
+    q = torch.zeros((N, BF.round_up(K)), dtype=torch.int8, device=w.device)
+    q[:, :K] = _tsign(w)
+    return q
+
+
+def _pack_fp4_rows(w):
+    """[N, K] fp32 -> FP4 sign rows [N, round_up(K, 256) / 2] (the layout of bnn_sign_pack_fp4: code
+    0x2 / 0xA / 0x0, element k in byte k / 2, low nibble for even k)."""
+    N, K = w.shape
+    s = _tsign(w)
+    code = torch.zeros((N, BF.round_up(K, 256)), dtype=torch.uint8, device=w.device)
+    code[:, :K] = torch.where(s > 0, 2, torch.where(s < 0, 10, 0)).to(torch.uint8)
+    return (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+
+
+def _unpack_fp4_rows(q4, K):
+    """FP4 sign rows -> int8 signs [rows, K]."""
+    code = torch.stack((q4 & 15, q4 >> 4), dim=2).reshape(q4.shape[0], -1)[:, :K]
+    return (code == 2).to(torch.int8) - (code == 10).to(torch.int8)
+
+
+class _Rec:
+    """Attribute bag standing in for a module (functional.bn_hardtanh_linear_eval reads attributes)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _latent(p):
+    """The latent value of a binarized layer's parameter: ``.org`` when the layer carries one."""
+    return getattr(p, "org", p.data).detach()
+
+
+class FrozenMLP:
+    """A frozen nets.MLP: packed tensors plus widths and the pixel Normalize.  See the module doc."""
+
+    def __init__(self, widths, normalize, eps, tensors, model=None):
+        self.widths = tuple(int(h) for h in widths)
+        self.normalize = None if normalize is None else (float(normalize[0]), float(normalize[1]))
+        self.eps = tuple(float(e) for e in eps)
+        self.t = dict(tensors)
+        self._model = model
+        self._buf = {}
+        self.two_pass = False     # True: every hidden layer as GEMM + bn_apply_pack (A/B and cross-checks)
+
+    # ------------------------------------------------------------------ snapshot
+    @staticmethod
+    def _snapshot(model):
+        if not isinstance(model, nets.MLP):
+            raise TypeError("freeze: expects a bnn_amd.nets.MLP (Net / SmallNet / WideNet)")
+        t = {}
+        for i, bn in enumerate((model.bn1, model.bn2, model.bn3), 1):
+            if bn.running_mean is None or bn.running_var is None:
+                raise ValueError(f"freeze: bn{i} keeps no running statistics (track_running_stats=False); "
+                                 "a frozen network needs them")
+            t[f"bn{i}.mean"] = bn.running_mean.detach().float().clone()
+            t[f"bn{i}.var"] = bn.running_var.detach().float().clone()
+            t[f"bn{i}.invstd"] = (bn.running_var.detach().float() + bn.eps).rsqrt()
+            if bn.weight is not None:
+                t[f"bn{i}.gamma"] = bn.weight.detach().float().clone()
+            if bn.bias is not None:
+                t[f"bn{i}.beta"] = bn.bias.detach().float().clone()
+        w1 = _latent(model.fc1.weight).float()
+        if w1.shape[1] != _K1:
+            raise ValueError("freeze: fc1 must take 784 pixels")
+        t["fc1.q"] = _pack_i8_rows(w1)
+        t["fc1.rowsum"] = t["fc1.q"][:, :_K1].sum(dim=1, dtype=torch.int64)
+        t["fc2.q4"] = _pack_fp4_rows(_latent(model.fc2.weight).float())
+        t["fc3.q4"] = _pack_fp4_rows(_latent(model.fc3.weight).float())
+        for i, fc in enumerate((model.fc1, model.fc2, model.fc3), 1):
+            if fc.bias is not None:
+                # (bias.org is the reference's per-forward clone of the same value)
+                t[f"fc{i}.bias"] = fc.bias.detach().float().clone()
+        t["fc4.weight"] = model.fc4.weight.detach().float().contiguous().clone()
+        if model.fc4.bias is not None:
+            t["fc4.bias"] = model.fc4.bias.detach().float().clone()
+        widths = (model.fc1.out_features, model.fc2.out_features, model.fc3.out_features)
+        return widths, model.fc1.pixel_normalize, (model.bn1.eps, model.bn2.eps, model.bn3.eps), t
+
+    def refresh(self):
+        """Re-snapshot the model this was frozen from (after more training)."""
+        if self._model is None:
+            raise RuntimeError("FrozenMLP.refresh: this snapshot was loaded from a state, not frozen from a model")
+        widths, normalize, eps, t = self._snapshot(self._model)
+        self.__init__(widths, normalize, eps, t, self._model)
+        return self
+
+    # ------------------------------------------------------------------ persistence
+    def state_dict(self):
+        """Tensors, numbers and strings only (torch.load(weights_only=True) reads it back)."""
+        return {"format": FORMAT, "widths": list(self.widths),
+                "normalize": None if self.normalize is None else list(self.normalize),
+                "eps": list(self.eps), "tensors": {k: v.detach().clone() for k, v in self.t.items()}}
+
+    @classmethod
+    def from_state(cls, state, device=None):
+        if state.get("format") != FORMAT:
+            raise ValueError(f"FrozenMLP.from_state: not a {FORMAT} state (format={state.get('format')!r})")
+        t = {k: (v.to(device) if device is not None else v.clone()) for k, v in state["tensors"].items()}
+        return cls(state["widths"], state["normalize"], state["eps"], t)
+
+    def to(self, device):
+        self.t = {k: v.to(device) for k, v in self.t.items()}
+        self._buf = {}
+        return self
+
+    @property
+    def device(self):
+        return self.t["fc4.weight"].device
+
+    # ------------------------------------------------------------------ forward
+    def _bn(self, i):
+        t = self.t
+        return t[f"bn{i}.mean"], t[f"bn{i}.invstd"], t.get(f"bn{i}.gamma"), t.get(f"bn{i}.beta")
+
+    def _pixels(self, x):
+        if x.dim() > 2:
+            x = x.reshape(x.shape[0], -1)
+        if x.dim() != 2 or x.shape[1] != _K1:
+            raise ValueError(f"FrozenMLP: expects [M, 784] or [M, 1, 28, 28] inputs (got {tuple(x.shape)})")
+        return x
+
+    def forward(self, x):
+        """log-probabilities [M, 10] of u8 pixels (the model's pixel_normalize applied) or fp32 images."""
+        x = self._pixels(x)
+        if x.dtype not in (torch.uint8, torch.float32):
+            raise TypeError(f"FrozenMLP: uint8 pixels or float32 images (got {x.dtype})")
+        if not x.is_cuda:
+            return self._forward_cpu(x)[0]
+        return self._forward_gpu(x)
+
+    __call__ = forward
+
+    def predict(self, x):
+        """int64 class labels [M]."""
+        return self.forward(x).argmax(dim=1)
+
+    def accuracy(self, x, labels, batch=4096):
+        """Fraction of ``labels`` predicted, run in batches of ``batch`` (one host read at the end)."""
+        n = x.shape[0]
+        if n == 0:
+            return float("nan")
+        hits = torch.zeros((), dtype=torch.int64, device=x.device)
+        for i in range(0, n, batch):
+            hits += (self.predict(x[i:i + batch]) == labels[i:i + batch].to(x.device)).sum()
+        return float(hits.item()) / n
+
+    def hidden_signs(self, x):
+        """sign(hardtanh(bn_i(z_i))) of the two hidden layers feeding fc2 / fc3, int8 [M, h_i]."""
+        x = self._pixels(x)
+        if not x.is_cuda:
+            return self._forward_cpu(x)[1]
+        self._forward_gpu(x)
+        b = self._buffers(x.shape[0], x.device)
+        return [_unpack_fp4_rows(b["a1"], self.widths[0]), _unpack_fp4_rows(b["a2"], self.widths[1])]
+
+    # ---- GPU
+    def _buffers(self, M, device):
+        key = (M, str(device))
+        b = self._buf.get(key)
+        if b is None:
+            h1, h2, _ = self.widths
+            b = {"q": torch.empty((M, BF.round_up(_K1)), dtype=torch.int8, device=device),
+                 "a1": torch.empty((M, BF.round_up(h1, 256) // 2), dtype=torch.uint8, device=device),
+                 "a2": torch.empty((M, BF.round_up(h2, 256) // 2), dtype=torch.uint8, device=device),
+                 "y4": torch.empty((M, BF.HEAD_NOUT), dtype=torch.float32, device=device)}
+            self._buf[key] = b
+        return b
+
+    def _apply_pack(self, z, i, out):
+        """The two-pass form's second pass: z fp32 -> FP4 rows of sign(BN_i(z)) (bnn_bn_apply_pack)."""
+        mean, invstd, gamma, beta = self._bn(i)
+        M, C = z.shape
+        L.call("bnn_bn_apply_pack", L.ptr(z), M, C, L.ptr(mean), L.ptr(invstd), None, L.ptr(gamma), L.ptr(beta), 1,
+               L.ptr(out), out.shape[1], None, 0, 0, L.stream())
+        return out
+
+    def _forward_gpu(self, x):
+        t = self.t
+        if t["fc4.weight"].device != x.device:
+            raise RuntimeError(f"FrozenMLP on {self.device} got an input on {x.device}; call .to(device)")
+        h1, h2, h3 = self.widths
+        M = x.shape[0]
+        if M == 0:
+            return torch.empty((0, t["fc4.weight"].shape[0]), dtype=torch.float32, device=x.device)
+        b = self._buffers(M, x.device)
+        wq = t["fc1.q"]
+        mean1, invstd1, g1, be1 = self._bn(1)
+        if x.dtype == torch.float32 and self.normalize is None and not torch.cuda.is_current_stream_capturing():
+            u = BF.unit_to_pixels(x)          # ToTensor images are their bytes (one host read, as fc1's)
+            x = u if u is not None else x
+        if x.dtype == torch.uint8:
+            x = x if x.is_contiguous() else x.contiguous()
+            L.call("bnn_pixels_pack", L.ptr(x), M, _K1, _K1, L.ptr(b["q"]), b["q"].shape[1], None, 0, L.stream())
+            a, s0 = BF.pixel_affine(self.normalize)
+            bscale = BF._const_vec(a, h1, x.device)
+            if BF.bnsign_ok(h1) and not self.two_pass:
+                a1 = BF.gemm_i8_affine_bnsign(b["q"], wq, M, h1, bscale, t.get("fc1.bias"), t["fc1.rowsum"], s0,
+                                              mean1, invstd1, g1, be1, k_true=_K1, out=b["a1"])
+            else:
+                z1 = BF.gemm_i8_affine(b["q"], 1, wq, 1, M, h1, b_scale=bscale, bias=t.get("fc1.bias"),
+                                       col_off=t["fc1.rowsum"], off_mul=s0, k_true=_K1, label="pixels")
+                a1 = self._apply_pack(z1, 1, b["a1"])
+        else:
+            # fp32 images that are not plain ToTensor bytes (already normalised, or arbitrary floats):
+            # fc1 on the fp32 digit GEMM as BinarizeLinear runs it, then the apply-pack pass
+            xd, sx = BF.quant_rows(x)
+            z1 = BF.gemm_i8(xd, 3, wq, 1, M, h1, a_scale=sx, bias=t.get("fc1.bias"), k_true=_K1)
+            a1 = self._apply_pack(z1, 1, b["a1"])
+        mean2, invstd2, g2, be2 = self._bn(2)
+        if BF.bnsign_ok(h2) and not self.two_pass:
+            a2 = BF.gemm_fp4_bnsign(a1, t["fc2.q4"], M, h2, t.get("fc2.bias"), mean2, invstd2, g2, be2, k_true=h1,
+                                    out=b["a2"])
+        else:
+            a2 = self._apply_pack(BF.gemm_fp4(a1, t["fc2.q4"], M, h2, bias=t.get("fc2.bias"), k_true=h1), 2, b["a2"])
+        mean3, invstd3, g3, be3 = self._bn(3)
+        bn3 = _Rec(running_mean=mean3, running_var=t["bn3.var"], eps=self.eps[2], weight=g3, bias=be3)
+        fc4 = _Rec(weight=t["fc4.weight"], bias=t.get("fc4.bias"), in_features=t["fc4.weight"].shape[1],
+                   out_features=t["fc4.weight"].shape[0])
+        fused = BF.head_eval_fusable(h3, fc4)
+        if fused and "fc3.bias" in t and BF.z16_ok(M, h3, h2):
+            z3 = (BF.gemm_fp4_i16(a2, t["fc3.q4"], M, h3, k_true=h2), t["fc3.bias"])
+        else:
+            z3 = BF.gemm_fp4(a2, t["fc3.q4"], M, h3, bias=t.get("fc3.bias"), k_true=h2)
+        if fused or h3 % 4 == 0:
+            logits = BF.bn_hardtanh_linear_eval(z3, bn3, fc4, invstd=invstd3, out=b["y4"] if fused else None)
+        else:       # a width libbnn's BatchNorm passes do not take (as nets.MLP: torch's modules)
+            y = tF.batch_norm(z3, mean3, t["bn3.var"], g3, be3, False, 0.0, self.eps[2])
+            logits = tF.linear(tF.hardtanh(y), fc4.weight, fc4.bias)
+        return tF.log_softmax(logits, dim=1)
+
+    # ---- CPU restatement
+    @staticmethod
+    def _bn_sign(f, mean, invstd, gamma, beta):
+        """tsign(fmaf((f - mean) * invstd, gamma, beta)) as the kernels form it: the product and sum in
+        double are exact up to one rounding that cannot change the sign."""
+        tt = ((f - mean) * invstd).double()
+        g = gamma.double() if gamma is not None else 1.0
+        bb = beta.double() if beta is not None else 0.0
+        return _tsign((tt * g + bb).float())
+
+    def _forward_cpu(self, x):
+        t = self.t
+        h1, h2, h3 = self.widths
+        w1 = t["fc1.q"][:, :_K1].double()
+        if x.dtype == torch.uint8:
+            a, s0 = BF.pixel_affine(self.normalize)
+            a32 = torch.tensor(a, dtype=torch.float32).double()
+            S = (x.double() - 128.0) @ w1.t() + s0 * t["fc1.rowsum"].double()      # exact integers (+ s0 R)
+            z1 = (S * a32).float()
+        else:
+            z1 = (x.double() @ w1.t()).float()
+        if "fc1.bias" in t:
+            z1 = z1 + t["fc1.bias"]
+        s1 = self._bn_sign(z1, *self._bn(1))
+        z2 = (s1.double() @ _unpack_fp4_rows(t["fc2.q4"], h1).double().t()).float()
+        if "fc2.bias" in t:
+            z2 = z2 + t["fc2.bias"]
+        s2 = self._bn_sign(z2, *self._bn(2))
+        z3 = (s2.double() @ _unpack_fp4_rows(t["fc3.q4"], h2).double().t()).float()
+        if "fc3.bias" in t:
+            z3 = z3 + t["fc3.bias"]
+        mean3, invstd3, g3, be3 = self._bn(3)
+        y = (z3 - mean3) * invstd3
+        if g3 is not None:
+            y = y * g3
+        if be3 is not None:
+            y = y + be3
+        logits = tF.linear(tF.hardtanh(y), t["fc4.weight"], t.get("fc4.bias"))
+        return tF.log_softmax(logits, dim=1), [s1, s2]
+
+
+def freeze(model):
+    """Snapshot a trained nets.MLP for inference (see the module doc).  The weight source of each
+    binarized layer is ``weight.org`` when the layer carries one, else ``weight``.  Raises ValueError
+    for a BatchNorm without running statistics."""
+    widths, normalize, eps, t = FrozenMLP._snapshot(model)
+    return FrozenMLP(widths, normalize, eps, t, model)

@@ -29,8 +29,11 @@ from . import nets
 from .checkpoint import load_checkpoint, save_checkpoint
 from .graph import GraphedStep
 from .data import load_idx_dataset, shard_indices, synthetic_mnist
+from .inference import freeze
 from .optim import LatentAdam
 from .parallel import GradExchange
+
+EVAL_SEED = 4321     # --eval's held-out synthetic samples (the training set is seed 1234)
 
 
 class AverageMeter:
@@ -73,6 +76,8 @@ def parse(argv=None):
     ap.add_argument("--csv-prefix", default=None, help="write <prefix>_BATCH_TIME.csv / _EPOCH_TIME.csv")
     ap.add_argument("--checkpoint", default=None, help="write a latent-weight checkpoint here after every epoch")
     ap.add_argument("--resume", default=None, help="resume from a checkpoint written by --checkpoint")
+    ap.add_argument("--eval", type=int, default=0, metavar="N", help="after every epoch rank 0 freezes the model "
+                    "(bnn_amd.inference) and prints its accuracy on N held-out samples (MLP models)")
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--master-addr", default=os.environ.get("MASTER_ADDR", "127.0.0.1"))
     ap.add_argument("--master-port", default=os.environ.get("MASTER_PORT", "23456"))
@@ -122,6 +127,9 @@ def train(gpu, args):
     nb = (len(idx) + args.batch_size - 1) // args.batch_size
     T, E = [], []
     graphed = static_x = static_y = None
+    frozen = held_x = held_y = None
+    if args.eval > 0 and not isinstance(model, nets.MLP):
+        raise SystemExit("--eval freezes the binarized MLPs (mlp / small / wide), not --model " + args.model)
 
     def _step(xb, yb):
         for p in model.parameters():
@@ -183,6 +191,15 @@ def train(gpu, args):
         if rank == 0:
             print("Training ", epoch, " : " + str(datetime.now() - start), flush=True)
         E.append([datetime.now() - start])
+        if args.eval > 0 and rank == 0:
+            if frozen is None:
+                # held-out samples: a draw of bnn_amd.data the training set (seed 1234) does not use
+                held_x, held_y = synthetic_mnist(args.eval, seed=EVAL_SEED, device=device, as_u8=True)
+                frozen = freeze(model)
+            else:
+                frozen.refresh()
+            print("Eval {} : accuracy {:.4f} on {} held-out samples".format(
+                epoch, frozen.accuracy(held_x, held_y, batch=max(1, min(args.eval, 65536))), args.eval), flush=True)
         if args.checkpoint:
             save_checkpoint(args.checkpoint, model, opt, epoch)
     if rank == 0:

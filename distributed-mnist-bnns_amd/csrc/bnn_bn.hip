@@ -933,8 +933,13 @@ constexpr int HD_CG = HD_COLS / 4, HD_RS = 256 / HD_CG, HD_NI = HD_ROWS / HD_RS;
 static_assert(HD_NI == 8, "a thread's rows are one keep-bit word");
 
 typedef float hf4 __attribute__((ext_vector_type(4)));
+typedef double hd4 __attribute__((ext_vector_type(4)));
 
-template <int NOUT, bool Z16 = false, bool KB = false>
+// A64 (the eval-mode head of frozen-model inference, bnn_bn_head_eval): the same h3 in fp32, multiplied
+// into the head on the f64 MFMA (v_mfma_f64_16x16x4_f64: the f32 form's A / B lane layout, D rows interleaved) -- exact products,
+// double accumulation, one rounding of the logit.  The f32 form's 64-deep serial chain per 256 columns
+// measured 1.2e-6 against float64 at C = 256 where torch's F.linear has 3.3e-7.
+template <int NOUT, bool Z16 = false, bool KB = false, bool A64 = false>
 #ifndef HFWD_OCC
 #define HFWD_OCC 4             // waves per SIMD of the fused head's forward (z16 input)
 #endif
@@ -954,6 +959,7 @@ __global__ __launch_bounds__(256, Z16 ? HFWD_OCC : 2) void bn_head_fwd_k(XIn xin
   const int64_t r0 = (int64_t)blockIdx.x * HD_ROWS;
   const int cq = 4 * (t % HD_CG);
   hf4 acc = hf4{0.f, 0.f, 0.f, 0.f};
+  hd4 acc64 = hd4{0.0, 0.0, 0.0, 0.0};
   // software pipeline: chunk c0 + 128's x rows are fetched into registers before chunk c0 is
   // normalised and multiplied (the pass is latency-bound otherwise); W4's columns and the BatchNorm
   // parameters of the chunk (L2-resident) are loaded at its top, ahead of the barrier
@@ -1017,7 +1023,8 @@ __global__ __launch_bounds__(256, Z16 ? HFWD_OCC : 2) void bn_head_fwd_k(XIn xin
     for (int k0 = 0; k0 < HD_COLS; k0 += 4) {
       const float a = ht[(16 * wv + (lane & 15)) * HD_LD + k0 + (lane >> 4)];
       const float b = (lane & 15) < NOUT ? ws[(lane & 15) * HD_WLD + k0 + (lane >> 4)] : 0.f;
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+      if constexpr (A64) acc64 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a, (double)b, acc64, 0, 0, 0);
+      else acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
     }
   }
   const int col = lane & 15;
@@ -1025,8 +1032,9 @@ __global__ __launch_bounds__(256, Z16 ? HFWD_OCC : 2) void bn_head_fwd_k(XIn xin
     const float bias = b4 ? b4[col] : 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int64_t r = r0 + 16 * wv + 4 * (lane >> 4) + i;
-      if (r < M) y4[r * NOUT + col] = acc[i] + bias;
+      // D rows of a lane: the f32 form holds 4 consecutive rows, the f64 form rows (lane >> 4) + 4 i
+      const int64_t r = r0 + 16 * wv + (A64 ? 4 * i + (lane >> 4) : 4 * (lane >> 4) + i);
+      if (r < M) y4[r * NOUT + col] = A64 ? (float)(acc64[i] + (double)bias) : acc[i] + bias;
     }
   }
 }
@@ -2180,7 +2188,7 @@ BNN_API int64_t bnn_bn_head_workspace(int64_t M, int64_t C, int32_t nout) {
 static int bn_head_fwd_impl(XIn xin, bool z16, int64_t M, int64_t C, const float* mean, const float* invstd,
                             const float* mean_lo, const float* gamma, const float* beta, float p, uint64_t seed,
                             const uint32_t* keep_bits, const float* w4, int32_t nout, const float* b4, float* y4,
-                            void* stream) {
+                            void* stream, bool eval64 = false) {
   const float* x = reinterpret_cast<const float*>(xin.p);
   if (!(z16 ? bn_args_ok16(xin, M, C) : bn_args_ok(x, M, C)) || C % HD_COLS != 0 || !mean || !invstd || !w4 || !y4 ||
       nout != HEAD_NOUT || !aligned16(mean) || !aligned16(invstd) || !vec_ok(mean_lo) || !vec_ok(gamma) ||
@@ -2195,6 +2203,7 @@ static int bn_head_fwd_impl(XIn xin, bool z16, int64_t M, int64_t C, const float
   dp.bits = dp.on ? keep_bits : nullptr;
   auto k = z16 ? (dp.bits ? bn_head_fwd_k<HEAD_NOUT, true, true> : bn_head_fwd_k<HEAD_NOUT, true, false>)
                : (dp.bits ? bn_head_fwd_k<HEAD_NOUT, false, true> : bn_head_fwd_k<HEAD_NOUT, false, false>);
+  if (eval64) k = z16 ? bn_head_fwd_k<HEAD_NOUT, true, false, true> : bn_head_fwd_k<HEAD_NOUT, false, false, true>;
   hipLaunchKernelGGL(k, g, dim3(256), 0, s, xin, M, C, mean, mean_lo, invstd, gamma, beta, w4, b4, y4, dp);
   return check_launch("bnn_bn_head_fwd");
 }
@@ -2213,6 +2222,22 @@ BNN_API int bnn_bn_head_fwd_i16(const int16_t* x16, const float* xbias, int64_t 
                                 const float* b4, float* y4, void* stream) {
   return bn_head_fwd_impl(XIn{x16, xbias}, true, M, C, mean, invstd, mean_lo, gamma, beta, p, seed, keep_bits, w4,
                           nout, b4, y4, stream);
+}
+
+// The head in eval mode (frozen-model inference): bn -> htanh -> fc on given mean / invstd (the running
+// statistics), no dropout, the logits accumulated in double (bn_head_fwd_k A64).  Exactly one of x
+// (fp32 [M][C]) and x16 (int16 [M][C] with xbias: z = fl(x16 + xbias)); C % 128 == 0, nout == 10.
+BNN_API int bnn_bn_head_eval(const float* x, const int16_t* x16, const float* xbias, int64_t M, int64_t C,
+                             const float* mean, const float* invstd, const float* gamma, const float* beta,
+                             const float* w4, int32_t nout, const float* b4, float* y4, void* stream) {
+  if ((x == nullptr) == (x16 == nullptr)) {
+    set_error("bnn_bn_head_eval: bad arguments (exactly one of x / x16)");
+    return kErrInval;
+  }
+  return x ? bn_head_fwd_impl(XIn{x, nullptr}, false, M, C, mean, invstd, nullptr, gamma, beta, 0.f, 0, nullptr, w4,
+                              nout, b4, y4, stream, true)
+           : bn_head_fwd_impl(XIn{x16, xbias}, true, M, C, mean, invstd, nullptr, gamma, beta, 0.f, 0, nullptr, w4,
+                              nout, b4, y4, stream, true);
 }
 
 // Row chunks of the fused head's backward statistics pass: the BatchNorm chunks, but never fewer

@@ -50,6 +50,9 @@ __device__ __forceinline__ void out_store2u(void* p, uint32_t lo, uint32_t hi) {
 // +1 for x>0, -1 for x<0, 0 for x==0 (NaN maps to 0 here; the reference would propagate NaN).
 __device__ __forceinline__ int tsign(float x) { return (x > 0.f) - (x < 0.f); }
 
+// FP4 (e2m1) code of a ternary value: +1 = 0b0010, -1 = 0b1010, 0 = 0b0000.
+__device__ __forceinline__ uint32_t fp4_code(int s) { return s > 0 ? 0x2u : (s < 0 ? 0xAu : 0u); }
+
 // The input of a BatchNorm pass, in one of three forms (XF):
 //  0  fp32 x [M][C];
 //  1  (z16) the int16 exact dot products I of the ternary BinarizeLinear that produced it

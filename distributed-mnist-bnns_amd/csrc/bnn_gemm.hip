@@ -57,6 +57,15 @@ struct GemmParams {
   // [M][ldc] + high nibbles [M][ldc / 2] instead of fp32 C (XIn XF 2 in bnn_common.h)
   int16_t* S20lo = nullptr;
   uint8_t* S20hi = nullptr;
+  // BN-sign epilogue (the BNS instances: bnn_gemm_fp4_bnsign, bnn_gemm_i8_affine_bnsign): the FP4
+  // operand rows q4 [M][ldq4] of sign(BN(f)) with f the value the plain kernel would store, from
+  // eval-mode BatchNorm vectors (gamma / beta nullable); no C is written
+  const float* bn_mean = nullptr;
+  const float* bn_invstd = nullptr;
+  const float* bn_gamma = nullptr;
+  const float* bn_beta = nullptr;
+  uint8_t* Q4 = nullptr;
+  int64_t ldq4 = 0;
 };
 
 __device__ __forceinline__ double int_offset(const GemmParams& p, int row, int col) {
@@ -293,7 +302,7 @@ __device__ __forceinline__ void block_barrier() {
 }
 
 template <int DA, int DB, int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0,
-          int DIAG = 0, int F4 = 0, int S16 = 0, int BST = 0>
+          int DIAG = 0, int F4 = 0, int S16 = 0, int BST = 0, int BNS = 0>
 __device__ __forceinline__ void gemm_v2_body(const GemmParams& p) {
   // F4 = 1: both operands are ternary FP4 (e2m1) nibbles, 2 per byte; K and the LDS tiles are
   // counted in bytes (BKT bytes = 2*BKT elements); v_mfma_scale_f32_32x32x64_f8f6f4 with unit
@@ -305,6 +314,10 @@ __device__ __forceinline__ void gemm_v2_body(const GemmParams& p) {
   // (MI355X_MICROARCH.md, DVFS give-back item 7).  Needs BKT = 128 for conflict-free reads.
   static_assert(!F4 || (DA == 1 && DB == 1), "FP4 mode is the ternary x ternary form");
   static_assert(!S16 || BKT == 128, "16x16 tiles use the BK=128 swizzle");
+  // BNS = 1: the BN-sign epilogue.  The stored value f is formed as in the plain kernel, then
+  // y = BN(f) exactly as bn_apply_pack_fp4_k forms it, and only the FP4 code of sign(y) leaves: the
+  // patch carries the 4-bit codes, each patch row (32 codes) goes out as one 16-B store.
+  static_assert(!BNS || (DA == 1 && DB == 1 && DIAG == 0 && !BST), "BN-sign epilogue: the (1,1) forms");
   constexpr int TS = S16 ? 16 : 32;            // MFMA tile edge
   constexpr int TM = S16 ? 2 * WM : WM, TN = S16 ? 2 * WN : WN;
   constexpr int TR = TS * TS / 64;             // accumulator registers per tile
@@ -735,6 +748,15 @@ __device__ __forceinline__ void gemm_v2_body(const GemmParams& p) {
         const bool offs = p.row_off || p.col_off;
         const double coff = (p.col_off && cin) ? (double)p.col_off[col] * p.off_mul : 0.0;
         const int icoff = (int)coff;   // s20: exact (host check)
+        float mu = 0.f, is = 1.f, ga = 1.f, be = 0.f;
+        if constexpr (BNS) {
+          if (cin) {
+            mu = p.bn_mean[col];
+            is = p.bn_invstd[col];
+            if (p.bn_gamma) ga = p.bn_gamma[col];
+            if (p.bn_beta) be = p.bn_beta[col];
+          }
+        }
 #pragma unroll
         for (int sa = 0; sa < SUB; ++sa) {
           const int ti = t * SUB + sa, ui = u * SUB + sb;
@@ -769,13 +791,37 @@ __device__ __forceinline__ void gemm_v2_body(const GemmParams& p) {
               f = (float)(v * bs * (p.a_scale ? (double)p.a_scale[row] : 1.0));
             }
             if (p.bias && p.S20lo == nullptr) f += bb;
+            if constexpr (BNS) {
+              // columns >= N carry code 0: the K padding the next GEMM reads
+              const float y = fmaf(((f - mu) - 0.f) * is, ga, be);
+              f = __int_as_float(cin ? (int)fp4_code(tsign(y)) : 0);
+            }
             patch[lr * 32 + ((((lc >> 2) ^ (lr & 7)) << 2) | (lc & 3))] = f;
           }
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if constexpr (BNS) {
+        // lane = (patch row lane >> 1, half lane & 1): the half row's 16 codes = 4 chunks -> 8 B; the
+        // odd lane's 8 B move to the even lane (quad_perm [1,0,3,2]), which stores the row's 16 B
+        const int lr = lane >> 1, hf = lane & 1;
+        uint32_t w[2] = {0u, 0u};
 #pragma unroll
-      for (int ps = 0; ps < 4; ++ps) {
+        for (int j = 0; j < 4; ++j) {
+          const int c4 = 4 * hf + j;
+          const float4 v = *reinterpret_cast<const float4*>(patch + lr * 32 + ((c4 ^ (lr & 7)) << 2));
+          const uint32_t c = (uint32_t)__float_as_int(v.x) | ((uint32_t)__float_as_int(v.y) << 4) |
+                             ((uint32_t)__float_as_int(v.z) << 8) | ((uint32_t)__float_as_int(v.w) << 12);
+          w[j >> 1] |= c << (16 * (j & 1));
+        }
+        const uint32_t o0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)w[0], 0xB1, 0xF, 0xF, true);
+        const uint32_t o1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)w[1], 0xB1, 0xF, 0xF, true);
+        const int row = trow0 + lr;
+        if (hf == 0 && row < p.M)   // tcol0 < 2 ldq4: the grid's columns lie within the row (host check)
+          *reinterpret_cast<uint4*>(p.Q4 + (int64_t)row * p.ldq4 + (tcol0 >> 1)) = make_uint4(w[0], w[1], o0, o1);
+      }
+#pragma unroll
+      for (int ps = 0; ps < (BNS ? 0 : 4); ++ps) {
         const int lr = (lane >> 3) + 8 * ps, c4 = lane & 7;
         const float4 v = *reinterpret_cast<const float4*>(patch + lr * 32 + ((c4 ^ (lr & 7)) << 2));
         const int row = trow0 + lr, c0 = tcol0 + 4 * c4;
@@ -844,6 +890,44 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_fp4_k(GemmParams 
 template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0, int S16 = 0, int BST = 0>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void gemm_fp4_h_k(GemmParams p) {
   gemm_v2_body<1, 1, WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, 0, 1, S16, BST>(p);
+}
+
+// The BN-sign epilogue forms (BNS = 1) of the FP4 GEMM and of the (1,1) int8 GEMM: their own kernel
+// names, so traces tell them from the plain kernels
+template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0, int S16 = 0>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_fp4_bnsign_k(GemmParams p) {
+  gemm_v2_body<1, 1, WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, 0, 1, S16, 0, 1>(p);
+}
+
+template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_i8_bnsign_k(GemmParams p) {
+  gemm_v2_body<1, 1, WAVES_M, WAVES_N, WM, WN, STAGES, BKT, 0, 0, 0, 0, 0, 1>(p);
+}
+
+// Launch of a BN-sign form.  The grid's tiles cover columns 0 .. gn*BN-1 <= 2 ldq4 of every row
+// < M (codes 0 at columns >= N); the rest of the row's pad is cleared here.
+template <int F4, int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0, int S16 = 0>
+int launch_bnsign(GemmParams p, hipStream_t s) {
+  constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
+  p.gm = (p.M + BM - 1) / BM;
+  p.gn = (p.N + BN - 1) / BN;
+  const int64_t covered = (int64_t)p.gn * BN / 2;   // bytes of each q4 row the tiles write
+  if (covered < p.ldq4) {
+    const hipError_t e = hipMemset2DAsync(p.Q4 + covered, (size_t)p.ldq4, 0, (size_t)(p.ldq4 - covered), (size_t)p.M, s);
+    if (e != hipSuccess) {
+      set_error("bnn_gemm_bnsign: clearing the pad failed: %s", hipGetErrorString(e));
+      return (int)e;
+    }
+  }
+  const dim3 grid((unsigned)((int64_t)p.gm * p.gn)), block(64 * WAVES_M * WAVES_N);
+  if constexpr (F4) {
+    hipLaunchKernelGGL((gemm_fp4_bnsign_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, S16>), grid, block, 0, s, p);
+    return check_launch("bnn_gemm_fp4_bnsign");
+  } else {
+    static_assert(IL == 0 && S16 == 0, "int8 BN-sign form: the 32x32 BK=64 kernels");
+    hipLaunchKernelGGL((gemm_i8_bnsign_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT>), grid, block, 0, s, p);
+    return check_launch("bnn_gemm_i8_affine_bnsign");
+  }
 }
 
 template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0, int S16 = 0, int BST = 0>
@@ -1187,6 +1271,61 @@ BNN_API int bnn_gemm_fp4_bnstats(const uint8_t* A, int64_t lda, const uint8_t* B
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   return chunk == 128 ? launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 2, 0, 1, 1, 1>(p, st)
                       : launch_v2<1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 1, 0, 1>(p, st);
+}
+
+// ---- BN-sign epilogue entries (frozen-model inference: DESIGN.md §11) -------------------------
+// q4 row buffer of a BN-sign form: N % 4 == 0, ldq4 a multiple of 128 bytes covering round_up(N, 256)
+// nibbles, 16-B aligned
+static bool bnsign_out_ok(const float* mean, const float* invstd, const uint8_t* q4, int64_t ldq4, int64_t N) {
+  return mean && invstd && q4 && N % 4 == 0 && ldq4 > 0 && ldq4 % 128 == 0 && 2 * ldq4 >= round_up(N, 256) &&
+         aligned16(q4);
+}
+
+BNN_API int bnn_gemm_fp4_bnsign(const uint8_t* A, int64_t lda, const uint8_t* B, int64_t ldb, const float* bias,
+                                const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                uint8_t* q4, int64_t ldq4, int64_t M, int64_t N, int64_t K, void* stream) {
+  if (!A || !B || M < 0 || N < 0 || K <= 0 || K % BK != 0 || lda < K || ldb < K || lda % 16 != 0 ||
+      ldb % 16 != 0 || !aligned16(A) || !aligned16(B) || M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff ||
+      lda * 256 >= (1LL << 31) || ldb * 256 >= (1LL << 31) || !bnsign_out_ok(mean, invstd, q4, ldq4, N)) {
+    set_error("bnn_gemm_fp4_bnsign: bad arguments (M=%lld N=%lld K=%lld bytes ldq4=%lld; K a positive multiple "
+              "of 64, N %% 4 == 0, ldq4 %% 128 == 0 with 2 ldq4 >= round_up(N, 256), 16-B aligned q4)",
+              (long long)M, (long long)N, (long long)K, (long long)ldq4);
+    return kErrInval;
+  }
+  if (M == 0) return 0;
+  GemmParams p{reinterpret_cast<const int8_t*>(A), reinterpret_cast<const int8_t*>(B), lda, ldb, 0, 0,
+               nullptr, nullptr, bias, nullptr, 0, (int)M, (int)N, (int)K, 0, 0, nullptr, nullptr, 0.0};
+  p.bn_mean = mean, p.bn_invstd = invstd, p.bn_gamma = gamma, p.bn_beta = beta;
+  p.Q4 = q4, p.ldq4 = ldq4;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // the tile shapes of bnn_gemm_fp4's default table (variants 36 and 31; 31's also where K % 128 != 0)
+  const bool big = ((M + 255) / 256) * ((N + 255) / 256) >= 512;
+  return (big && K % 128 == 0) ? launch_bnsign<1, 2, 4, 4, 2, 2, 128, 2, 1>(p, st)
+                               : launch_bnsign<1, 2, 2, 2, 2, 3, 64, 0, 0>(p, st);
+}
+
+BNN_API int bnn_gemm_i8_affine_bnsign(const int8_t* A, int64_t lda, const int8_t* B, int64_t ldb,
+                                      const float* b_scale, const float* bias, const int64_t* col_off,
+                                      double off_mul, const float* mean, const float* invstd, const float* gamma,
+                                      const float* beta, uint8_t* q4, int64_t ldq4, int64_t M, int64_t N, int64_t K,
+                                      void* stream) {
+  if (!A || !B || M < 0 || N < 0 || K <= 0 || K % BK != 0 || lda < K || ldb < K || lda % 16 != 0 ||
+      ldb % 16 != 0 || !aligned16(A) || !aligned16(B) || M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff ||
+      lda * 256 >= (1LL << 31) || ldb * 256 >= (1LL << 31) || !bnsign_out_ok(mean, invstd, q4, ldq4, N)) {
+    set_error("bnn_gemm_i8_affine_bnsign: bad arguments (M=%lld N=%lld K=%lld ldq4=%lld; K a positive multiple "
+              "of 64, N %% 4 == 0, ldq4 %% 128 == 0 with 2 ldq4 >= round_up(N, 256), 16-B aligned q4)",
+              (long long)M, (long long)N, (long long)K, (long long)ldq4);
+    return kErrInval;
+  }
+  if (M == 0) return 0;
+  GemmParams p{A, B, lda, ldb, 0, 0, nullptr, b_scale, bias, nullptr, 0,
+               (int)M, (int)N, (int)K, 0, 0, nullptr, col_off, off_mul};
+  p.bn_mean = mean, p.bn_invstd = invstd, p.bn_gamma = gamma, p.bn_beta = beta;
+  p.Q4 = q4, p.ldq4 = ldq4;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // the BK=64 32x32 tiles the pixel GEMM's default table picks at K = 832 (variants 2 and 1)
+  const bool big = ((M + 255) / 256) * ((N + 255) / 256) >= 512;
+  return big ? launch_bnsign<0, 2, 4, 4, 2, 3, 64>(p, st) : launch_bnsign<0, 2, 2, 2, 2, 3, 64>(p, st);
 }
 
 BNN_API const char* bnn_gemm_i8_kernel(int32_t a_digits, int32_t b_digits, int64_t M, int64_t N,

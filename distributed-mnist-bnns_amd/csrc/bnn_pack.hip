@@ -41,9 +41,6 @@ __device__ __forceinline__ int pack4(int a, int b, int c, int d) {
   return (a & 255) | ((b & 255) << 8) | ((c & 255) << 16) | ((d & 255) << 24);
 }
 
-// FP4 (e2m1) code of a ternary value: +1 = 0b0010, -1 = 0b1010, 0 = 0b0000.
-__device__ __forceinline__ uint32_t fp4_code(int s) { return s > 0 ? 0x2u : (s < 0 ? 0xAu : 0u); }
-
 // Optional per-column affine map applied before the sign: the BatchNorm output
 // y = (x - mean) * invstd * gamma + beta, computed exactly as bn_apply_k does (bnn_bn.hip), so the
 // fused BN -> Hardtanh -> sign path sees bit-identical y (Hardtanh does not change a sign).

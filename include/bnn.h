@@ -205,6 +205,22 @@ int bnn_gemm_fp4(const uint8_t* A, int64_t lda, const uint8_t* B, int64_t ldb, c
 int bnn_gemm_fp4_i16(const uint8_t* A, int64_t lda, const uint8_t* B, int64_t ldb, int16_t* C16, int64_t ldc,
                      int64_t M, int64_t N, int64_t K, bnn_stream_t stream);
 
+/* Frozen-model inference (bnn_amd.inference): the hidden layers' GEMMs with the next layer's operand
+ * as their only output.
+ * bnn_gemm_fp4 whose epilogue is eval-mode BatchNorm -> Hardtanh -> sign-pack: q4 = FP4 rows of
+ * sign(BN(sum + bias)), bit-identical to bnn_gemm_fp4 followed by bnn_bn_apply_pack(fmt 1, qt NULL,
+ * mean_lo NULL).  N % 4 == 0; ldq4 a multiple of 128 with 2*ldq4 >= round_up(N,256); q4 16-B aligned.
+ * mean / invstd [N] are required, gamma / beta nullable (1 / 0).  On return the nibbles of columns
+ * N .. 2*ldq4-1 of every row < M are zero (the next GEMM's K padding); no fp32 activation is written. */
+int bnn_gemm_fp4_bnsign(const uint8_t* A, int64_t lda, const uint8_t* B, int64_t ldb, const float* bias,
+                        const float* mean, const float* invstd, const float* gamma, const float* beta,
+                        uint8_t* q4, int64_t ldq4, int64_t M, int64_t N, int64_t K, bnn_stream_t stream);
+/* the same on bnn_gemm_i8_affine's (1,1) u8-pixel form (fc1): b_scale, bias, col_off, off_mul as there */
+int bnn_gemm_i8_affine_bnsign(const int8_t* A, int64_t lda, const int8_t* B, int64_t ldb,
+                              const float* b_scale, const float* bias, const int64_t* col_off, double off_mul,
+                              const float* mean, const float* invstd, const float* gamma, const float* beta,
+                              uint8_t* q4, int64_t ldq4, int64_t M, int64_t N, int64_t K, bnn_stream_t stream);
+
 /* Tuning hook (not part of the stable contract): select the bnn_gemm_i8 kernel variant for all
  * later calls in this process; -1 restores the built-in default table (tools/gemm_sweep.py). */
 int bnn_gemm_set_variant(int32_t variant);
@@ -567,6 +583,13 @@ int bnn_bn_head_fwd_i16(const int16_t* x16, const float* xbias, int64_t M, int64
                         const float* invstd, const float* mean_lo, const float* gamma, const float* beta, float p,
                         uint64_t seed, const uint32_t* keep_bits, const float* w4, int32_t nout, const float* b4,
                         float* y4, bnn_stream_t stream);
+/* The head in eval mode (frozen-model inference): y4 = fc(hardtanh(bn(z))) on given mean / invstd (the
+ * running mean and (running_var + eps)^-1/2), no dropout; h3 formed in fp32 as bnn_bn_head_fwd forms it,
+ * the logits accumulated in double and rounded once.  Exactly one of x (fp32 [M][C]) and x16 (int16
+ * [M][C] with xbias: z = fl(x16 + xbias)); C % 128 == 0, nout == 10; gamma / beta nullable. */
+int bnn_bn_head_eval(const float* x, const int16_t* x16, const float* xbias, int64_t M, int64_t C,
+                     const float* mean, const float* invstd, const float* gamma, const float* beta,
+                     const float* w4, int32_t nout, const float* b4, float* y4, bnn_stream_t stream);
 int bnn_bn_head_bwd_q6_i16(const int16_t* x16, const float* xbias, const float* dy4, const float* w4, int32_t nout,
                            int64_t M, int64_t C, const float* gamma, const float* beta, const float* save_mean,
                            const float* save_invstd, const float* save_mean_lo, float p, uint64_t seed,
