@@ -4,15 +4,16 @@ Layers: ``functional`` (libbnn.so ops + autograd Functions), ``nn`` (BinarizeLin
 BinarizeConv2d modules with the reference's ``weight.org`` protocol), ``parallel`` (RCCL
 bucketed gradient exchange), ``optim`` (fused latent Adam + clamp), ``nets`` / ``trainer``
 (the reference's training loop restated), ``data`` (synthetic MNIST + sampler), ``inference``
-(``freeze(model) -> FrozenMLP``: a trained MLP packed once and run without the float model).
+(``freeze(model) -> FrozenMLP / FrozenCNN``: a trained network packed once and run without the float
+model).
 """
 __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # ``from bnn_amd import freeze, FrozenMLP`` (frozen-model inference) without importing torch
+    # ``from bnn_amd import freeze, FrozenMLP, FrozenCNN`` (frozen-model inference) without importing torch
     # for users of the package's lighter modules
-    if name in ("freeze", "FrozenMLP"):
+    if name in ("freeze", "FrozenMLP", "FrozenCNN"):
         from . import inference
         return getattr(inference, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -98,6 +98,12 @@ SIGNATURES = {
     "bnn_bn2d_bwd_q": (I32, [P, P, I32, P, I64, I64, I64, I64, P, P, P, P, I32, I32, P, P, P, P, P]),
     "bnn_conv2d_fwd_q": (I32, [P, P, P, I32, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, P]),
     "bnn_conv2d_fwd_q_ok": (I32, [I32, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32]),
+    "bnn_conv2d_fwd_bnsign_pool_ok": (I32, [I32, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32]),
+    "bnn_conv2d_fwd_bnsign_pool": (I32, [P, I32, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32,
+                                         I32, I32, P]),
+    "bnn_conv2d_fwd_bn_pool_linear_ok": (I32, [I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, I32]),
+    "bnn_conv2d_fwd_bn_pool_linear": (I32, [P, P, P, P, P, P, P, P, P, I32, P, I64, I64, I64, I64, I64, I64, I64, I32,
+                                            I32, I32, I32, P]),
     "bnn_bn_dropout_fwd_train": (I32, [P, I64, I64, P, P, P, P, F32, F32, P, P, P, P, I32, F32, U64, P, P, P]),
     "bnn_dropout_keep_bits_bytes": (I64, [I64, I64]),
     "bnn_bn_set_head_reduce_cols": (I32, [I32]),

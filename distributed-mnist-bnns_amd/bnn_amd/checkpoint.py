@@ -90,15 +90,19 @@ def load_checkpoint(path, model, optimizer=None, map_location=None):
 
 
 def save_frozen(path, frozen):
-    """Write a ``bnn_amd.inference.FrozenMLP`` -- packed tensors plus widths and the pixel Normalize --
-    for inference without the float model.  Atomic, as ``save_checkpoint``."""
+    """Write a ``bnn_amd.inference.FrozenMLP`` or ``FrozenCNN`` -- packed tensors plus widths / layer
+    geometry and the pixel Normalize -- for inference without the float model.  Atomic, as
+    ``save_checkpoint``."""
     tmp = f"{path}.tmp"
     torch.save(frozen.state_dict(), tmp)
     os.replace(tmp, path)
 
 
 def load_frozen(path, map_location=None):
-    """The ``FrozenMLP`` written by ``save_frozen`` (on ``map_location``, default: where it was saved)."""
-    from .inference import FrozenMLP
+    """The ``FrozenMLP`` or ``FrozenCNN`` written by ``save_frozen`` (on ``map_location``, default: where it
+    was saved); the state's format string tells which."""
+    from .inference import FORMAT_CNN, FrozenCNN, FrozenMLP
     state = torch.load(path, map_location=map_location, weights_only=True)
+    if state.get("format") == FORMAT_CNN:
+        return FrozenCNN.from_state(state)
     return FrozenMLP.from_state(state)

@@ -1,4 +1,5 @@
-"""Frozen-model inference for the binarized MLPs (nets.MLP and its Net / SmallNet / WideNet widths).
+"""Frozen-model inference for the binarized MLPs (nets.MLP and its Net / SmallNet / WideNet widths) and the
+binarized CNN (nets.BinCNN -> FrozenCNN, at the end of this module).
 
 ``freeze(model)`` snapshots a trained network once -- fc1's int8 weight rows and their row sums, fc2
 and fc3's FP4 weight rows, every bias, each BatchNorm's running mean / invstd / gamma / beta, fc4 --
@@ -24,7 +25,7 @@ from . import _lib as L
 from . import functional as BF
 from . import nets
 
-__all__ = ["freeze", "FrozenMLP"]
+__all__ = ["freeze", "FrozenMLP", "FrozenCNN"]
 
 FORMAT = "bnn_amd.frozen/1"
 _K1 = 28 * 28
@@ -310,9 +311,350 @@ class FrozenMLP:
         return tF.log_softmax(logits, dim=1), [s1, s2]
 
 
-def freeze(model):
-    """Snapshot a trained nets.MLP for inference (see the module doc).  The weight source of each
-    binarized layer is ``weight.org`` when the layer carries one, else ``weight``.  Raises ValueError
-    for a BatchNorm without running statistics."""
+# ====================================================================== the binarized CNN
+FORMAT_CNN = "bnn_amd.frozen_cnn/1"
+
+
+def _pick_co(co):
+    return 8 if co <= 8 else 16 if co <= 16 else 32 if co <= 32 else 64
+
+
+def _pack_conv_rows(w):
+    """[Co, C, KH, KW] (C % 16 == 0) -> int8 [round_up(Co, 16), KCp * 16]: the LDS image of libbnn's int8-MFMA
+    conv, byte (kh KW + kw) C + c of row co = tsign(w[co, c, kh, kw]), KCp = round_up(KH KW C / 16, 4), zeros
+    in every pad."""
+    Co, C, KH, KW = w.shape
+    kc = KH * KW * C // 16
+    q = torch.zeros((BF.round_up(Co, 16), BF.round_up(kc, 4) * 16), dtype=torch.int8, device=w.device)
+    q[:Co, :KH * KW * C] = _tsign(w).permute(0, 2, 3, 1).reshape(Co, KH * KW * C)
+    return q
+
+
+def _unpack_conv_rows(q, Co, C, KH, KW):
+    return q[:Co, :KH * KW * C].reshape(Co, KH, KW, C).permute(0, 3, 1, 2).contiguous()
+
+
+def _pack_conv_c1(w):
+    """[Co, 1, KH, KW] (KW <= 8) -> int8 [KH, KWG, CO, 4] (KWG = 1 for KW <= 4 else 2, CO = 8 / 16 / 32 / 64):
+    byte j of word (kh, g, co) = tsign(w[co, 0, kh, 4 g + j]), zero for 4 g + j >= KW and co >= Co -- the
+    dot4 words of libbnn's single-channel conv."""
+    Co, _, KH, KW = w.shape
+    kwg = 1 if KW <= 4 else 2
+    q = torch.zeros((KH, kwg * 4, _pick_co(Co)), dtype=torch.int8, device=w.device)
+    q[:, :KW, :Co] = _tsign(w)[:, 0].permute(1, 2, 0)
+    return q.reshape(KH, kwg, 4, -1).permute(0, 1, 3, 2).contiguous()
+
+
+def _unpack_conv_c1(q, Co, KW):
+    KH, kwg, CO, _ = q.shape
+    return q.permute(0, 1, 3, 2).reshape(KH, kwg * 4, CO)[:, :KW, :Co].permute(2, 0, 1).unsqueeze(1).contiguous()
+
+
+def pixel_sign_table(normalize=None):
+    """int8 [256]: tsign of the fp32 value the data pipeline makes of each byte (ToTensor, then Normalize)."""
+    return _tsign(BF.pixels_to_float(torch.arange(256, dtype=torch.uint8), normalize))
+
+
+def _invstd(var, eps):
+    """bit-identical to libbnn's bn_invstd_k: float(1 / sqrt(double(var) + double(float32(eps))))."""
+    e = float(torch.tensor(eps, dtype=torch.float32))
+    return (1.0 / torch.sqrt(var.detach().double().cpu() + e)).float().to(var.device)
+
+
+class FrozenCNN:
+    """A frozen nets.BinCNN: per conv layer the packed sign weights, bias and the BatchNorm2d's running
+    mean / var / invstd / gamma / beta; the classifier; the 256-entry pixel sign table.
+
+        u8 pixels -> conv1 [BN-sign-pool epilogue] -> int8 signs [N, 14, 14, 16]
+                  -> conv2 [BN-pool-Linear epilogue] -> logits -> log-softmax
+
+    Hardtanh and MaxPool2d are monotone, so the next layer's operand sign(maxpool(hardtanh(bn(z)))) is the
+    window maximum of sign(bn(z)): the hidden layer writes 1 B per pooled element and no fp32 map
+    (bnn_conv2d_fwd_bnsign_pool), the last one goes straight to the logits (bnn_conv2d_fwd_bn_pool_linear,
+    sums in double).  ``two_pass = True`` runs every layer as conv + bnn_bn2d_fwd_eval (+ linear_nsmall /
+    F.linear), the form ``model.eval()`` runs; a layer whose shape the fused kernels do not take falls back
+    to it by itself.  No host synchronisation, buffers kept per batch size (graph capture works); CPU
+    tensors run a plain-torch restatement (a checking path)."""
+
+    def __init__(self, layers, in_hw, normalize, eps, tensors, model=None):
+        # layers: per conv (C, Co, KH, KW, pad)
+        self.layers = [tuple(int(v) for v in l) for l in layers]
+        self.in_hw = (int(in_hw[0]), int(in_hw[1]))
+        self.normalize = None if normalize is None else (float(normalize[0]), float(normalize[1]))
+        self.eps = tuple(float(e) for e in eps)
+        self.t = dict(tensors)
+        self._model = model
+        self._buf = {}
+        self.two_pass = False
+
+    # ------------------------------------------------------------------ snapshot
+    @staticmethod
+    def _snapshot(model, normalize):
+        if not isinstance(model, nets.BinCNN):
+            raise TypeError("freeze: expects a bnn_amd.nets.BinCNN")
+        from .nn import BinarizeConv2d
+        import torch.nn as tnn
+        t, layers, eps = {}, [], []
+        for i, seq in enumerate((model.layer1, model.layer2), 1):
+            ok = (isinstance(seq, tnn.Sequential) and len(seq) == 4 and isinstance(seq[0], BinarizeConv2d)
+                  and isinstance(seq[1], tnn.BatchNorm2d) and isinstance(seq[2], tnn.Hardtanh)
+                  and seq[2].min_val == -1.0 and seq[2].max_val == 1.0 and isinstance(seq[3], tnn.MaxPool2d))
+            if ok:
+                pool = seq[3]
+                pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+                ok = (pair(pool.kernel_size) == (2, 2) and pair(pool.stride) == (2, 2) and pair(pool.padding) == (0, 0)
+                      and pair(pool.dilation) == (1, 1) and not pool.ceil_mode)
+            if not ok:
+                raise ValueError(f"freeze: layer{i} must be BinarizeConv2d -> BatchNorm2d -> Hardtanh(-1, 1) -> "
+                                 "MaxPool2d(2, 2) without padding or ceil_mode (the sign commutes with exactly that)")
+            conv, bn = seq[0], seq[1]
+            if bn.running_mean is None or bn.running_var is None:
+                raise ValueError(f"freeze: layer{i}'s BatchNorm2d keeps no running statistics "
+                                 "(track_running_stats=False); a frozen network needs them")
+            if (tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.groups != 1
+                    or conv.padding[0] != conv.padding[1] or conv.in_channels == 3):
+                raise ValueError(f"freeze: layer{i}'s convolution must have stride 1, dilation 1, one group, square "
+                                 "padding and a binarised input (in_channels != 3)")
+            w = _latent(conv.weight).float()
+            Co, C, KH, KW = w.shape
+            layers.append((C, Co, KH, KW, conv.padding[0]))
+            t[f"conv{i}.sign"] = _tsign(w)
+            if C == 1 and KW <= 8:
+                t[f"conv{i}.wq"] = _pack_conv_c1(w)
+            elif C % 16 == 0:
+                t[f"conv{i}.wq"] = _pack_conv_rows(w)
+            if conv.bias is not None:
+                t[f"conv{i}.bias"] = conv.bias.detach().float().clone()
+            t[f"bn{i}.mean"] = bn.running_mean.detach().float().clone()
+            t[f"bn{i}.var"] = bn.running_var.detach().float().clone()
+            t[f"bn{i}.invstd"] = _invstd(bn.running_var, bn.eps)
+            if bn.weight is not None:
+                t[f"bn{i}.gamma"] = bn.weight.detach().float().clone()
+            if bn.bias is not None:
+                t[f"bn{i}.beta"] = bn.bias.detach().float().clone()
+            eps.append(bn.eps)
+        if layers[0][0] != 1:
+            raise ValueError("freeze: the first convolution must take one-channel images")
+        t["fc.weight"] = model.fc.weight.detach().float().contiguous().clone()
+        if model.fc.bias is not None:
+            t["fc.bias"] = model.fc.bias.detach().float().clone()
+        t["pixel.table"] = pixel_sign_table(normalize).to(t["fc.weight"].device)
+        return layers, (28, 28), normalize, eps, t
+
+    def refresh(self):
+        """Re-snapshot the model this was frozen from (after more training)."""
+        if self._model is None:
+            raise RuntimeError("FrozenCNN.refresh: this snapshot was loaded from a state, not frozen from a model")
+        two = self.two_pass
+        self.__init__(*self._snapshot(self._model, self.normalize), self._model)
+        self.two_pass = two
+        return self
+
+    # ------------------------------------------------------------------ persistence
+    def state_dict(self):
+        """Tensors, numbers and strings only (torch.load(weights_only=True) reads it back)."""
+        return {"format": FORMAT_CNN, "layers": [list(l) for l in self.layers], "in_hw": list(self.in_hw),
+                "normalize": None if self.normalize is None else list(self.normalize),
+                "eps": list(self.eps), "tensors": {k: v.detach().clone() for k, v in self.t.items()}}
+
+    @classmethod
+    def from_state(cls, state, device=None):
+        if state.get("format") != FORMAT_CNN:
+            raise ValueError(f"FrozenCNN.from_state: not a {FORMAT_CNN} state (format={state.get('format')!r})")
+        t = {k: (v.to(device) if device is not None else v.clone()) for k, v in state["tensors"].items()}
+        return cls(state["layers"], state["in_hw"], state["normalize"], state["eps"], t)
+
+    def to(self, device):
+        self.t = {k: v.to(device) for k, v in self.t.items()}
+        self._buf = {}
+        return self
+
+    @property
+    def device(self):
+        return self.t["fc.weight"].device
+
+    # ------------------------------------------------------------------ forward
+    def _bn(self, i):
+        t = self.t
+        return t[f"bn{i}.mean"], t[f"bn{i}.invstd"], t.get(f"bn{i}.gamma"), t.get(f"bn{i}.beta")
+
+    def _images(self, x):
+        H, W = self.in_hw
+        if x.dim() == 2 and x.shape[1] == H * W:
+            x = x.reshape(x.shape[0], 1, H, W)
+        if x.dim() != 4 or tuple(x.shape[1:]) != (1, H, W):
+            raise ValueError(f"FrozenCNN: expects [N, {H * W}] or [N, 1, {H}, {W}] inputs (got {tuple(x.shape)})")
+        if x.dtype not in (torch.uint8, torch.float32):
+            raise TypeError(f"FrozenCNN: uint8 pixels or float32 images (got {x.dtype})")
+        return x
+
+    def forward(self, x):
+        """log-probabilities [N, 10] of u8 pixels (the Normalize given to freeze applied) or fp32 images."""
+        x = self._images(x)
+        if not x.is_cuda:
+            return self._forward_cpu(x)[0]
+        return self._forward_gpu(x)[0]
+
+    __call__ = forward
+
+    def predict(self, x):
+        """int64 class labels [N]."""
+        return self.forward(x).argmax(dim=1)
+
+    accuracy = FrozenMLP.accuracy
+
+    def hidden_signs(self, x):
+        """Layer 1's pooled signs sign(maxpool(hardtanh(bn1(conv1(x))))), int8 NCHW [N, Co, H/2, W/2]."""
+        x = self._images(x)
+        if not x.is_cuda:
+            return self._forward_cpu(x)[1]
+        cur, form, Co = self._forward_gpu(x)[1]
+        if form == "s8":
+            return cur[..., :Co].permute(0, 3, 1, 2).contiguous()
+        return _tsign(cur)
+
+    # ---- GPU
+    def _shapes(self):
+        """Per layer (C, Co, K.., pad, H, W, PH, PW) along the net."""
+        H, W = self.in_hw
+        out = []
+        for C, Co, KH, KW, pad in self.layers:
+            OH, OW = H + 2 * pad - KH + 1, W + 2 * pad - KW + 1
+            out.append((C, Co, KH, KW, pad, H, W, OH // 2, OW // 2))
+            H, W = OH // 2, OW // 2
+        return out
+
+    def _buffers(self, N, device):
+        key = (N, str(device))
+        b = self._buf.get(key)
+        if b is None:
+            b = {"y": torch.empty((N, self.t["fc.weight"].shape[0]), dtype=torch.float32, device=device)}
+            for i, (C, Co, KH, KW, pad, H, W, PH, PW) in enumerate(self._shapes()[:-1], 1):
+                b[f"a{i}"] = torch.empty((N, PH, PW, BF.round_up(Co, 16)), dtype=torch.int8, device=device)
+            self._buf[key] = b
+        return b
+
+    def _wf(self, i):
+        """fp32 sign weights of layer i for the two-pass form's conv (its kernel takes a latent fp32 weight)."""
+        k = f"conv{i}.wf"
+        w = self._buf.get(k)
+        if w is None or w.device != self.t[f"conv{i}.sign"].device:
+            w = self._buf[k] = self.t[f"conv{i}.sign"].float().contiguous()
+        return w
+
+    def _two_pass_layer(self, i, x, shp):
+        """Layer i as model.eval() runs it: conv (binarising x, fp32 NCHW) -> bnn_bn2d_fwd_eval with Hardtanh and
+        the 2x2 pool -> fp32 pooled map."""
+        C, Co, KH, KW, pad, H, W, PH, PW = shp
+        N = x.shape[0]
+        z = BF.binary_conv2d(x, self._wf(i), self.t.get(f"conv{i}.bias"), True, 1, pad, 1, 1)
+        y = torch.empty((N, Co, PH, PW), dtype=torch.float32, device=x.device)
+        ws = torch.empty((L.lib().bnn_bn2d_workspace(N, Co),), dtype=torch.uint8, device=x.device)
+        mean, _, gamma, beta = self._bn(i)
+        L.call("bnn_bn2d_fwd_eval", L.ptr(z), N, Co, z.shape[2], z.shape[3], L.ptr(gamma), L.ptr(beta), L.ptr(mean),
+               L.ptr(self.t[f"bn{i}.var"]), float(self.eps[i - 1]), L.ptr(y), 1, 2, L.ptr(ws), L.stream())
+        return y
+
+    @staticmethod
+    def _signs_nhwc(y):
+        """fp32 NCHW pooled map -> int8 channels-innermost signs, channels padded to a multiple of 16."""
+        N, C, H, W = y.shape
+        a = torch.zeros((N, H, W, BF.round_up(C, 16)), dtype=torch.int8, device=y.device)
+        a[..., :C] = _tsign(y).permute(0, 2, 3, 1)
+        return a
+
+    def _forward_gpu(self, x):
+        t = self.t
+        if t["fc.weight"].device != x.device:
+            raise RuntimeError(f"FrozenCNN on {self.device} got an input on {x.device}; call .to(device)")
+        N = x.shape[0]
+        n_out = t["fc.weight"].shape[0]
+        if N == 0:
+            return torch.empty((0, n_out), dtype=torch.float32, device=x.device), None
+        x = x if x.is_contiguous() else x.contiguous()
+        b = self._buffers(N, x.device)
+        shapes = self._shapes()
+        cur, form = x, ("u8" if x.dtype == torch.uint8 else "f32")      # form: u8 / f32 (NCHW) / s8 (NHWC signs)
+        hidden = None
+        for i, shp in enumerate(shapes, 1):
+            C, Co, KH, KW, pad, H, W, PH, PW = shp
+            last = i == len(shapes)
+            mean, invstd, gamma, beta = self._bn(i)
+            wq = t.get(f"conv{i}.wq")
+            geo = (N, C, H, W, Co, KH, KW, 1, pad, 1, 1)
+            if last:
+                fused = (not self.two_pass and wq is not None and C % 16 == 0
+                         and t["fc.weight"].shape[1] == Co * PH * PW
+                         and L.lib().bnn_conv2d_fwd_bn_pool_linear_ok(*geo, n_out) == 1)
+            else:
+                xfmt = {"f32": 0, "u8": 1, "s8": 2}[form]
+                fused = (not self.two_pass and wq is not None
+                         and L.lib().bnn_conv2d_fwd_bnsign_pool_ok(xfmt, *geo) == 1)
+            if fused and last:
+                if form != "s8":
+                    cur, form = self._signs_nhwc(cur if form == "f32" else BF.pixels_to_float(cur, self.normalize)), "s8"
+                L.call("bnn_conv2d_fwd_bn_pool_linear", L.ptr(cur), L.ptr(wq), L.ptr(t.get(f"conv{i}.bias")),
+                       L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), L.ptr(t["fc.weight"]),
+                       L.ptr(t.get("fc.bias")), n_out, L.ptr(b["y"]), *geo, L.stream())
+                logits = b["y"]
+            elif fused:
+                out = b[f"a{i}"]
+                L.call("bnn_conv2d_fwd_bnsign_pool", L.ptr(cur), xfmt, L.ptr(t["pixel.table"]), L.ptr(wq),
+                       L.ptr(t.get(f"conv{i}.bias")), L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta),
+                       L.ptr(out), *geo, L.stream())
+                cur, form = out, "s8"
+            else:
+                if form == "u8":
+                    cur = BF.pixels_to_float(cur, self.normalize)
+                elif form == "s8":
+                    cur = cur[..., :C].permute(0, 3, 1, 2).float().contiguous()
+                cur, form = self._two_pass_layer(i, cur, shp), "f32"
+                if last:
+                    flat = cur.reshape(N, -1)
+                    if BF.linear_nsmall_ok(flat, t["fc.weight"]):
+                        logits = BF.linear_nsmall(flat, t["fc.weight"], t.get("fc.bias"))
+                    else:
+                        logits = tF.linear(flat, t["fc.weight"], t.get("fc.bias"))
+            if i == 1 and not last:
+                hidden = (cur, form, Co)
+        return tF.log_softmax(logits, dim=1), hidden
+
+    # ---- CPU restatement
+    def _forward_cpu(self, x):
+        t = self.t
+        if x.dtype == torch.uint8:
+            s = t["pixel.table"].to(torch.int64)[x.long()].double()
+        else:
+            s = _tsign(x).double()
+        shapes = self._shapes()
+        hidden = None
+        for i, (C, Co, KH, KW, pad, H, W, PH, PW) in enumerate(shapes, 1):
+            I = tF.conv2d(s, t[f"conv{i}.sign"].double(), None, 1, pad)          # exact integer sums
+            z = I.float()
+            if f"conv{i}.bias" in t:
+                z = z + t[f"conv{i}.bias"].view(1, -1, 1, 1)
+            mean, invstd, gamma, beta = (None if v is None else v.view(1, -1, 1, 1) for v in self._bn(i))
+            xh = ((z - mean) * invstd).double()
+            g = gamma.double() if gamma is not None else 1.0
+            bb = beta.double() if beta is not None else 0.0
+            y = (xh * g + bb).float()                       # fmaf: the exact product and sum, rounded once
+            p = tF.max_pool2d(tF.hardtanh(y), 2, 2)
+            if i == 1:
+                hidden = _tsign(p)
+            s = _tsign(p).double()
+        logits = tF.linear(p.reshape(p.shape[0], -1), t["fc.weight"], t.get("fc.bias"))
+        return tF.log_softmax(logits, dim=1), hidden
+
+
+def freeze(model, normalize=None):
+    """Snapshot a trained network for inference (see the module doc): nets.MLP -> FrozenMLP, nets.BinCNN ->
+    FrozenCNN.  The weight source of each binarized layer is ``weight.org`` when the layer carries one, else
+    ``weight``.  ``normalize`` = (mean, std) is the Normalize the u8 pixels of a BinCNN go through (an MLP
+    carries its own in ``fc1.pixel_normalize``).  Raises ValueError for a BatchNorm without running
+    statistics or a CNN layer that is not conv -> BatchNorm2d -> Hardtanh(-1, 1) -> MaxPool2d(2, 2)."""
+    if isinstance(model, nets.BinCNN):
+        return FrozenCNN(*FrozenCNN._snapshot(model, normalize), model)
+    if normalize is not None:
+        raise ValueError("freeze: normalize applies to a BinCNN; an MLP carries fc1.pixel_normalize")
     widths, normalize, eps, t = FrozenMLP._snapshot(model)
     return FrozenMLP(widths, normalize, eps, t, model)

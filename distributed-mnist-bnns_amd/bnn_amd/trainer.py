@@ -77,7 +77,7 @@ def parse(argv=None):
     ap.add_argument("--checkpoint", default=None, help="write a latent-weight checkpoint here after every epoch")
     ap.add_argument("--resume", default=None, help="resume from a checkpoint written by --checkpoint")
     ap.add_argument("--eval", type=int, default=0, metavar="N", help="after every epoch rank 0 freezes the model "
-                    "(bnn_amd.inference) and prints its accuracy on N held-out samples (MLP models)")
+                    "(bnn_amd.inference) and prints its accuracy on N held-out samples")
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--master-addr", default=os.environ.get("MASTER_ADDR", "127.0.0.1"))
     ap.add_argument("--master-port", default=os.environ.get("MASTER_PORT", "23456"))
@@ -128,8 +128,8 @@ def train(gpu, args):
     T, E = [], []
     graphed = static_x = static_y = None
     frozen = held_x = held_y = None
-    if args.eval > 0 and not isinstance(model, nets.MLP):
-        raise SystemExit("--eval freezes the binarized MLPs (mlp / small / wide), not --model " + args.model)
+    if args.eval > 0 and not isinstance(model, (nets.MLP, nets.BinCNN)):
+        raise SystemExit("--eval freezes the binarized MLPs (mlp / small / wide) and the cnn, not --model " + args.model)
 
     def _step(xb, yb):
         for p in model.parameters():

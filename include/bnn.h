@@ -339,6 +339,45 @@ int bnn_conv2d_fwd_q(const float* x, const float* w_latent, void* y, int32_t yfm
  * bnn_conv_set_mfma), else 0: the host asks before emitting a compact conv output. */
 int bnn_conv2d_fwd_q_ok(int32_t yfmt, int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
                         int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+/* Frozen-model inference (bnn_amd.inference.FrozenCNN): the binary convolution with eval-mode
+ * BatchNorm2d -> Hardtanh -> MaxPool2d(2, 2) in its epilogue.  Geometry of both entries: stride 1,
+ * dilation 1, groups 1, C == 1 (KW <= 8) or C % 16 == 0 (<= 64, at most 256 output pixels), Co <= 64,
+ * pad <= K - 1, even OH and OW; anything else returns -1 and launches nothing (the _ok queries tell).
+ * mean / invstd [Co] are the running mean and (running_var + eps)^-1/2; bias / gamma / beta nullable.
+ *
+ * wq: the weight's ternary signs as int8, packed once by the host, 16-B aligned.
+ *   C % 16 == 0: [round_up(Co, 16)][KCp * 16], KCp = round_up(KH KW C / 16, 4), byte (tap kh KW + kw) C + c of
+ *                row co = sign(W[co][c][kh][kw]); pad rows and pad bytes 0 (conv_fwd_i8mfma_k's LDS image).
+ *   C == 1:      [KH][KWG][CO][4], KWG = 1 (KW <= 4) or 2, CO = 8 / 16 / 32 / 64 (the smallest >= Co): byte j of
+ *                word (kh, g, co) = sign(W[co][0][kh][4 g + j]); 0 for 4 g + j >= KW and co >= Co.
+ *
+ * bnn_conv2d_fwd_bnsign_pool: x in one of three forms -- xfmt 0: fp32 NCHW, binarised in the kernel;
+ * 1: u8 pixels [N][H][W] (C == 1) mapped through table[256] (int8 signs, 4-B aligned); 2: int8 signs
+ * channels-innermost [N][H][W][C] (16-B aligned) -- to out = int8 signs [N][OH/2][OW/2][round_up(Co, 16)]
+ * (16-B aligned; pad channels 0; nothing beyond sample N is written): per element x = fl(I + bias[c]),
+ * y = fmaf((x - mean[c]) * invstd[c], gamma[c], beta[c]); a window gives +1 if some y > 0, else 0 if some
+ * y == 0, else -1, and 0 if it holds a NaN -- tsign of the fp32 window maximum of torch's
+ * Hardtanh -> MaxPool2d (replaces bnn_conv2d_fwd + bnn_bn2d_fwd_eval(hardtanh, pool 2) + sign).
+ *
+ * bnn_conv2d_fwd_bn_pool_linear: x int8 signs [N][H][W][C] (C % 16 == 0) to logits [N][10] =
+ * Linear(fcw [10][Co PH PW] in NCHW flatten order, fcb nullable) of the pooled Hardtanh map, which is
+ * never written.  Past x = fl(I + bias[c]) every step is in double and the sum has a fixed order, so the
+ * logits are deterministic, carry one rounding to fp32, and a sample's do not depend on N or its place
+ * in the batch.  n_out must be 10; conv weights + image + fcw must fit one workgroup's LDS. */
+int bnn_conv2d_fwd_bnsign_pool_ok(int32_t xfmt, int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                  int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int bnn_conv2d_fwd_bnsign_pool(const void* x, int32_t xfmt, const int8_t* table, const int8_t* wq, const float* bias,
+                               const float* mean, const float* invstd, const float* gamma, const float* beta,
+                               int8_t* out, int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                               int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups,
+                               bnn_stream_t stream);
+int bnn_conv2d_fwd_bn_pool_linear_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                                     int32_t stride, int32_t pad, int32_t dil, int32_t groups, int32_t n_out);
+int bnn_conv2d_fwd_bn_pool_linear(const int8_t* x, const int8_t* wq, const float* bias, const float* mean,
+                                  const float* invstd, const float* gamma, const float* beta, const float* fcw,
+                                  const float* fcb, int32_t n_out, float* logits, int64_t N, int64_t C, int64_t H,
+                                  int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad,
+                                  int32_t dil, int32_t groups, bnn_stream_t stream);
 int bnn_conv2d_bwd_data(const float* dy, const float* w_latent, float* dx, int64_t N, int64_t C,
                         int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride,
                         int32_t pad, int32_t dil, int32_t groups, bnn_stream_t stream);

@@ -7,7 +7,10 @@ In one process, alternating per repeat:
   (b) frozen  -- freeze(model)(u): BN-sign GEMM epilogues + the eval head;
   (c) frozen2 -- the frozen forward with every hidden layer in its two-pass form (GEMM + bn_apply_pack),
                  which separates the epilogue's share from the head's and the bookkeeping's.
-Sizes: WideNet at batch 65,536; Net at 4,096 and 10,000 (``--only wide:65536`` picks one).  Each leg is
+Sizes: WideNet at batch 65,536; Net at 4,096 and 10,000 (``--only wide:65536`` picks one); ``--only
+cnn:4096`` times the BinCNN the same way -- (a) model.eval() on the fp32 images, (b) FrozenCNN on the u8
+pixels (conv epilogues: BN-sign-pool, BN-pool-Linear), (c) FrozenCNN with every layer as conv +
+bnn_bn2d_fwd_eval (+ linear_nsmall).  Each leg is
 warmed up, then timed with device events over ~``--seconds`` of work per repeat; the line printed is one
 JSON object with the median ms per batch of every leg, every repeat's figure, the per-layer epilogue
 bytes computed from the shapes, and labels_equal, the fraction of rows on which (a) and (b) agree.
@@ -45,7 +48,76 @@ def _time_leg(fn, seconds):
     return e0.elapsed_time(e1) / n, n
 
 
+def _time_legs(legs, seconds, repeats):
+    outs = {k: f() for k, f in legs.items()}          # warm-up (packs the weight caches, allocates buffers)
+    for f in legs.values():
+        f()
+    torch.cuda.synchronize()
+    runs = {k: [] for k in legs}
+    iters = {}
+    for _ in range(repeats):
+        for k, f in legs.items():
+            ms, n = _time_leg(f, seconds)
+            runs[k].append(round(ms, 4))
+            iters[k] = n
+    return outs, runs, iters
+
+
+def run_cnn(batch, seconds, repeats):
+    from bnn_amd import freeze, nets
+    from bnn_amd import functional as BF
+    from bnn_amd.data import synthetic_mnist
+    torch.manual_seed(0)
+    model = nets.BinCNN(org_protocol=False, mutate_input=False, fused_bn=True).cuda().eval()
+    with torch.no_grad():          # running statistics of the scale the layers produce
+        for bn, fan_in in ((model.layer1[1], 25 * 0.2), (model.layer2[1], 400)):
+            bn.running_mean.normal_(0.0, 0.2 * fan_in ** 0.5)
+            bn.running_var.uniform_(0.5 * fan_in, 1.5 * fan_in)
+    u, _ = synthetic_mnist(batch, seed=5, device="cuda", as_u8=True)
+    xf = BF.pixels_to_float(u)
+    fz = freeze(model)
+
+    def leg_eval():
+        with torch.no_grad():
+            return model(xf)
+
+    def leg_frozen():
+        fz.two_pass = False
+        return fz(u)
+
+    def leg_frozen2():
+        fz.two_pass = True
+        out = fz(u)
+        fz.two_pass = False
+        return out
+
+    outs, runs, iters = _time_legs({"eval": leg_eval, "frozen": leg_frozen, "frozen_two_pass": leg_frozen2},
+                                   seconds, repeats)
+    fz.two_pass = True
+    h2 = fz.hidden_signs(u)
+    fz.two_pass = False
+    shp = fz._shapes()
+    per = {}
+    for i, (C, Co, KH, KW, pad, H, W, PH, PW) in enumerate(shp, 1):
+        full, pooled = Co * 4 * PH * PW * 4, Co * PH * PW * 4
+        # eval: conv writes fp32, bn2d reads it and writes the pooled fp32 map, the consumer reads that
+        per[f"layer{i}"] = {"eval_bytes": int(batch * (2 * full + 2 * pooled)),
+                            "frozen_bytes": int(batch * (2 * PH * PW * ((Co + 15) // 16 * 16) if i < len(shp) else 40))}
+    return {"net": "cnn", "batch": batch,
+            "eval_ms": round(statistics.median(runs["eval"]), 4),
+            "frozen_ms": round(statistics.median(runs["frozen"]), 4),
+            "frozen_two_pass_ms": round(statistics.median(runs["frozen_two_pass"]), 4),
+            "runs_ms": runs, "iters_per_run": iters,
+            "labels_equal": float((outs["eval"].argmax(1) == outs["frozen"].argmax(1)).float().mean()),
+            "two_pass_labels_equal": float((outs["frozen_two_pass"].argmax(1) == outs["frozen"].argmax(1)).float().mean()),
+            "two_pass_hidden_signs_identical": bool(torch.equal(fz.hidden_signs(u), h2)),
+            "max_abs_diff_to_eval": float((outs["eval"] - outs["frozen"]).abs().max()),
+            "intermediate_bytes": per}
+
+
 def run_size(name, batch, seconds, repeats):
+    if name == "cnn":
+        return run_cnn(batch, seconds, repeats)
     from bnn_amd import freeze, nets
     from bnn_amd.data import synthetic_mnist
     torch.manual_seed(0)
@@ -74,18 +146,8 @@ def run_size(name, batch, seconds, repeats):
         fz.two_pass = False
         return out
 
-    legs = {"eval": leg_eval, "frozen": leg_frozen, "frozen_two_pass": leg_frozen2}
-    outs = {k: f() for k, f in legs.items()}          # warm-up (packs the weight caches, allocates buffers)
-    for f in legs.values():
-        f()
-    torch.cuda.synchronize()
-    runs = {k: [] for k in legs}
-    iters = {}
-    for _ in range(repeats):
-        for k, f in legs.items():
-            ms, n = _time_leg(f, seconds)
-            runs[k].append(round(ms, 4))
-            iters[k] = n
+    outs, runs, iters = _time_legs({"eval": leg_eval, "frozen": leg_frozen, "frozen_two_pass": leg_frozen2},
+                                   seconds, repeats)
     h1, h2, h3 = fz.widths
     epi = {f"fc{i}": {"two_pass_bytes": int(batch * h * 8.5), "bnsign_bytes": int(batch * h * 0.5)}
            for i, h in ((1, h1), (2, h2))}
