@@ -101,8 +101,5 @@ def save_frozen(path, frozen):
 def load_frozen(path, map_location=None):
     """The ``FrozenMLP`` or ``FrozenCNN`` written by ``save_frozen`` (on ``map_location``, default: where it
     was saved); the state's format string tells which."""
-    from .inference import FORMAT_CNN, FrozenCNN, FrozenMLP
-    state = torch.load(path, map_location=map_location, weights_only=True)
-    if state.get("format") == FORMAT_CNN:
-        return FrozenCNN.from_state(state)
-    return FrozenMLP.from_state(state)
+    from .inference import from_state
+    return from_state(torch.load(path, map_location=map_location, weights_only=True))

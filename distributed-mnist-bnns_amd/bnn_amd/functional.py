@@ -2306,52 +2306,76 @@ def gemm_i8_affine_bnsign(A, B, M, N, b_scale, bias, col_off, off_mul, mean, inv
     return q4
 
 
-def head_eval_fusable(C, fc):
+def head_eval_fusable(C, in_features, out_features):
     """bn -> htanh -> fc as the fused head on running statistics: C % 128 == 0 and a 10-way fc."""
-    return C % 128 == 0 and fc.out_features == HEAD_NOUT and fc.in_features == C
+    return C % 128 == 0 and out_features == HEAD_NOUT and in_features == C
+
+
+_HEAD_NO_STATS = "bn_hardtanh_linear_eval needs a BatchNorm with running statistics"
+_HEAD_Z16 = "bn_hardtanh_linear_eval: an int16 pre-activation needs the fused head (head_eval_fusable)"
+
+
+def bn_head_eval(z, mean, invstd, gamma, beta, w4, b4, out=None):
+    """fc(hardtanh(bn(z))) as the fused head on running statistics (head_eval_fusable shapes), without
+    autograd: bnn_bn_head_eval, bnn_bn_head_fwd[_i16]'s kernel with the logits accumulated in double
+    (that kernel's fp32 chain measured 1.2e-6 against float64 where F.linear has 3.3e-7: DESIGN.md §11).
+    z: fp32 [M, C], or the pair (int16 dot products [M, C], fp32 bias [C]) of gemm_fp4_i16."""
+    z16 = isinstance(z, (tuple, list))
+    if mean is None or invstd is None:
+        raise ValueError(_HEAD_NO_STATS)
+    x = z[0] if z16 else _c2d(z)
+    M, C = x.shape
+    if not head_eval_fusable(C, w4.shape[1], w4.shape[0]):
+        raise ValueError(_HEAD_Z16 if z16 else f"bn_head_eval: C = {C} with a {tuple(w4.shape)} fc is not "
+                         "head_eval_fusable")
+    _check(x, dtype=torch.int16 if z16 else torch.float32)
+    w4 = w4 if w4.is_contiguous() else w4.contiguous()
+    y4 = torch.empty((M, HEAD_NOUT), dtype=torch.float32, device=x.device) if out is None else out
+    if M == 0:
+        return y4
+    with _timed("bn_head_fwd [eval]", 0, (2 if z16 else 4) * M * C + 4 * M * HEAD_NOUT):
+        L.call("bnn_bn_head_eval", None if z16 else L.ptr(x), L.ptr(x) if z16 else None,
+               L.ptr(z[1]) if z16 else None, M, C, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), L.ptr(w4),
+               HEAD_NOUT, L.ptr(b4), L.ptr(y4), L.stream())
+    return y4
+
+
+def bn_linear_eval(z, mean, var, eps, gamma, beta, w4, b4):
+    """The same for every other shape: bnn_bn_fwd_eval (BatchNorm on running statistics + Hardtanh) and
+    F.linear.  z: fp32 [M, C] only."""
+    if isinstance(z, (tuple, list)):
+        raise ValueError(_HEAD_Z16)
+    if mean is None or var is None:
+        raise ValueError(_HEAD_NO_STATS)
+    x = _c2d(z)
+    _check(x)
+    M, C = x.shape
+    if M == 0:
+        return torch.empty((0, w4.shape[0]), dtype=torch.float32, device=x.device)
+    h = torch.empty_like(x)
+    with _timed("bn_fwd_eval", 0, 8 * M * C):
+        L.call("bnn_bn_fwd_eval", L.ptr(x), M, C, L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(var),
+               float(eps), L.ptr(h), 1, L.ptr(_bn_ws(M, C, x.device)), L.stream())
+    return torch.nn.functional.linear(h, w4 if w4.is_contiguous() else w4.contiguous(), b4)
 
 
 def bn_hardtanh_linear_eval(z, bn, fc, invstd=None, out=None):
-    """fc(hardtanh(bn(z))) in eval mode, without autograd: the fused head on the running statistics
-    -- mean = running_mean, invstd = (running_var + eps).rsqrt(), no dropout -- when
-    head_eval_fusable; otherwise bnn_bn_fwd_eval + F.linear.  The fused form is bnn_bn_head_eval:
-    bnn_bn_head_fwd[_i16]'s kernel with the logits accumulated in double (that kernel's fp32 chain
-    measured 1.2e-6 against float64 where F.linear has 3.3e-7: DESIGN.md §11).
+    """fc(hardtanh(bn(z))) in eval mode on modules: bn_head_eval -- mean = running_mean, invstd =
+    (running_var + eps).rsqrt(), no dropout -- when head_eval_fusable, otherwise bn_linear_eval.
 
-    z: fp32 [M, C], or the pair (int16 dot products [M, C], fp32 bias [C]) of gemm_fp4_i16 (fused head
-    only).  bn / fc: modules or any objects with running_mean, running_var, eps, weight, bias /
-    weight, bias, in_features, out_features.  invstd: (running_var + eps).rsqrt() when the caller
-    already holds it."""
+    z: as bn_head_eval's (the int16 pair: fused head only).  bn / fc: modules or any objects with
+    running_mean, running_var, eps, weight, bias / weight, bias, in_features, out_features.  invstd:
+    (running_var + eps).rsqrt() when the caller already holds it."""
     z16 = isinstance(z, (tuple, list))
     x = z[0] if z16 else _c2d(z)
     _check(x, dtype=torch.int16 if z16 else torch.float32)
     if bn.running_mean is None or bn.running_var is None:
-        raise ValueError("bn_hardtanh_linear_eval needs a BatchNorm with running statistics")
-    M, C = x.shape
+        raise ValueError(_HEAD_NO_STATS)
     gw = bn.weight.detach() if bn.weight is not None else None
     gb = bn.bias.detach() if bn.bias is not None else None
-    w4 = fc.weight.detach()
-    w4 = w4 if w4.is_contiguous() else w4.contiguous()
     b4 = fc.bias.detach() if fc.bias is not None else None
-    rm = bn.running_mean
-    if head_eval_fusable(C, fc):
+    if head_eval_fusable(x.shape[1], fc.in_features, fc.out_features):
         if invstd is None:
             invstd = (bn.running_var + bn.eps).rsqrt()
-        y4 = torch.empty((M, HEAD_NOUT), dtype=torch.float32, device=x.device) if out is None else out
-        if M == 0:
-            return y4
-        with _timed("bn_head_fwd [eval]", 0, (2 if z16 else 4) * M * C + 4 * M * HEAD_NOUT):
-            L.call("bnn_bn_head_eval", None if z16 else L.ptr(x), L.ptr(x) if z16 else None,
-                   L.ptr(z[1]) if z16 else None, M, C, L.ptr(rm), L.ptr(invstd), L.ptr(gw), L.ptr(gb), L.ptr(w4),
-                   HEAD_NOUT, L.ptr(b4), L.ptr(y4), L.stream())
-        return y4
-    if z16:
-        raise ValueError("bn_hardtanh_linear_eval: an int16 pre-activation needs the fused head "
-                         "(head_eval_fusable)")
-    if M == 0:
-        return torch.empty((0, fc.out_features), dtype=torch.float32, device=x.device)
-    h = torch.empty_like(x)
-    with _timed("bn_fwd_eval", 0, 8 * M * C):
-        L.call("bnn_bn_fwd_eval", L.ptr(x), M, C, L.ptr(gw), L.ptr(gb), L.ptr(rm), L.ptr(bn.running_var),
-               float(bn.eps), L.ptr(h), 1, L.ptr(_bn_ws(M, C, x.device)), L.stream())
-    return torch.nn.functional.linear(h, w4, b4)
+        return bn_head_eval(z, bn.running_mean, invstd, gw, gb, fc.weight.detach(), b4, out)
+    return bn_linear_eval(z, bn.running_mean, bn.running_var, bn.eps, gw, gb, fc.weight.detach(), b4)

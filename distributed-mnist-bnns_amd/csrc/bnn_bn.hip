@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256, RED_OCC) void bn_reduce_k(XIn xin, const float
         const float gs[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float xh = ((xs[j] - mu[j]) - lo[j]) * is[j];
+          const float xh = bn_xh1(xs[j], mu[j], lo[j], is[j]);
           const float y = fmaf(xh, ga[j], be[j]);
           const float g = (!hardtanh || (y > -1.f && y < 1.f)) ? gs[j] : 0.f;
           fa[j] += g;
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) void bn_apply_k(const float* __restrict__ x, i
     float v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      v[j] = fmaf(((xs[j] - mu[j]) - lo[j]) * is[j], ga[j], be[j]);
+      v[j] = bn_y1(xs[j], mu[j], lo[j], is[j], ga[j], be[j]);
       if (hardtanh) v[j] = fminf(fmaxf(v[j], -1.f), 1.f);
     }
     *reinterpret_cast<float4*>(y + r * C + c) = make_float4(v[0], v[1], v[2], v[3]);
@@ -1007,7 +1007,7 @@ __global__ __launch_bounds__(256, Z16 ? HFWD_OCC : 2) void bn_head_fwd_k(XIn xin
         else drop4(dp, (uint64_t)(r * C + c), xs);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          h[j] = fminf(fmaxf(fmaf(((xs[j] - mu[j]) - lo[j]) * is[j], ga[j], be[j]), -1.f), 1.f);
+          h[j] = fminf(fmaxf(bn_y1(xs[j], mu[j], lo[j], is[j], ga[j], be[j]), -1.f), 1.f);
       }
       *reinterpret_cast<float4*>(ht + rr * HD_LD + cq) = make_float4(h[0], h[1], h[2], h[3]);
     }
@@ -1116,7 +1116,7 @@ __global__ __launch_bounds__(256, HRED_OCC) void bn_head_reduce_k(XIn xin, const
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const int j = 2 * jp + e;
-          const float xh = ((xs[j] - mu[j]) - lo[j]) * is[j];
+          const float xh = bn_xh1(xs[j], mu[j], lo[j], is[j]);
           const float y = fmaf(xh, ga[j], be[j]);
           const bool in = y > -1.f && y < 1.f;
           const float g = in ? (e ? gs2.y : gs2.x) : 0.f;
@@ -1248,7 +1248,7 @@ __global__ __launch_bounds__(256, 4) void bn_head_reduce2_k(XIn xin, const float
         float hh[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          const float xh = ((xs[e] - mu[e]) - lo[e]) * is[e];
+          const float xh = bn_xh1(xs[e], mu[e], lo[e], is[e]);
           const float y = fmaf(xh, ga[e], be[e]);
           const bool in = y > -1.f && y < 1.f;
           const float g = in ? (e ? gs2.y : gs2.x) : 0.f;
@@ -1472,7 +1472,7 @@ __global__ __launch_bounds__(BN2_T) void bn2d_reduce_k(X2 x, const float* __rest
       const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float xh = (xs[q] - k.mu) * k.is;
+        const float xh = bn_xh1(xs[q], k.mu, 0.f, k.is);
         const float y = fmaf(xh, k.ga, k.be);
         const float g = (!hardtanh || (y > -1.f && y < 1.f)) ? gs[q] : 0.f;
         fa += g;
@@ -1721,8 +1721,8 @@ __global__ __launch_bounds__(256) void bn2d_apply_k(X2 x, int64_t N, int64_t C, 
     const int64_t c = ((4 * i) / HW) % C;
     const Bn2Chan k = bn2_chan(c, mean, invstd, gamma, beta);
     const float4 xv = x2_ld4<XF, true>(x, 4 * i, x2_bias<XF>(x, c));
-    float v[4] = {fmaf((xv.x - k.mu) * k.is, k.ga, k.be), fmaf((xv.y - k.mu) * k.is, k.ga, k.be),
-                  fmaf((xv.z - k.mu) * k.is, k.ga, k.be), fmaf((xv.w - k.mu) * k.is, k.ga, k.be)};
+    float v[4] = {bn_y1(xv.x, k.mu, 0.f, k.is, k.ga, k.be), bn_y1(xv.y, k.mu, 0.f, k.is, k.ga, k.be),
+                  bn_y1(xv.z, k.mu, 0.f, k.is, k.ga, k.be), bn_y1(xv.w, k.mu, 0.f, k.is, k.ga, k.be)};
     if (hardtanh) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = fminf(fmaxf(v[j], -1.f), 1.f);
@@ -1773,7 +1773,7 @@ __global__ __launch_bounds__(256) void bn2d_bwd_apply_k(X2 x, const float* __res
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float xh = (xs[j] - k.mu) * k.is;
+      const float xh = bn_xh1(xs[j], k.mu, 0.f, k.is);
       const float yv = fmaf(xh, k.ga, k.be);
       const float g = (!hardtanh || (yv > -1.f && yv < 1.f)) ? gs[j] : 0.f;
       o[j] = sc * (g - m0 - xh * m1);

@@ -31,7 +31,7 @@ __device__ __forceinline__ Win bn2_window(float2 top, float2 bot, const Bn2Chan&
   int arg = 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    w.xh[j] = (xs[j] - k.mu) * k.is;
+    w.xh[j] = bn_xh1(xs[j], k.mu, 0.f, k.is);
     w.y[j] = fmaf(w.xh[j], k.ga, k.be);
     const float v = hardtanh ? fminf(fmaxf(w.y[j], -1.f), 1.f) : w.y[j];
     if (v > best || v != v) {

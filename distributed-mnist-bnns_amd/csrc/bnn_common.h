@@ -135,8 +135,21 @@ __device__ __forceinline__ float4 xin_load4(const XIn& in, int64_t idx, const fl
   return xin_cvt4<XF>(xin_raw4<XF>(in, idx), b, in.scale);
 }
 
+// The BatchNorm forward for one element: xh = ((x - mean) - mean_lo) * invstd (two subtractions and a
+// product, each rounded) and y = fmaf(xh, gamma, beta) (rounded once).  One definition for every pass that
+// forms y or its sign -- the apply / apply-pack / Hardtanh / head passes, the statistics passes of the
+// backward (which rebuild y for the Hardtanh mask), the BatchNorm2d window, and the BN-sign epilogues of
+// the GEMMs and convolutions, which tests hold byte-identical to GEMM + bn_apply_pack and conv +
+// bn2d_fwd_eval -- so they agree bit for bit.  A pass without a mean_lo passes 0.f (x - 0.f is x for
+// every float, -0.f and NaN included).
+__device__ __forceinline__ float bn_xh1(float x, float m, float lo, float is) { return ((x - m) - lo) * is; }
+
+__device__ __forceinline__ float bn_y1(float x, float m, float lo, float is, float ga, float be) {
+  return fmaf(bn_xh1(x, m, lo, is), ga, be);
+}
+
 // The training-mode BatchNorm(+Hardtanh) backward for one element (mnist-dist2.py:66-74): with
-// xh = ((x - mean) - mean_lo) * invstd, y = xh*gamma + beta, g = dy masked by -1 < y < 1,
+// xh = bn_xh1(x), y = xh*gamma + beta, g = dy masked by -1 < y < 1,
 // dz = gamma*invstd*(g - a0 - xh*a1), a0 = sum(g)/M, a1 = sum(g*xh)/M.  One definition for every
 // pass that forms dz (bn_bwd_apply_k, the fused FP6 and int8 quantising passes), so they agree
 // bit for bit.
@@ -144,7 +157,7 @@ __device__ __forceinline__ float bn_dz1(float x, float g, float m, float lo, flo
                                         float a1, int hardtanh) {
   // no mul+add contraction: the rounding must not depend on the kernel this is inlined into
 #pragma clang fp contract(off)
-  const float xh = ((x - m) - lo) * is;
+  const float xh = bn_xh1(x, m, lo, is);
   const float yv = fmaf(xh, ga, be);
   const float gg = (!hardtanh || (yv > -1.f && yv < 1.f)) ? g : 0.f;
   return ga * is * (gg - a0 - xh * a1);

@@ -58,13 +58,12 @@ __device__ __forceinline__ double quad_max(double v) {
   return fmax(v, dpp_quad_d(v, true));
 }
 
-// y of one element exactly as conv + bnn_bn2d_fwd_eval form it: x = fl(I + bias), then bn2_window's
-// expression (bnn_bn2d.h)
+// y of one element as conv + bnn_bn2d_fwd_eval form it: x = fl(I + bias), then the shared element bn_y1
+// (bnn_common.h), which bn2_window goes through as well
 __device__ __forceinline__ float bn_y(int I, float b, float mu, float is, float ga, float be) {
 #pragma clang fp contract(off)
   const float x = (float)I + b;
-  const float xh = (x - mu) * is;
-  return fmaf(xh, ga, be);
+  return bn_y1(x, mu, 0.f, is, ga, be);
 }
 
 // bit r of a nibble -> bit 8 r (the four terms occupy disjoint bits: no carries)

@@ -793,7 +793,7 @@ __device__ __forceinline__ void gemm_v2_body(const GemmParams& p) {
             if (p.bias && p.S20lo == nullptr) f += bb;
             if constexpr (BNS) {
               // columns >= N carry code 0: the K padding the next GEMM reads
-              const float y = fmaf(((f - mu) - 0.f) * is, ga, be);
+              const float y = bn_y1(f, mu, 0.f, is, ga, be);
               f = __int_as_float(cin ? (int)fp4_code(tsign(y)) : 0);
             }
             patch[lr * 32 + ((((lc >> 2) ^ (lr & 7)) << 2) | (lc & 3))] = f;

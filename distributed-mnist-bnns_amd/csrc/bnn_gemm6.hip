@@ -864,7 +864,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
           const float gs[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float xh = ((xs[j] - bm[j]) - bl[j]) * bi[j];
+            const float xh = bn_xh1(xs[j], bm[j], bl[j], bi[j]);
             const float y = fmaf(xh, bg[j], bbt[j]);
             const float g = (!p.bn.hardtanh || (y > -1.f && y < 1.f)) ? gs[j] : 0.f;
             st0[j] += g;

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict_
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float y = v[j];
-        if (AFF) y = (mr < M && cb + j < K) ? fmaf(((y - mu[j]) - lo[j]) * is[j], ga[j], be[j]) : 0.f;
+        if (AFF) y = (mr < M && cb + j < K) ? bn_y1(y, mu[j], lo[j], is[j], ga[j], be[j]) : 0.f;
         tile[rr][ac + j] = tsign(y);
       }
     }
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict_
     if (AFF) {
 #pragma unroll
       for (int j = 0; j < 16; ++j)
-        v[j] = (m < M && cb + j < K) ? fmaf(((v[j] - mu[j]) - lo[j]) * is[j], ga[j], be[j]) : 0.f;
+        v[j] = (m < M && cb + j < K) ? bn_y1(v[j], mu[j], lo[j], is[j], ga[j], be[j]) : 0.f;
     }
 #pragma unroll
     for (int j = 0; j < 16; ++j) s[j] = tsign(v[j]);
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(256) void bn_apply_pack_fp4_k(XIn xin, int64_t M, i
       int sg[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        sg[j] = IDN ? tsign(v[j]) : tsign(fmaf(((v[j] - mu[j]) - lo[j]) * is[j], ga[j], be[j]));
+        sg[j] = IDN ? tsign(v[j]) : tsign(bn_y1(v[j], mu[j], lo[j], is[j], ga[j], be[j]));
         code |= fp4_code(sg[j]) << (4 * j);
       }
       *reinterpret_cast<uint16_t*>(q + m * ldq + k0 / 2 + 2 * lane) = (uint16_t)code;

@@ -237,6 +237,42 @@ def test_frozen_two_pass_form_is_bit_identical(trained):
         fz.two_pass = False
 
 
+def test_frozen_mixed_widths_fused_two_pass_refresh_and_state(F):
+    """Widths (192, 256, 128) at M = 37: h1 % 128 != 0 puts fc1 on the small BN-sign tile and h3 = 128 is the
+    fused head's minimum width.  The fused forward equals its two-pass form bit for bit, hidden signs
+    included; refresh() keeps two_pass and the output; a state round trip onto the GPU gives the same bits."""
+    from bnn_amd import freeze, inference, nets
+    from bnn_amd.data import synthetic_mnist
+    torch.manual_seed(7)
+    model = nets.MLP(192, 256, 128, org_protocol=False, mutate_input=False, fused_bn=True).cuda().eval()
+    g = torch.Generator(device="cuda").manual_seed(8)
+    with torch.no_grad():
+        for bn, scale in ((model.bn1, 30.0), (model.bn2, 12.0), (model.bn3, 12.0)):
+            n = bn.num_features
+            bn.running_mean.copy_(torch.randn(n, generator=g, device="cuda") * 0.3 * scale)
+            bn.running_var.copy_((torch.rand(n, generator=g, device="cuda") + 0.5) * scale * scale)
+            bn.weight.copy_(torch.rand(n, generator=g, device="cuda") + 0.5)
+            bn.weight[5] = -0.75
+    u, _ = synthetic_mnist(37, seed=12, device="cuda", as_u8=True)
+    fz = freeze(model)
+    assert F.head_eval_fusable(128, 128, 10) and fz.widths == (192, 256, 128)
+    want = fz(u).clone()
+    signs = fz.hidden_signs(u)
+    assert want.shape == (37, 10) and torch.isfinite(want).all()
+    assert [tuple(s.shape) for s in signs] == [(37, 192), (37, 256)] and all((s != 0).any() for s in signs)
+    fz.two_pass = True
+    assert torch.equal(fz(u), want)
+    assert all(torch.equal(a, b) for a, b in zip(fz.hidden_signs(u), signs))
+    fz.refresh()
+    assert fz.two_pass is True and fz._buf == {} and torch.equal(fz(u), want)
+    fz.two_pass = False
+    assert torch.equal(fz(u), want)
+    again = inference.from_state(fz.state_dict(), device="cuda")
+    assert again.device == u.device and torch.equal(again(u), want)
+    with pytest.raises(RuntimeError, match=r"FrozenMLP on cpu got an input on cuda:0; call \.to\(device\)"):
+        again.to("cpu")(u)
+
+
 def test_frozen_fp32_images_give_the_same_labels(F, trained):
     t = trained[256]
     x = F.pixels_to_float(t["u"])                        # ToTensor's images of the same pixels

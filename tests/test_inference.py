@@ -99,6 +99,82 @@ def test_frozen_state_round_trips(tmp_path):
         loaded.refresh()
 
 
+def test_refresh_keeps_two_pass_and_drops_the_buffers():
+    from bnn_amd import freeze
+    from bnn_amd.inference import _unpack_fp4_rows
+    m = _model()
+    fz = freeze(m)
+    fz.two_pass = True
+    fz._buffers(3, torch.device("cpu"))
+    assert fz._buf
+    with torch.no_grad():
+        m.fc3.weight.neg_()
+    want = m.fc3.weight.detach().sign()
+    assert fz.refresh() is fz
+    assert fz.two_pass is True
+    assert torch.equal(_unpack_fp4_rows(fz.t["fc3.q4"], 192).float(), want)
+    assert fz._buf == {}
+
+
+def parent_state(fz, meta):
+    """The dictionary the state_dict() of the commit that introduced the formats wrote, rebuilt by hand:
+    ``meta`` is that commit's literal list of (key, value) pairs after "format"."""
+    return {"format": meta[0], **dict(meta[1:]), "tensors": {k: v.clone() for k, v in fz.t.items()}}
+
+
+def check_parent_state_loads(fz, state, keys, u, tmp_path):
+    from bnn_amd import inference
+    from bnn_amd.checkpoint import load_frozen
+    assert list(state) == keys
+    path = str(tmp_path / "parent.pt")
+    torch.save(state, path)
+    want = fz.forward(u)
+    for got in (inference.from_state(state), load_frozen(path)):
+        assert type(got) is type(fz)
+        again = got.state_dict()
+        assert list(again) == keys
+        assert all(again[k] == state[k] for k in keys[:-1])
+        assert list(again["tensors"]) == list(state["tensors"])
+        assert all(torch.equal(again["tensors"][k], v) and again["tensors"][k].dtype == v.dtype
+                   for k, v in state["tensors"].items())
+        assert torch.equal(got.forward(u), want)
+
+
+def test_a_state_written_by_the_parent_format_loads(tmp_path):
+    from bnn_amd import freeze, inference
+    fz = freeze(_model(seed=4, normalize=(0.1307, 0.3081)))
+    state = parent_state(fz, ["bnn_amd.frozen/1", ("widths", [192, 192, 192]), ("normalize", [0.1307, 0.3081]),
+                              ("eps", [1e-05, 1e-05, 1e-05])])
+    assert sorted(state["tensors"]) == sorted(
+        [f"bn{i}.{k}" for i in (1, 2, 3) for k in ("mean", "var", "invstd", "gamma", "beta")]
+        + ["fc1.q", "fc1.rowsum", "fc2.q4", "fc3.q4", "fc1.bias", "fc2.bias", "fc3.bias", "fc4.weight", "fc4.bias"])
+    check_parent_state_loads(fz, state, ["format", "widths", "normalize", "eps", "tensors"], _pixels(19, seed=8),
+                             tmp_path)
+    with pytest.raises(ValueError, match=r"bnn_amd\.frozen/1.*bnn_amd\.frozen_cnn/1"):
+        inference.from_state({"format": "x"})
+
+
+def test_tensor_level_eval_head_checks_its_arguments():
+    """The argument errors of bn_hardtanh_linear_eval, raised by the tensor-level functions it wraps
+    (before any device check, so a CPU tensor shows them)."""
+    z = torch.zeros(4, 192)
+    v = torch.ones(192)
+    w4 = torch.zeros(10, 192)
+    pair = (torch.zeros(4, 192, dtype=torch.int16), v)
+    no_stats = "bn_hardtanh_linear_eval needs a BatchNorm with running statistics"
+    needs_fused = r"bn_hardtanh_linear_eval: an int16 pre-activation needs the fused head \(head_eval_fusable\)"
+    with pytest.raises(ValueError, match=needs_fused):
+        BF.bn_linear_eval(pair, v, v, 1e-5, None, None, w4, None)
+    with pytest.raises(ValueError, match=no_stats):
+        BF.bn_linear_eval(z, v, None, 1e-5, None, None, w4, None)
+    with pytest.raises(ValueError, match=needs_fused):       # 192 is no width of the fused head
+        BF.bn_head_eval(pair, v, v, None, None, w4, None)
+    with pytest.raises(ValueError, match=no_stats):
+        BF.bn_head_eval(z, v, None, None, None, w4, None)
+    assert BF.head_eval_fusable(256, 256, 10) and not BF.head_eval_fusable(192, 192, 10)
+    assert not BF.head_eval_fusable(256, 256, 12) and not BF.head_eval_fusable(256, 128, 10)
+
+
 def test_freeze_needs_running_statistics():
     from bnn_amd import freeze
     m = _model()

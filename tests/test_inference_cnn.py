@@ -175,6 +175,37 @@ def test_refresh_and_the_latent_org_weight():
     assert torch.equal(_unpack_conv_rows(fz.t["conv2.wq"], 32, 16, 5, 5).float(), (-latent).sign())
 
 
+def test_refresh_keeps_two_pass_and_drops_the_buffers():
+    from bnn_amd import freeze
+    from bnn_amd.inference import _unpack_conv_rows
+    m = _model()
+    fz = freeze(m, normalize=NORM)
+    fz.two_pass = True
+    fz._buffers(3, torch.device("cpu"))
+    assert fz._buf
+    with torch.no_grad():
+        m.layer2[0].weight.neg_()
+    want = m.layer2[0].weight.detach().sign()
+    assert fz.refresh() is fz
+    assert fz.two_pass is True and fz.normalize == NORM
+    assert torch.equal(_unpack_conv_rows(fz.t["conv2.wq"], 32, 16, 5, 5).float(), want)
+    assert fz._buf == {}
+
+
+def test_a_state_written_by_the_parent_format_loads(tmp_path):
+    from bnn_amd import freeze
+    from test_inference import check_parent_state_loads, parent_state
+    fz = freeze(_model(seed=4), normalize=NORM)
+    state = parent_state(fz, ["bnn_amd.frozen_cnn/1", ("layers", [[1, 16, 5, 5, 2], [16, 32, 5, 5, 2]]),
+                              ("in_hw", [28, 28]), ("normalize", [0.1307, 0.3081]), ("eps", [1e-05, 1e-05])])
+    assert sorted(state["tensors"]) == sorted(
+        [f"{p}{i}.{k}" for i in (1, 2) for p, ks in (("conv", ("sign", "wq", "bias")),
+                                                     ("bn", ("mean", "var", "invstd", "gamma", "beta"))) for k in ks]
+        + ["fc.weight", "fc.bias", "pixel.table"])
+    check_parent_state_loads(fz, state, ["format", "layers", "in_hw", "normalize", "eps", "tensors"],
+                             _pixels(19, seed=8), tmp_path)
+
+
 def test_freeze_refuses_what_the_sign_identity_does_not_cover():
     from bnn_amd import freeze
     m = _model()

@@ -63,23 +63,21 @@ def _time_legs(legs, seconds, repeats):
     return outs, runs, iters
 
 
-def run_cnn(batch, seconds, repeats):
-    from bnn_amd import freeze, nets
-    from bnn_amd import functional as BF
-    from bnn_amd.data import synthetic_mnist
-    torch.manual_seed(0)
-    model = nets.BinCNN(org_protocol=False, mutate_input=False, fused_bn=True).cuda().eval()
-    with torch.no_grad():          # running statistics of the scale the layers produce
-        for bn, fan_in in ((model.layer1[1], 25 * 0.2), (model.layer2[1], 400)):
+def _fill_stats(bns):
+    """Running statistics of the scale the layers produce (timing does not depend on them; labels_equal does
+    not either, both legs read the same ones)."""
+    with torch.no_grad():
+        for bn, fan_in in bns:
             bn.running_mean.normal_(0.0, 0.2 * fan_in ** 0.5)
             bn.running_var.uniform_(0.5 * fan_in, 1.5 * fan_in)
-    u, _ = synthetic_mnist(batch, seed=5, device="cuda", as_u8=True)
-    xf = BF.pixels_to_float(u)
-    fz = freeze(model)
 
+
+def _run_legs(model, fz, x_eval, u, seconds, repeats):
+    """Times the three legs -- model.eval() on x_eval, fz on the u8 pixels u, fz in its two-pass form -- and
+    returns their first outputs and the fields every size reports."""
     def leg_eval():
         with torch.no_grad():
-            return model(xf)
+            return model(x_eval)
 
     def leg_frozen():
         fz.two_pass = False
@@ -93,6 +91,23 @@ def run_cnn(batch, seconds, repeats):
 
     outs, runs, iters = _time_legs({"eval": leg_eval, "frozen": leg_frozen, "frozen_two_pass": leg_frozen2},
                                    seconds, repeats)
+    return outs, {"eval_ms": round(statistics.median(runs["eval"]), 4),
+                  "frozen_ms": round(statistics.median(runs["frozen"]), 4),
+                  "frozen_two_pass_ms": round(statistics.median(runs["frozen_two_pass"]), 4),
+                  "runs_ms": runs, "iters_per_run": iters,
+                  "labels_equal": float((outs["eval"].argmax(1) == outs["frozen"].argmax(1)).float().mean())}
+
+
+def run_cnn(batch, seconds, repeats):
+    from bnn_amd import freeze, nets
+    from bnn_amd import functional as BF
+    from bnn_amd.data import synthetic_mnist
+    torch.manual_seed(0)
+    model = nets.BinCNN(org_protocol=False, mutate_input=False, fused_bn=True).cuda().eval()
+    _fill_stats(((model.layer1[1], 25 * 0.2), (model.layer2[1], 400)))
+    u, _ = synthetic_mnist(batch, seed=5, device="cuda", as_u8=True)
+    fz = freeze(model)
+    outs, res = _run_legs(model, fz, BF.pixels_to_float(u), u, seconds, repeats)
     fz.two_pass = True
     h2 = fz.hidden_signs(u)
     fz.two_pass = False
@@ -103,12 +118,7 @@ def run_cnn(batch, seconds, repeats):
         # eval: conv writes fp32, bn2d reads it and writes the pooled fp32 map, the consumer reads that
         per[f"layer{i}"] = {"eval_bytes": int(batch * (2 * full + 2 * pooled)),
                             "frozen_bytes": int(batch * (2 * PH * PW * ((Co + 15) // 16 * 16) if i < len(shp) else 40))}
-    return {"net": "cnn", "batch": batch,
-            "eval_ms": round(statistics.median(runs["eval"]), 4),
-            "frozen_ms": round(statistics.median(runs["frozen"]), 4),
-            "frozen_two_pass_ms": round(statistics.median(runs["frozen_two_pass"]), 4),
-            "runs_ms": runs, "iters_per_run": iters,
-            "labels_equal": float((outs["eval"].argmax(1) == outs["frozen"].argmax(1)).float().mean()),
+    return {"net": "cnn", "batch": batch, **res,
             "two_pass_labels_equal": float((outs["frozen_two_pass"].argmax(1) == outs["frozen"].argmax(1)).float().mean()),
             "two_pass_hidden_signs_identical": bool(torch.equal(fz.hidden_signs(u), h2)),
             "max_abs_diff_to_eval": float((outs["eval"] - outs["frozen"]).abs().max()),
@@ -122,41 +132,14 @@ def run_size(name, batch, seconds, repeats):
     from bnn_amd.data import synthetic_mnist
     torch.manual_seed(0)
     model = nets.MODELS[name](org_protocol=False, mutate_input=False, fused_bn=True).cuda().eval()
-    # running statistics of the scale the layers produce (timing does not depend on them; labels_equal does
-    # not either, both legs read the same ones)
-    with torch.no_grad():
-        for bn, fan_in in ((model.bn1, 784 * 0.05), (model.bn2, model.fc2.in_features),
-                           (model.bn3, model.fc3.in_features)):
-            bn.running_mean.normal_(0.0, 0.2 * fan_in ** 0.5)
-            bn.running_var.uniform_(0.5 * fan_in, 1.5 * fan_in)
+    _fill_stats(((model.bn1, 784 * 0.05), (model.bn2, model.fc2.in_features), (model.bn3, model.fc3.in_features)))
     u, _ = synthetic_mnist(batch, seed=5, device="cuda", as_u8=True)
     fz = freeze(model)
-
-    def leg_eval():
-        with torch.no_grad():
-            return model(u)
-
-    def leg_frozen():
-        fz.two_pass = False
-        return fz(u)
-
-    def leg_frozen2():
-        fz.two_pass = True
-        out = fz(u)
-        fz.two_pass = False
-        return out
-
-    outs, runs, iters = _time_legs({"eval": leg_eval, "frozen": leg_frozen, "frozen_two_pass": leg_frozen2},
-                                   seconds, repeats)
+    outs, res = _run_legs(model, fz, u, u, seconds, repeats)
     h1, h2, h3 = fz.widths
     epi = {f"fc{i}": {"two_pass_bytes": int(batch * h * 8.5), "bnsign_bytes": int(batch * h * 0.5)}
            for i, h in ((1, h1), (2, h2))}
-    return {"net": name, "widths": [h1, h2, h3], "batch": batch,
-            "eval_ms": round(statistics.median(runs["eval"]), 4),
-            "frozen_ms": round(statistics.median(runs["frozen"]), 4),
-            "frozen_two_pass_ms": round(statistics.median(runs["frozen_two_pass"]), 4),
-            "runs_ms": runs, "iters_per_run": iters,
-            "labels_equal": float((outs["eval"].argmax(1) == outs["frozen"].argmax(1)).float().mean()),
+    return {"net": name, "widths": [h1, h2, h3], "batch": batch, **res,
             "two_pass_bit_identical": bool(torch.equal(outs["frozen"], outs["frozen_two_pass"])),
             "epilogue_bytes": epi}
 
