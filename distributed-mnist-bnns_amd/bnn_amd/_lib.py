@@ -25,6 +25,13 @@ SIGNATURES = {
     "bnn_sign_pack_fp4": (I32, [P, I64, I64, I64, P, I64, P, I64, I32, P]),
     "bnn_sign_pack_fp4_out": (I32, [P, I64, I64, P, I64, P, I64, I32, P, P]),
     "bnn_sign_f32": (I32, [P, P, I64, P]),
+    "bnn_binarize_stoch_f32": (I32, [P, P, I64, U64, P]),
+    "bnn_stoch_pack_i8": (I32, [P, I64, I64, I64, P, I64, P, I64, U64, P]),
+    "bnn_stoch_pack_fp4": (I32, [P, I64, I64, I64, P, I64, P, I64, I32, U64, I32, P]),
+    "bnn_stoch_pack_fp4_out": (I32, [P, I64, I64, P, I64, P, I64, I32, P, U64, I32, P]),
+    "bnn_bn_apply_pack_stoch": (I32, [P, I64, I64, P, P, P, P, P, I32, P, I64, P, I64, I32, U64, I32, P]),
+    "bnn_bn_apply_pack_stoch_i16": (I32, [P, P, I64, I64, P, P, P, P, P, P, I64, P, I64, I32, U64, P]),
+    "bnn_bn_apply_pack_stoch_s20": (I32, [P, P, P, F32, I64, I64, P, P, P, P, P, P, I64, P, I64, I32, U64, P]),
     "bnn_sign_pack_bits": (I32, [P, I64, I64, I64, P, P, I64, P]),
     "bnn_quant_rows": (I32, [P, I64, I64, I64, P, I64, I64, P, P]),
     "bnn_quant_cols_workspace": (I64, [I64, I64]),

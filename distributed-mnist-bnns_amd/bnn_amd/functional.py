@@ -127,8 +127,31 @@ def sign(x, out=None):
     return y
 
 
-def sign_pack(x, want_q=True, want_qt=False):
-    """fp32 [M,K] -> (q int8 [M, ldq] ternary, qt int8 [K, ldqt] transposed); padding zeroed."""
+def binarize_stochastic(x, seed, out=None):
+    """``Binarize(x, 'stoch')`` (models/binarized_modules.py:14-15) as fp32 +-1: element i of the
+    contiguous x is +1 with probability clamp((x + 1) / 2, 0, 1) (to 2^-24), drawn from the hash of
+    (seed, i) -- the rule of DESIGN.md §13, shared bit for bit by every stoch_pack* form and the fused
+    bn_hardtanh_binary_linear(..., stochastic=seed).  ``out`` may be x (in place)."""
+    _check(x)
+    x = _c2d(x)
+    y = torch.empty_like(x) if out is None else out
+    if y.shape != x.shape or not y.is_contiguous():
+        raise ValueError("binarize_stochastic: out must be a contiguous tensor of x's shape")
+    _check(y)
+    if x.numel() == 0:
+        return y
+    with _timed("stoch_f32_k", 0, 8 * x.numel()):
+        L.call("bnn_binarize_stoch_f32", L.ptr(x), L.ptr(y), x.numel(), _u64(seed), L.stream())
+    return y
+
+
+def _u64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def sign_pack(x, want_q=True, want_qt=False, stochastic=None):
+    """fp32 [M,K] -> (q int8 [M, ldq] ternary, qt int8 [K, ldqt] transposed); padding zeroed.
+    stochastic: a seed -- the signs are binarize_stochastic(x, seed)'s, drawn in this pass."""
     _check(x)
     x = _c2d(x)
     M, K = x.shape
@@ -138,10 +161,19 @@ def sign_pack(x, want_q=True, want_qt=False):
     if want_qt:
         qt = torch.empty((K, round_up(M)), dtype=torch.int8, device=x.device)
     nbytes = 4 * M * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
-    with _timed("sign_pack_tile_k", 0, nbytes):
-        L.call("bnn_sign_pack_i8", L.ptr(x), M, K, K, L.ptr(q), q.shape[1] if q is not None else 0,
-               L.ptr(qt), qt.shape[1] if qt is not None else 0, L.stream())
+    with _timed("sign_pack_tile_k" if stochastic is None else "stoch_pack_tile_k", 0, nbytes):
+        if stochastic is None:
+            L.call("bnn_sign_pack_i8", L.ptr(x), M, K, K, L.ptr(q), q.shape[1] if q is not None else 0,
+                   L.ptr(qt), qt.shape[1] if qt is not None else 0, L.stream())
+        else:
+            L.call("bnn_stoch_pack_i8", L.ptr(x), M, K, K, L.ptr(q), q.shape[1] if q is not None else 0,
+                   L.ptr(qt), qt.shape[1] if qt is not None else 0, _u64(stochastic), L.stream())
     return q, qt
+
+
+def stoch_pack(x, seed, want_q=True, want_qt=False):
+    """sign_pack of binarize_stochastic(x, seed), drawn in the packing pass (no fp32 +-1 tensor)."""
+    return sign_pack(x, want_q=want_q, want_qt=want_qt, stochastic=seed)
 
 
 _QT_CODE = {"i8": 0, "fp4": 1, "fp4p": 2}
@@ -164,25 +196,38 @@ def _qt_buffer(K, M, qt_fmt, device):
     return torch.empty((K, round_up(M)), dtype=torch.int8, device=device)
 
 
-def sign_pack_fp4(x, want_qt=False, qt_fmt="i8", want_q=True):
+def sign_pack_fp4(x, want_qt=False, qt_fmt="i8", want_q=True, stochastic=None, force=False):
     """fp32 [M,K] -> (q4 uint8 [M, ldq4] FP4 e2m1 ternary nibbles, qt [K, ldqt] or None).
-    ldq4 = round_up(K, 256) / 2 bytes (zero nibbles beyond K); qt as _qt_buffer."""
+    ldq4 = round_up(K, 256) / 2 bytes (zero nibbles beyond K); qt as _qt_buffer.
+    stochastic: a seed -- the signs are binarize_stochastic(x, seed)'s, drawn in this pass; ``force``
+    (stochastic only) takes the 256 x 256-tile kernel at any grid size the shape allows."""
     _check(x)
     x = _c2d(x)
     M, K = x.shape
     q4 = torch.empty((M, round_up(K, 256) // 2), dtype=torch.uint8, device=x.device) if want_q else None
     qt = _qt_buffer(K, M, qt_fmt, x.device) if want_qt else None
     nbytes = 4 * M * K + (q4.numel() if q4 is not None else 0) + (qt.numel() if qt is not None else 0)
-    with _timed("sign_pack_tile_k<1>", 0, nbytes):
-        L.call("bnn_sign_pack_fp4", L.ptr(x), M, K, K, L.ptr(q4), q4.shape[1] if q4 is not None else 0,
-               L.ptr(qt), qt.shape[1] if qt is not None else 0, _QT_CODE[qt_fmt], L.stream())
+    with _timed("sign_pack_tile_k<1>" if stochastic is None else "stoch_pack_tile_k<1>", 0, nbytes):
+        if stochastic is None:
+            L.call("bnn_sign_pack_fp4", L.ptr(x), M, K, K, L.ptr(q4), q4.shape[1] if q4 is not None else 0,
+                   L.ptr(qt), qt.shape[1] if qt is not None else 0, _QT_CODE[qt_fmt], L.stream())
+        else:
+            L.call("bnn_stoch_pack_fp4", L.ptr(x), M, K, K, L.ptr(q4), q4.shape[1] if q4 is not None else 0,
+                   L.ptr(qt), qt.shape[1] if qt is not None else 0, _QT_CODE[qt_fmt], _u64(stochastic),
+                   int(bool(force)), L.stream())
     return q4, qt
 
 
-def sign_pack_fp4_writeback(x, want_qt=False):
+def stoch_pack_fp4(x, seed, want_qt=False, qt_fmt="i8", want_q=True, force=False):
+    """sign_pack_fp4 of binarize_stochastic(x, seed), drawn in the packing pass."""
+    return sign_pack_fp4(x, want_qt=want_qt, qt_fmt=qt_fmt, want_q=want_q, stochastic=seed, force=force)
+
+
+def sign_pack_fp4_writeback(x, want_qt=False, stochastic=None, force=False):
     """The drop-in BinarizeLinear's input side effect and its GEMM operands from one read of x:
     (sign(x) fp32 -- the new ``input.data`` of binarized_modules.py:76 -- FP4 rows, FP4 transpose in
-    the FP6 GEMM's panel layout or None)."""
+    the FP6 GEMM's panel layout or None).  stochastic: a seed -- all three hold
+    binarize_stochastic(x, seed) instead of sign(x) (``force`` as sign_pack_fp4)."""
     _check(x)
     x = _c2d(x)
     M, K = x.shape
@@ -192,12 +237,25 @@ def sign_pack_fp4_writeback(x, want_qt=False):
     if M == 0:
         return s, q4, qt
     if qt is None:
-        sign(x, out=s)
-        return (s,) + sign_pack_fp4(s, want_qt=False)[:1] + (None,)
-    with _timed("sign_pack_fp4_out", 0, 8 * M * K + q4.numel() + qt.numel()):
-        L.call("bnn_sign_pack_fp4_out", L.ptr(x), M, K, L.ptr(q4), q4.shape[1], L.ptr(qt), qt.shape[1],
-               _QT_CODE["fp4p"], L.ptr(s), L.stream())
+        if stochastic is None:
+            sign(x, out=s)
+        else:
+            binarize_stochastic(x, stochastic, out=s)
+        return (s,) + sign_pack_fp4(s, want_qt=False)[:1] + (None,)     # the sign of +-1 is itself
+    with _timed("sign_pack_fp4_out" if stochastic is None else "stoch_pack_fp4_out", 0,
+                8 * M * K + q4.numel() + qt.numel()):
+        if stochastic is None:
+            L.call("bnn_sign_pack_fp4_out", L.ptr(x), M, K, L.ptr(q4), q4.shape[1], L.ptr(qt), qt.shape[1],
+                   _QT_CODE["fp4p"], L.ptr(s), L.stream())
+        else:
+            L.call("bnn_stoch_pack_fp4_out", L.ptr(x), M, K, L.ptr(q4), q4.shape[1], L.ptr(qt), qt.shape[1],
+                   _QT_CODE["fp4p"], L.ptr(s), _u64(stochastic), int(bool(force)), L.stream())
     return s, q4, qt
+
+
+def stoch_pack_fp4_writeback(x, seed, want_qt=False, force=False):
+    """sign_pack_fp4_writeback with binarize_stochastic(x, seed) in place of sign(x)."""
+    return sign_pack_fp4_writeback(x, want_qt=want_qt, stochastic=seed, force=force)
 
 
 def sign_pack_bits(x, words=None):
@@ -717,10 +775,14 @@ class BinaryLinearFunction(torch.autograd.Function):
     """y = F.linear(bin(x), sign(w)) + b with the reference's STE backward (see module doc)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, binarize_input, backend="fp4", cache=False, xpack=None):
+    def forward(ctx, x, weight, bias, binarize_input, backend="fp4", cache=False, xpack=None, stochastic=None):
         # xpack: (FP4 rows, FP4 panel transpose or None) of sign(x), made with the input write-back
         # (sign_pack_fp4_writeback); used instead of packing x again
+        # stochastic: a seed -- the input is binarised as binarize_stochastic(x, seed), drawn in the pack
+        # pass; the transposed operand saved here carries the same draw to the backward's dW
         _check(x, weight, bias)
+        if stochastic is not None and (not binarize_input or xpack is not None):
+            raise ValueError("stochastic binarization applies to a binarised input packed by this op")
         M, K = x.shape
         N = weight.shape[0]
         ctx.dims = (M, K, N)
@@ -744,15 +806,17 @@ class BinaryLinearFunction(torch.autograd.Function):
                 w4, wqt = packed_weight(weight, "fp4", True, need_dx, cache, qt_fmt=qf)
                 y = gemm_fp4(x4, w4, M, N, bias=b, k_true=K)
             elif backend == "fp4":
-                x4, xqt = sign_pack_fp4(x, want_qt=need_dw, qt_fmt=qf)
+                x4, xqt = sign_pack_fp4(x, want_qt=need_dw, qt_fmt=qf, stochastic=stochastic)
                 w4, wqt = packed_weight(weight, "fp4", True, need_dx, cache, qt_fmt=qf)
                 y = gemm_fp4(x4, w4, M, N, bias=b, k_true=K)
             elif backend == "xnor":
+                if stochastic is not None:      # the bit-planes and the transpose from one fp32 +-1 draw
+                    x = binarize_stochastic(x, stochastic)
                 y = gemm_xnor(sign_pack_bits(x), sign_pack_bits(weight), M, N, bias=b)
                 xqt = sign_pack(x, want_q=False, want_qt=True)[1] if need_dw else None
                 wqt = packed_weight(weight, "i8", False, need_dx, cache)[1] if need_dx else None
             else:
-                xq, xqt = sign_pack(x, want_q=True, want_qt=need_dw)
+                xq, xqt = sign_pack(x, want_q=True, want_qt=need_dw, stochastic=stochastic)
                 wq, wqt = packed_weight(weight, "i8", True, need_dx, cache)
                 y = gemm_i8(xq, 1, wq, 1, M, N, bias=b, k_true=K)
             ctx.save_for_backward(xqt, wqt)
@@ -774,7 +838,7 @@ class BinaryLinearFunction(torch.autograd.Function):
             return (torch.empty((0, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None,
                     torch.zeros((N, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None,
                     torch.zeros((N,), dtype=torch.float32, device=dev)
-                    if ctx.has_bias and ctx.needs_input_grad[2] else None, None, None, None, None)
+                    if ctx.has_bias and ctx.needs_input_grad[2] else None, None, None, None, None, None)
         xs, wqt = ctx.saved_tensors
         dy = _c2d(dy)
         dx = dw = db = None
@@ -791,7 +855,7 @@ class BinaryLinearFunction(torch.autograd.Function):
                     else:
                         dw = gemm_fp6(dt, xs, K, k_true=M)
                 db = cs if need_db else None
-            return dx, dw, db, None, None, None, None
+            return dx, dw, db, None, None, None, None, None
         if ctx.needs_input_grad[0]:
             d, s = quant_rows(dy)                                   # [3, M, ldN]
             dx = gemm_i8(d, 3, wqt, 1, M, K, a_scale=s, k_true=N)   # dY . W_b
@@ -804,18 +868,22 @@ class BinaryLinearFunction(torch.autograd.Function):
                     xt, sxc, _ = quant_cols_t(xs)
                     dw = gemm_i8(dt, 3, xt, 3, N, K, a_scale=sc, b_scale=sxc, k_true=M)
             db = cs
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
-def binary_linear(x, weight, bias=None, binarize_input=True, backend="fp4", cache=False, xpack=None):
+def binary_linear(x, weight, bias=None, binarize_input=True, backend="fp4", cache=False, xpack=None,
+                  stochastic=None):
     """Functional BinarizeLinear core: 2-D or N-D input (leading dims flattened).  ``cache``: the
-    weight is a latent weight whose packed operands are cached on it (packed_weight)."""
+    weight is a latent weight whose packed operands are cached on it (packed_weight).  ``stochastic``:
+    a seed (stochastic_seed) -- the input is binarised stochastically (binarize_stochastic) instead of
+    by its sign; the backward uses the forward's draw."""
     if x.dim() == 2:
         # no reshape view: the output tensor itself carries the FP6 hand-off request (_Q6_WANT) to
         # the BatchNorm that consumes it, and its gradient comes back to this Function unchanged
-        return BinaryLinearFunction.apply(x, weight, bias, binarize_input, backend, cache, xpack)
+        return BinaryLinearFunction.apply(x, weight, bias, binarize_input, backend, cache, xpack, stochastic)
     lead = x.shape[:-1]
-    y = BinaryLinearFunction.apply(x.reshape(-1, x.shape[-1]), weight, bias, binarize_input, backend, cache, xpack)
+    y = BinaryLinearFunction.apply(x.reshape(-1, x.shape[-1]), weight, bias, binarize_input, backend, cache, xpack,
+                                   stochastic)
     return y.reshape(*lead, weight.shape[0])
 
 
@@ -1300,11 +1368,16 @@ def _zq_fmt(x, binarize_input, stride, dilation, groups, C, KH, KW, H, W, pad, N
 
 class BinaryConv2dFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, binarize_input, stride, padding, dilation, groups, emit_compact=False):
+    def forward(ctx, x, weight, bias, binarize_input, stride, padding, dilation, groups, emit_compact=False,
+                stochastic=None):
         global ZQ_HANDOFFS
         _check(x, weight, bias)
         _conv_env()
         x = _c2d(x)
+        if stochastic is not None and binarize_input:
+            # one stochastic fp32 pass in front: the kernels' own sign of +-1 is the identity, and the
+            # backward's filter gradient reads this saved draw
+            x = binarize_stochastic(x, stochastic)
         w = _c2d(weight.detach())
         N, C, H, W = x.shape
         Co, _, KH, KW = w.shape
@@ -1362,7 +1435,7 @@ class BinaryConv2dFunction(torch.autograd.Function):
             return (torch.empty_like(x) if ctx.needs_input_grad[0] else None,
                     torch.zeros_like(w) if ctx.needs_input_grad[1] else None,
                     torch.zeros((Co,), dtype=torch.float32, device=x.device)
-                    if ctx.has_bias and ctx.needs_input_grad[2] else None, None, None, None, None, None, None)
+                    if ctx.has_bias and ctx.needs_input_grad[2] else None, None, None, None, None, None, None, None)
         dx = dw = db = None
         if bn is not None and not L.lib().bnn_conv2d_bwd_filter_bn_ok(N, C, H, W, Co, KH, KW, stride, padding,
                                                                       dilation, groups):
@@ -1385,7 +1458,7 @@ class BinaryConv2dFunction(torch.autograd.Function):
                        int(binarize_input), L.ptr(dw), L.ptr(db), L.ptr(ws), N, C, H, W, Co, KH, KW, stride,
                        padding, dilation, groups, L.stream())
             C1BN_HANDOFFS += 1
-            return (None, dw if ctx.needs_input_grad[1] else None, db, None, None, None, None, None, None)
+            return (None, dw if ctx.needs_input_grad[1] else None, db, None, None, None, None, None, None, None)
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             with _timed("conv2d_bwd_data", 2 * macs, 4 * (dy.numel() + dx.numel() + w.numel())):
@@ -1403,7 +1476,7 @@ class BinaryConv2dFunction(torch.autograd.Function):
                        L.stream())
             if not ctx.needs_input_grad[1]:
                 dw = None
-        return dx, dw, db, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None
 
 
 def _bn2d_dy_of_handoff(bn, shape):
@@ -1422,12 +1495,13 @@ def _bn2d_dy_of_handoff(bn, shape):
 
 
 def binary_conv2d(x, weight, bias=None, binarize_input=True, stride=1, padding=0, dilation=1, groups=1,
-                  emit_compact=False):
+                  emit_compact=False, stochastic=None):
     """emit_compact: return the output as a zq placeholder when the shape allows (its consumer
-    must be batch_norm2d_hardtanh_pool in training mode)."""
+    must be batch_norm2d_hardtanh_pool in training mode).  stochastic: a seed -- the input is binarised
+    by binarize_stochastic(x, seed) instead of its sign."""
     return BinaryConv2dFunction.apply(x, weight, bias, binarize_input, _pair_same(stride, "stride"),
                                       _pair_same(padding, "padding"), _pair_same(dilation, "dilation"),
-                                      int(groups), bool(emit_compact))
+                                      int(groups), bool(emit_compact), stochastic)
 
 
 # ----------------------------------------------------------------------------- (3) STE helpers
@@ -1882,6 +1956,20 @@ def dropout_seed():
     return _DEVICE_STEP.base_seed if _DEVICE_STEP is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
+_SALT_STRIDE = 0x9E3779B97F4A7C15
+
+
+def stochastic_seed(salt):
+    """The seed of one stochastic-binarization site: (base + salt * 0x9E3779B97F4A7C15) mod 2^64 with
+    base = dropout_seed() (the device step's base seed, else one draw of torch's CPU generator per
+    call) and salt >= 1 the site's number (the nets number their layers) -- sites of one step never
+    share a mask with each other or with the dropout, which uses the unsalted base."""
+    salt = int(salt)
+    if salt < 1:
+        raise ValueError("stochastic_seed: salt must be an integer >= 1")
+    return (dropout_seed() + salt * _SALT_STRIDE) & 0xFFFFFFFFFFFFFFFF
+
+
 def dropout_bn_hardtanh_linear(x, p, bn, fc, seed=None):
     """fc(hardtanh(bn(nn.Dropout(p)(x)))) through libbnn (training mode; see head_fusable)."""
     if seed is None:
@@ -2076,7 +2164,10 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, bn_w, bn_b, rm, rv, training, momentum, eps, weight, bias, backend, emit_z16=False,
-                emit_stats=False):
+                emit_stats=False, stochastic=None):
+        # stochastic: a seed -- the operand is binarize_stochastic(bn(z), seed) (the draw's clamp absorbs
+        # the Hardtanh), drawn in the apply-pack pass from the fp32, z16 or s20 form of z alike; the
+        # backward's dW reads the saved transposed operand of the same pass
         _check(z, bn_w, bn_b, rm, rv, weight, bias)
         ctx.q6 = _q6_wanted(z, z.shape[-1], training)
         ctx.i8c = (I8C_HANDOFF and bool(getattr(z, _I8C_WANT, False)) and training and not ctx.q6
@@ -2131,8 +2222,21 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
         ctx.qt_panel = need_dw and qf == "fp4p"
         qt = _qt_buffer(C, M, qf, z.device) if need_dw else None
         nx = 2.5 if zs is not None else (4 if zz is None else 2)
-        with _timed("bn_apply_pack", 0, nx * M * C + q.numel() + (qt.numel() if qt is not None else 0)):
-            if zs is not None:
+        with _timed("bn_apply_pack" if stochastic is None else "bn_apply_pack_stoch", 0,
+                    nx * M * C + q.numel() + (qt.numel() if qt is not None else 0)):
+            if stochastic is not None and zs is not None:
+                L.call("bnn_bn_apply_pack_stoch_s20", L.ptr(zs[0]), L.ptr(zs[1]), L.ptr(zs[2]), zs[3], M, C,
+                       L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.ptr(gw), L.ptr(gb), L.ptr(q), q.shape[1], L.ptr(qt),
+                       qt.shape[1], 1 if ctx.qt_panel else 0, _u64(stochastic), L.stream())
+            elif stochastic is not None and zz is None:
+                L.call("bnn_bn_apply_pack_stoch", L.ptr(z), M, C, L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.ptr(gw),
+                       L.ptr(gb), 1 if fp4 else 0, L.ptr(q), q.shape[1], L.ptr(qt), qt.shape[1] if qt is not None else 0,
+                       _QT_CODE[qf], _u64(stochastic), 0, L.stream())
+            elif stochastic is not None:
+                L.call("bnn_bn_apply_pack_stoch_i16", L.ptr(zz[0]), L.ptr(zz[1]), M, C, L.ptr(mean), L.ptr(invstd),
+                       L.ptr(mlo), L.ptr(gw), L.ptr(gb), L.ptr(q), q.shape[1], L.ptr(qt), qt.shape[1],
+                       1 if ctx.qt_panel else 0, _u64(stochastic), L.stream())
+            elif zs is not None:
                 L.call("bnn_bn_apply_pack_s20", L.ptr(zs[0]), L.ptr(zs[1]), L.ptr(zs[2]), zs[3], M, C, L.ptr(mean),
                        L.ptr(invstd), L.ptr(mlo), L.ptr(gw), L.ptr(gb), L.ptr(q), q.shape[1], L.ptr(qt), qt.shape[1],
                        1 if ctx.qt_panel else 0, L.stream())
@@ -2242,18 +2346,21 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
                 with _timed("bn_bwd", 0, 16 * M * C):
                     _bn_bwd_call(ctx.training, z, dh, M, C, gw, gb, mean, invstd, mlo, True, dz, dgw, dgb, ws)
         return (dz, dgw if ctx.needs_input_grad[1] else None, dgb if ctx.needs_input_grad[2] else None,
-                None, None, None, None, None, dw, db, None, None, None)
+                None, None, None, None, None, dw, db, None, None, None, None)
 
 
-def bn_hardtanh_binary_linear(z, bn, fc, backend="fp4", emit_z16=False, emit_stats=False):
+def bn_hardtanh_binary_linear(z, bn, fc, backend="fp4", emit_z16=False, emit_stats=False, stochastic=None):
     """fc(hardtanh(bn(z))) through BNHardtanhBinaryLinearFunction (bn: nn.BatchNorm1d, fc: a
     BinarizeLinear holding its latent weight, i.e. ``org_protocol = False``).  emit_z16: return
     fc's output as a z16 placeholder (its consumer must be a z16-aware libbnn BatchNorm pass:
-    bn_hardtanh_binary_linear or dropout_bn_hardtanh_linear in training mode; see z16_ok)."""
+    bn_hardtanh_binary_linear or dropout_bn_hardtanh_linear in training mode; see z16_ok).
+    stochastic: a seed (stochastic_seed) -- fc's input is binarize_stochastic(bn(z), seed) instead of
+    sign(bn(z)), drawn in the same single pass over z."""
     rm, rv, bn_training, factor = _bn_module_args(bn)
     return BNHardtanhBinaryLinearFunction.apply(z, bn.weight, bn.bias, rm, rv, bn_training, factor, bn.eps,
                                                 fc.weight, fc.bias, backend, bool(emit_z16),
-                                                emit_stats if isinstance(emit_stats, tuple) else bool(emit_stats))
+                                                emit_stats if isinstance(emit_stats, tuple) else bool(emit_stats),
+                                                stochastic)
 
 
 # ----------------------------------------------------------------------------- frozen-model inference

@@ -19,6 +19,19 @@ from . import functional as BF
 from .nn import BatchNorm1d, BinarizeConv2d, BinarizeLinear
 
 
+def _stochastic_sites(layers):
+    """Stochastic input binarization (training mode) for the given {layer number: layer}; the number is
+    the site's salt (functional.stochastic_seed), so the layers of one step draw different masks."""
+    for salt, m in layers.items():
+        m.quant_mode = "stoch"
+        m.stoch_salt = salt
+
+
+def _stoch_seed(fc):
+    """The seed of fc's stochastic input draw in this forward, or None (deterministic / eval mode)."""
+    return BF.stochastic_seed(fc.stoch_salt) if fc.quant_mode == "stoch" and fc.training else None
+
+
 def _configure(module, org_protocol, mutate_input, backend=None):
     for m in module.modules():
         if isinstance(m, (BinarizeLinear, BinarizeConv2d)):
@@ -33,8 +46,10 @@ class MLP(nn.Module):
     """mnist-dist2.py:46-76 with explicit widths."""
 
     def __init__(self, h1, h2, h3, p_drop=0.3, org_protocol=True, mutate_input=True, backend=None,
-                 fused_bn=False, normalize=None, dropin_bn=False):
+                 fused_bn=False, normalize=None, dropin_bn=False, stochastic=False):
         super().__init__()
+        # stochastic: fc2 and fc3 binarise their inputs stochastically in training mode (fc1 takes
+        # pixels); eval mode and the frozen model stay deterministic
         # dropin_bn: bn1..bn3 are bnn_amd.nn.BatchNorm1d (torch's module on libbnn's passes), the
         # drop-in a user of the reference swaps for nn.BatchNorm1d; the modules and state_dict keep
         # their names and shapes either way
@@ -58,6 +73,8 @@ class MLP(nn.Module):
         # uint8 pixel batches: fc1 applies ToTensor (+ Normalize(*normalize)) on the bytes
         self.fc1.pixel_normalize = normalize
         _configure(self, org_protocol, mutate_input, backend)
+        if stochastic:
+            _stochastic_sites({2: self.fc2, 3: self.fc3})
 
     def _bnh(self, bn, ht, x):
         if self.fused_bn and x.is_cuda and x.dim() == 2 and x.shape[1] % 4 == 0:
@@ -73,7 +90,9 @@ class MLP(nn.Module):
         its latent weight in the Parameter and runs an MFMA backend.  emit_stats: fc's FP4 forward
         also forms the next (training-mode, fused) BatchNorm's forward statistics."""
         if self._fusable(fc, z):
-            return BF.bn_hardtanh_binary_linear(z, bn, fc, fc.backend, emit_z16=emit_z16, emit_stats=emit_stats)
+            seed = _stoch_seed(fc)
+            kw = {} if seed is None else {"stochastic": seed}   # (the deterministic call is unchanged)
+            return BF.bn_hardtanh_binary_linear(z, bn, fc, fc.backend, emit_z16=emit_z16, emit_stats=emit_stats, **kw)
         return fc(self._bnh(bn, ht, z))
 
     def _z16(self, fc, M, consumer):
@@ -146,8 +165,9 @@ def WideNet(width=8192, **kw):
 
 
 class BinCNN(nn.Module):
-    def __init__(self, num_classes=10, org_protocol=True, mutate_input=True, fused_bn=False):
+    def __init__(self, num_classes=10, org_protocol=True, mutate_input=True, fused_bn=False, stochastic=False):
         super().__init__()
+        # stochastic: layer2's conv binarises its input stochastically in training mode (layer1 takes pixels)
         # fused_bn: BatchNorm2d -> Hardtanh -> MaxPool2d of each layer run as one libbnn op (same
         # parameters, buffers and math; the Sequential modules and state_dict are unchanged)
         self.fused_bn = fused_bn
@@ -158,6 +178,8 @@ class BinCNN(nn.Module):
         self.fc = nn.Linear(7 * 7 * 32, num_classes)
         self.logsoftmax = nn.LogSoftmax(dim=1)
         _configure(self, org_protocol, mutate_input)
+        if stochastic:
+            _stochastic_sites({2: self.layer2[0]})
 
     def _layer(self, seq, x):
         conv, bn, ht, pool = seq

@@ -18,6 +18,11 @@ Side effects kept (the caller loop of mnist-dist2.py:131-137 depends on them):
   ``bias.org`` is re-cloned every forward (:82, :104), and the caller's input tensor is
   replaced by its sign unless the first-layer rule applies (:75-76, :94-95).
 
+``quant_mode = "stoch"`` (class or instance attribute of ``BinarizeLinear`` / ``BinarizeConv2d``, default
+``"det"``) makes the input binarization the stochastic one of ``Binarize(t, 'stoch')`` while the module
+is in training mode (eval mode stays deterministic), drawn by libbnn in the same pass that packs the
+input; ``stoch_salt`` numbers the site (functional.stochastic_seed).
+
 Two class attributes switch behaviour for the build's own trainer:
   ``org_protocol = False`` keeps the latent weight in the Parameter itself (no ``.org``,
   binarised on the fly inside the kernel; pair it with ``bnn_amd.optim.LatentAdam``), and
@@ -39,9 +44,14 @@ __all__ = ["Binarize", "HingeLoss", "SqrtHingeLossFunction", "Quantize", "Binari
 
 def Binarize(tensor, quant_mode="det"):
     """Deterministic: ``tensor.sign()`` as a new tensor (libbnn).  Stochastic (reference :15, never
-    used by the reference modules): in place, ``round(clamp((x+1)/2 + U(-.5,.5), 0, 1))*2 - 1``."""
+    used by the reference modules): in place, ``round(clamp((x+1)/2 + U(-.5,.5), 0, 1))*2 - 1`` -- on a
+    contiguous fp32 CUDA tensor one libbnn pass (functional.binarize_stochastic, seeded by one draw of
+    torch's CPU generator or the device step) that overwrites ``tensor`` with the draw and returns it (the
+    reference overwrites its argument too); other tensors keep the torch ops."""
     if quant_mode == "det":
         return BF.sign(tensor)
+    if tensor.is_cuda and tensor.dtype == torch.float32 and tensor.is_contiguous():
+        return BF.binarize_stochastic(tensor, BF.stochastic_seed(1), out=tensor)
     noise = torch.rand(tensor.size(), device=tensor.device, dtype=tensor.dtype) - 0.5
     prob = tensor.add_(1.0).div_(2.0).add_(noise).clamp_(0.0, 1.0)
     return prob.round().mul_(2.0).sub_(1.0)
@@ -98,6 +108,13 @@ def Quantize(tensor, quant_mode="det", params=None, numBits=8):
     raise NotImplementedError("Quantize(quant_mode!='det') calls an undefined quant_fixed in the reference")
 
 
+def _stochastic(module):
+    """Whether a binarized layer draws its input binarization now: quant_mode "stoch" in training mode."""
+    if module.quant_mode not in ("det", "stoch"):
+        raise ValueError(f"quant_mode must be 'det' or 'stoch', got {module.quant_mode!r}")
+    return module.quant_mode == "stoch" and module.training
+
+
 def _apply_org_protocol(p):
     """binarized_modules.py:77-79: lazily keep the latent copy, expose its sign in .data."""
     if not hasattr(p, "org"):
@@ -109,6 +126,8 @@ class BinarizeLinear(nn.Linear):
     org_protocol = True
     mutate_input = True
     backend = "fp4"        # ternary GEMM engine: "fp4" (FP4 MFMA), "mfma" (int8 MFMA), "xnor" (VALU)
+    quant_mode = "det"     # "stoch": stochastic input binarization in training mode (Binarize(t, 'stoch'))
+    stoch_salt = 1         # the site's number in functional.stochastic_seed (the nets number their layers)
 
     def __init__(self, *kargs, **kwargs):
         super().__init__(*kargs, **kwargs)
@@ -158,22 +177,28 @@ class BinarizeLinear(nn.Linear):
                         self.bias.org = self.bias.data.clone()
                 return BF.binary_linear_pixels(u, self.weight, self.bias, None, cache=not self.org_protocol)
         xpack = None
+        # the stochastic draw's seed (training mode only), or None: the deterministic sign
+        seed = BF.stochastic_seed(self.stoch_salt) if binarize and _stochastic(self) else None
         if binarize and self.mutate_input:
             if (self.backend == "fp4" and BF.DIGIT_GEMM == "fp6" and input.dim() == 2 and input.dtype == torch.float32
                     and input.is_cuda):
                 # the write-back and the GEMM operands of sign(input) from one read of the input
                 need_dw = self.weight.requires_grad and torch.is_grad_enabled()
-                s, x4, xqt = BF.sign_pack_fp4_writeback(input.data, want_qt=need_dw)
+                s, x4, xqt = BF.sign_pack_fp4_writeback(input.data, want_qt=need_dw, stochastic=seed)
                 input.data = s                                  # :76
                 xpack = (x4, xqt)
+            elif seed is not None:
+                input.data = BF.binarize_stochastic(input.data, seed)
             else:
                 input.data = BF.sign(input.data)                # :76
+            seed = None                                         # the input now holds the draw: its sign is itself
         if self.org_protocol:
             _apply_org_protocol(self.weight)                    # :77-79
             if self.bias is not None:
                 self.bias.org = self.bias.data.clone()          # :82
+        kw = {} if seed is None else {"stochastic": seed}       # (the deterministic call is unchanged)
         return BF.binary_linear(input, self.weight, self.bias, binarize, self.backend,
-                                cache=not self.org_protocol, xpack=xpack)
+                                cache=not self.org_protocol, xpack=xpack, **kw)
 
 
 class BatchNorm1d(nn.BatchNorm1d):
@@ -207,6 +232,8 @@ class BatchNorm1d(nn.BatchNorm1d):
 class BinarizeConv2d(nn.Conv2d):
     org_protocol = True
     mutate_input = True
+    quant_mode = "det"     # as BinarizeLinear's
+    stoch_salt = 1
 
     def __init__(self, *kargs, **kwargs):
         super().__init__(*kargs, **kwargs)
@@ -219,11 +246,17 @@ class BinarizeConv2d(nn.Conv2d):
         # emit_compact (the build's fused BinCNN only): the output may travel as its exact int8 /
         # int16 sums + bias to a libbnn BatchNorm2d (functional.binary_conv2d)
         binarize = input.size(1) != 3                         # :94
+        seed = BF.stochastic_seed(self.stoch_salt) if binarize and _stochastic(self) else None
         if binarize and self.mutate_input:
-            input.data = BF.sign(input.data)                    # :95
+            if seed is not None:
+                input.data = BF.binarize_stochastic(input.data, seed)
+                seed = None                                     # the input now holds the draw
+            else:
+                input.data = BF.sign(input.data)                # :95
         if self.org_protocol:
             _apply_org_protocol(self.weight)                    # :96-98
             if self.bias is not None:
                 self.bias.org = self.bias.data.clone()          # :104
+        kw = {} if seed is None else {"stochastic": seed}       # (the deterministic call is unchanged)
         return BF.binary_conv2d(input, self.weight, self.bias, binarize, self.stride, self.padding,
-                                self.dilation, self.groups, emit_compact=emit_compact)
+                                self.dilation, self.groups, emit_compact=emit_compact, **kw)

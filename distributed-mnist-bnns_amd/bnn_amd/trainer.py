@@ -73,6 +73,8 @@ def parse(argv=None):
     ap.add_argument("--lr-quirk-period", type=int, default=40, help="the 40 of epoch%%40==0 (mnist-dist2.py:126)")
     ap.add_argument("--device-step", action="store_true", help="eager steps on the device step counter (dropout "
                     "seeds and Adam as --graph draws them: an eager twin of a --graph run)")
+    ap.add_argument("--stochastic", action="store_true", help="stochastic activation binarization in training "
+                    "(Binarize(t, 'stoch') on the hidden layers' inputs; eval and --eval stay deterministic)")
     ap.add_argument("--csv-prefix", default=None, help="write <prefix>_BATCH_TIME.csv / _EPOCH_TIME.csv")
     ap.add_argument("--checkpoint", default=None, help="write a latent-weight checkpoint here after every epoch")
     ap.add_argument("--resume", default=None, help="resume from a checkpoint written by --checkpoint")
@@ -112,7 +114,7 @@ def train(gpu, args):
             dist.init_process_group(args.backend, init_method="env://", world_size=world, rank=rank)
     torch.cuda.manual_seed(args.seed)
     model = nets.MODELS[args.model](org_protocol=False, mutate_input=False,
-                                    fused_bn=True).to(device)
+                                    fused_bn=True, stochastic=args.stochastic).to(device)
     exchange = GradExchange(model) if world > 1 else None
     if args.graph and world > 1:
         raise SystemExit("--graph runs one process (the gradient exchange is not captured)")

@@ -330,6 +330,31 @@ __device__ __forceinline__ uint32_t drop_hash(uint64_t seed, uint64_t i) {
 
 __device__ __forceinline__ bool drop_keep(const Drop& d, uint64_t i) { return drop_hash(d.seed, i) < d.thresh; }
 
+// Stochastic binarization, Binarize(t, 'stoch') of models/binarized_modules.py:14-15
+// (round(clamp((x + 1) / 2 + U(-.5, .5), 0, 1)) * 2 - 1), for element i = m * K + k (mod 2^32) of a logical
+// row-major [M][K] activation: +1 with probability floor(p * 2^24) / 2^24, p = clamp((x + 1) / 2, 0, 1), else
+// -1, drawn from the top 24 bits of drop_hash(seed, i).  x >= 1 always gives +1 (t = 2^24 exceeds every
+// 24-bit draw), x <= -1 always -1 (t = 0), never 0 -- except NaN -> 0, as tsign().  One definition for
+// every pass that draws (sign_f32_k, sign_pack_tile_k, bn_apply_pack_fp4_k), so all forms of the same
+// (x, seed) agree bit for bit.  key = stoch_key(): loop-invariant, as drop_key is for the dropout passes.
+struct Stoch {
+  uint64_t seed;
+  const int64_t* ctr;   // device step counter folded into the seed (bnn_set_seed_counter), or null
+};
+
+__device__ __forceinline__ uint32_t stoch_key(const Stoch& s) {
+  uint64_t seed = s.seed;
+  if (s.ctr != nullptr) seed += (uint64_t)s.ctr[0] * 0xD1B54A32D192ED03ull;   // as drop_resolve
+  return drop_key(seed);
+}
+
+__device__ __forceinline__ int ssign(float x, uint32_t key, uint32_t i) {
+  const float p = fminf(fmaxf(fmaf(x, 0.5f, 0.5f), 0.f), 1.f);
+  const uint32_t t = (uint32_t)(p * 16777216.0f);   // exact product, truncated: 0 .. 2^24
+  const uint32_t h = fmix32(i * 0x9E3779B1u ^ key);   // drop_hash(seed', i)
+  return (x != x) ? 0 : ((h >> 8) < t ? 1 : -1);
+}
+
 // keep bits of elements i0 .. i0+3 (bit j): the index products (i0 + j) * golden formed by adds
 // from one multiply (the same values mod 2^32; the 32-bit multiply is a quarter-rate instruction)
 __device__ __forceinline__ uint32_t drop_bits4(const Drop& d, uint64_t i0) {
@@ -351,5 +376,7 @@ inline Drop make_drop(float p, uint64_t seed) {
   }
   return d;
 }
+
+inline Stoch make_stoch(uint64_t seed) { return Stoch{seed, g_seed_ctr}; }
 
 }  // namespace bnn

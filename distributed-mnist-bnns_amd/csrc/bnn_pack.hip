@@ -4,6 +4,8 @@
 //
 // Reference behaviour restated: Binarize(t,'det') = t.sign() (models/binarized_modules.py:11-13)
 // applied to inputs (:76, :95) and to the latent weight (:79, :98); sign(0) = 0 -> ternary.
+// Binarize(t,'stoch') (:14-15) is the same passes with the draw ssign() (bnn_common.h) in place of
+// the sign: the ST = 1 instantiations of sign_f32_k, sign_pack_tile_k and bn_apply_pack_fp4_k.
 #include <algorithm>
 
 #include "bnn_common.h"
@@ -96,13 +98,16 @@ __device__ __forceinline__ void adam4(float* __restrict__ prow, int64_t off, int
 #ifndef PK_COAL
 #define PK_COAL 1
 #endif
-template <int FMT, int AFF = 0, int ADAM = 0>
+// ST = 1: the sign is the stochastic draw ssign() of element m * K + k with st's seed (never with ADAM);
+// padding elements stay 0.
+template <int FMT, int AFF = 0, int ADAM = 0, int ST = 0>
 __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict__ x, int64_t M,
                                                         int64_t K, int64_t ldx, int8_t* __restrict__ q,
                                                         int64_t ldq, int8_t* __restrict__ qt,
                                                         int64_t ldqt, int vec, ColAffine af = {},
                                                         int rtiles = 1, int64_t ntiles_y = 0,
-                                                        AdamArgs ad = {}, int qt4 = 0) {
+                                                        AdamArgs ad = {}, int qt4 = 0, Stoch st = {}) {
+  static_assert(!ST || (PK_COAL && !ADAM), "the stochastic draw is built into the row-run form only");
   // qt4 = 1: the transpose is written as FP4 nibbles (qt rows of ldqt BYTES, element m in byte
   // m/2), the B operand of the FP6 digit GEMMs (bnn_gemm6.hip); 2: the same nibbles in that GEMM's
   // panel layout ([K/512][ldqt/32][512][32 B], bnn_fp4_panelize); else int8 (rows of ldqt elements)
@@ -121,6 +126,8 @@ __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict_
   constexpr int NP = 16;
   const int64_t cb = k0 + c;
 #endif
+  uint32_t skey = 0;
+  if constexpr (ST) skey = stoch_key(st);
   if (AFF) {
     // per-column parameters for columns cb .. cb + NP - 1: float4 loads when the run is in range
     if (af.vec && cb + NP <= K) {
@@ -200,7 +207,10 @@ __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict_
       for (int j = 0; j < 4; ++j) {
         float y = v[j];
         if (AFF) y = (mr < M && cb + j < K) ? bn_y1(y, mu[j], lo[j], is[j], ga[j], be[j]) : 0.f;
-        tile[rr][ac + j] = tsign(y);
+        if constexpr (ST)
+          tile[rr][ac + j] = (mr < M && cb + j < K) ? ssign(y, skey, (uint32_t)(mr * K + cb + j)) : 0;
+        else
+          tile[rr][ac + j] = tsign(y);
       }
     }
     __syncthreads();
@@ -317,15 +327,18 @@ __device__ __forceinline__ void nib_transpose8(uint32_t (&x)[8]) {
 // IDN = 1: no BatchNorm (y = x: the plain sign-pack of bnn_sign_pack_fp4 on 256 x 256 tiles), and
 // sout (nullable) also receives sign(x) as fp32 -- the drop-in's `input.data = sign(input)` write-back
 // (binarized_modules.py:76) from the same read of x.
-template <int XF, int IDN = 0>
+// ST = 1: the sign is the stochastic draw ssign() of element m * C + c with st's seed.
+template <int XF, int IDN = 0, int ST = 0>
 __global__ __launch_bounds__(256) void bn_apply_pack_fp4_k(XIn xin, int64_t M, int64_t C,
                                                            ColAffine af, uint8_t* __restrict__ q, int64_t ldq,
                                                            uint8_t* __restrict__ qt, int64_t ldqt, int64_t pnks,
-                                                           float* __restrict__ sout = nullptr) {
+                                                           float* __restrict__ sout = nullptr, Stoch st = {}) {
   __shared__ uint32_t img[AP_T * AP_LD];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int64_t k0 = (int64_t)blockIdx.x * AP_T, m0 = (int64_t)blockIdx.y * AP_T;
   const int64_t cb = k0 + 4 * lane;
+  uint32_t skey = 0;
+  if constexpr (ST) skey = stoch_key(st);
   float mu[4] = {0.f, 0.f, 0.f, 0.f}, is[4] = {1.f, 1.f, 1.f, 1.f}, ga[4] = {1.f, 1.f, 1.f, 1.f};
   float be[4] = {0.f, 0.f, 0.f, 0.f}, lo[4] = {0.f, 0.f, 0.f, 0.f};
   if constexpr (!IDN) {
@@ -353,7 +366,9 @@ __global__ __launch_bounds__(256) void bn_apply_pack_fp4_k(XIn xin, int64_t M, i
       int sg[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        sg[j] = IDN ? tsign(v[j]) : tsign(bn_y1(v[j], mu[j], lo[j], is[j], ga[j], be[j]));
+        const float y = IDN ? v[j] : bn_y1(v[j], mu[j], lo[j], is[j], ga[j], be[j]);
+        if constexpr (ST) sg[j] = ssign(y, skey, (uint32_t)(m * C + cb + j));
+        else sg[j] = tsign(y);
         code |= fp4_code(sg[j]) << (4 * j);
       }
       *reinterpret_cast<uint16_t*>(q + m * ldq + k0 / 2 + 2 * lane) = (uint16_t)code;
@@ -453,23 +468,31 @@ __global__ __launch_bounds__(256) void adam_pack_fp4_k(float* __restrict__ p, Ad
   }
 }
 
+// ST = 1: y[i] = the stochastic draw ssign() of element i (y may alias x: a thread reads what it writes)
+template <int ST = 0>
 __global__ __launch_bounds__(256) void sign_f32_k(const float* __restrict__ x, float* __restrict__ y,
-                                                  int64_t n, int vec) {
+                                                  int64_t n, int vec, Stoch st = {}) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t skey = 0;
+  if constexpr (ST) skey = stoch_key(st);
+  auto sg = [&](float v, int64_t e) -> float {
+    if constexpr (ST) return (float)ssign(v, skey, (uint32_t)e);
+    else return (float)tsign(v);
+  };
   if (vec) {
     const int64_t n4 = n / 4;
     for (int64_t j = i; j < n4; j += stride) {
       float4 f = reinterpret_cast<const float4*>(x)[j];
-      f.x = (float)tsign(f.x);
-      f.y = (float)tsign(f.y);
-      f.z = (float)tsign(f.z);
-      f.w = (float)tsign(f.w);
+      f.x = sg(f.x, 4 * j);
+      f.y = sg(f.y, 4 * j + 1);
+      f.z = sg(f.z, 4 * j + 2);
+      f.w = sg(f.w, 4 * j + 3);
       reinterpret_cast<float4*>(y)[j] = f;
     }
-    for (int64_t j = n4 * 4 + i; j < n; j += stride) y[j] = (float)tsign(x[j]);
+    for (int64_t j = n4 * 4 + i; j < n; j += stride) y[j] = sg(x[j], j);
   } else {
-    for (int64_t j = i; j < n; j += stride) y[j] = (float)tsign(x[j]);
+    for (int64_t j = i; j < n; j += stride) y[j] = sg(x[j], j);
   }
 }
 
@@ -941,20 +964,20 @@ inline int grid_cap(int64_t want) { return (int)std::max<int64_t>(1, std::min<in
 
 using namespace bnn;
 
-BNN_API int bnn_sign_pack_i8(const float* x, int64_t M, int64_t K, int64_t ldx, int8_t* q,
-                             int64_t ldq, int8_t* qt, int64_t ldqt, void* stream) {
+// The stochastic twins (bnn_stoch_pack_*, bnn_bn_apply_pack_stoch*) share the deterministic entries'
+// checks and launch geometry: each entry below is one body with st == nullptr (sign) or the draw's seed.
+static int sign_pack_i8_impl(const char* name, const float* x, int64_t M, int64_t K, int64_t ldx, int8_t* q,
+                             int64_t ldq, int8_t* qt, int64_t ldqt, const Stoch* st, void* stream) {
   if (!x || M < 0 || K < 0 || ldx < K || (!q && !qt)) {
-    set_error("bnn_sign_pack_i8: bad arguments (M=%lld K=%lld ldx=%lld)", (long long)M,
-              (long long)K, (long long)ldx);
+    set_error("%s: bad arguments (M=%lld K=%lld ldx=%lld)", name, (long long)M, (long long)K, (long long)ldx);
     return kErrInval;
   }
   if (q && (ldq % TILE != 0 || ldq < round_up(K, TILE) || !aligned16(q))) {
-    set_error("bnn_sign_pack_i8: ldq=%lld must be a multiple of 64 >= round_up(K,64), q 16-B aligned",
-              (long long)ldq);
+    set_error("%s: ldq=%lld must be a multiple of 64 >= round_up(K,64), q 16-B aligned", name, (long long)ldq);
     return kErrInval;
   }
   if (qt && (ldqt % TILE != 0 || ldqt < round_up(M, TILE) || !aligned16(qt))) {
-    set_error("bnn_sign_pack_i8: ldqt=%lld must be a multiple of 64 >= round_up(M,64)", (long long)ldqt);
+    set_error("%s: ldqt=%lld must be a multiple of 64 >= round_up(M,64)", name, (long long)ldqt);
     return kErrInval;
   }
   if (M == 0 && !qt) return 0;
@@ -963,81 +986,139 @@ BNN_API int bnn_sign_pack_i8(const float* x, int64_t M, int64_t K, int64_t ldx, 
   const int64_t gy = qt ? ldqt / TILE : (M + TILE - 1) / TILE;
   if (gx == 0 || gy == 0) return 0;
   if (gy > 65535) {
-    set_error("bnn_sign_pack_i8: M too large for one launch (%lld)", (long long)M);
+    set_error("%s: M too large for one launch (%lld)", name, (long long)M);
     return kErrInval;
   }
-  hipLaunchKernelGGL(sign_pack_tile_k<0>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x,
-                     M, K, ldx, q, ldq, qt, ldqt, vec);
-  return check_launch("bnn_sign_pack_i8");
+  if (st)
+    hipLaunchKernelGGL((sign_pack_tile_k<0, 0, 0, 1>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x,
+                       M, K, ldx, q, ldq, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0, AdamArgs{}, 0, *st);
+  else
+    hipLaunchKernelGGL(sign_pack_tile_k<0>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x,
+                       M, K, ldx, q, ldq, qt, ldqt, vec);
+  return check_launch(name);
 }
 
-BNN_API int bnn_sign_f32(const float* x, float* y, int64_t n, void* stream);
+BNN_API int bnn_sign_pack_i8(const float* x, int64_t M, int64_t K, int64_t ldx, int8_t* q,
+                             int64_t ldq, int8_t* qt, int64_t ldqt, void* stream) {
+  return sign_pack_i8_impl("bnn_sign_pack_i8", x, M, K, ldx, q, ldq, qt, ldqt, nullptr, stream);
+}
+
+BNN_API int bnn_stoch_pack_i8(const float* x, int64_t M, int64_t K, int64_t ldx, int8_t* q, int64_t ldq, int8_t* qt,
+                              int64_t ldqt, uint64_t seed, void* stream) {
+  const Stoch st = make_stoch(seed);
+  return sign_pack_i8_impl("bnn_stoch_pack_i8", x, M, K, ldx, q, ldq, qt, ldqt, &st, stream);
+}
 
 // Whether bnn_sign_pack_fp4 takes the 256 x 256-tile kernel (bn_apply_pack_fp4_k<0, 1>): both outputs
 // as FP4 (rows + transpose or panel transpose), whole 256-column tiles, dense 16-B aligned rows, and a
 // grid of >= 1024 tiles (below that the 64 x 64 tiles fill the chip better).
+// force (the stochastic entries' argument, for tests): the form whenever the shape allows it, at any grid.
 static bool sp_wide_ok(const float* x, int64_t M, int64_t K, int64_t ldx, const uint8_t* q4, int64_t ldq4,
-                       const int8_t* qt, int64_t ldqt, int32_t qt_fmt) {
+                       const int8_t* qt, int64_t ldqt, int32_t qt_fmt, bool force = false) {
   return q4 && qt && (qt_fmt == 1 || qt_fmt == 2) && K % AP_T == 0 && ldx == K && 2 * ldq4 == K && aligned16(x) &&
-         (K / AP_T) * ((M + AP_T - 1) / AP_T) >= 1024 && (M + AP_T - 1) / AP_T <= 65535 &&
+         M > 0 && K > 0 && (force || (K / AP_T) * ((M + AP_T - 1) / AP_T) >= 1024) && (M + AP_T - 1) / AP_T <= 65535 &&
          2 * ldqt >= (M + AP_T - 1) / AP_T * AP_T;
 }
 
-BNN_API int bnn_sign_pack_fp4(const float* x, int64_t M, int64_t K, int64_t ldx, uint8_t* q4, int64_t ldq4,
-                              int8_t* qt, int64_t ldqt, int32_t qt_fmt, void* stream) {
+// the 256 x 256-tile plain pack (IDN = 1), with the fp32 write-back when sout != null
+static void launch_wide_pack(const float* x, int64_t M, int64_t K, uint8_t* q4, int64_t ldq4, int8_t* qt,
+                             int64_t ldqt, int32_t qt_fmt, float* sout, const Stoch* st, void* stream) {
+  const dim3 grid((unsigned)(K / AP_T), (unsigned)((M + AP_T - 1) / AP_T));
+  const int64_t pnks = qt_fmt == 2 ? ldqt / 32 : (int64_t)0;
+  if (st)
+    hipLaunchKernelGGL((bn_apply_pack_fp4_k<0, 1, 1>), grid, dim3(256), 0, S(stream), XIn{x, nullptr}, M, K,
+                       ColAffine{}, q4, ldq4, reinterpret_cast<uint8_t*>(qt), ldqt, pnks, sout, *st);
+  else
+    hipLaunchKernelGGL((bn_apply_pack_fp4_k<0, 1>), grid, dim3(256), 0, S(stream), XIn{x, nullptr}, M, K,
+                       ColAffine{}, q4, ldq4, reinterpret_cast<uint8_t*>(qt), ldqt, pnks, sout);
+}
+
+static int sign_pack_fp4_impl(const char* name, const float* x, int64_t M, int64_t K, int64_t ldx, uint8_t* q4,
+                              int64_t ldq4, int8_t* qt, int64_t ldqt, int32_t qt_fmt, const Stoch* st, bool force,
+                              void* stream) {
   if (!x || M < 0 || K < 0 || ldx < K || (!q4 && !qt)) {
-    set_error("bnn_sign_pack_fp4: bad arguments (M=%lld K=%lld ldx=%lld)", (long long)M, (long long)K,
-              (long long)ldx);
+    set_error("%s: bad arguments (M=%lld K=%lld ldx=%lld)", name, (long long)M, (long long)K, (long long)ldx);
     return kErrInval;
   }
   if (q4 && (ldq4 % 128 != 0 || 2 * ldq4 < round_up(K, 256) || !aligned16(q4))) {
-    set_error("bnn_sign_pack_fp4: ldq4=%lld bytes must be a multiple of 128 covering round_up(K,256)",
-              (long long)ldq4);
+    set_error("%s: ldq4=%lld bytes must be a multiple of 128 covering round_up(K,256)", name, (long long)ldq4);
     return kErrInval;
   }
   if (!qt_ok(qt, M, ldqt, qt_fmt)) {
-    set_error("bnn_sign_pack_fp4: ldqt=%lld does not cover M=%lld in qt_fmt %d", (long long)ldqt, (long long)M,
-              qt_fmt);
+    set_error("%s: ldqt=%lld does not cover M=%lld in qt_fmt %d", name, (long long)ldqt, (long long)M, qt_fmt);
     return kErrInval;
   }
   if (M == 0 && !qt) return 0;
   const int vec = aligned16(x) && (ldx % 4 == 0);
-  if (sp_wide_ok(x, M, K, ldx, q4, ldq4, qt, ldqt, qt_fmt)) {   // the 256 x 256-tile form, same codes
-    hipLaunchKernelGGL((bn_apply_pack_fp4_k<0, 1>), dim3((unsigned)(K / AP_T), (unsigned)((M + AP_T - 1) / AP_T)),
-                       dim3(256), 0, S(stream), XIn{x, nullptr}, M, K, ColAffine{}, q4, ldq4,
-                       reinterpret_cast<uint8_t*>(qt), ldqt, qt_fmt == 2 ? ldqt / 32 : (int64_t)0, nullptr);
-    return check_launch("bnn_sign_pack_fp4");
+  if (sp_wide_ok(x, M, K, ldx, q4, ldq4, qt, ldqt, qt_fmt, force)) {   // the 256 x 256-tile form, same codes
+    launch_wide_pack(x, M, K, q4, ldq4, qt, ldqt, qt_fmt, nullptr, st, stream);
+    return check_launch(name);
   }
   const int64_t gx = q4 ? (2 * ldq4) / TILE : (K + TILE - 1) / TILE;
   const int64_t gy = qt ? qt_tiles(ldqt, qt_fmt) : (M + TILE - 1) / TILE;
   if (gx == 0 || gy == 0) return 0;
   if (gy > 65535) {
-    set_error("bnn_sign_pack_fp4: M too large for one launch (%lld)", (long long)M);
+    set_error("%s: M too large for one launch (%lld)", name, (long long)M);
     return kErrInval;
   }
-  hipLaunchKernelGGL(sign_pack_tile_k<1>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x, M, K,
-                     ldx, reinterpret_cast<int8_t*>(q4), ldq4, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0, AdamArgs{},
-                     qt_fmt);
-  return check_launch("bnn_sign_pack_fp4");
+  if (st)
+    hipLaunchKernelGGL((sign_pack_tile_k<1, 0, 0, 1>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x,
+                       M, K, ldx, reinterpret_cast<int8_t*>(q4), ldq4, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0,
+                       AdamArgs{}, qt_fmt, *st);
+  else
+    hipLaunchKernelGGL(sign_pack_tile_k<1>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x, M, K,
+                       ldx, reinterpret_cast<int8_t*>(q4), ldq4, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0,
+                       AdamArgs{}, qt_fmt);
+  return check_launch(name);
 }
+
+BNN_API int bnn_sign_pack_fp4(const float* x, int64_t M, int64_t K, int64_t ldx, uint8_t* q4, int64_t ldq4,
+                              int8_t* qt, int64_t ldqt, int32_t qt_fmt, void* stream) {
+  return sign_pack_fp4_impl("bnn_sign_pack_fp4", x, M, K, ldx, q4, ldq4, qt, ldqt, qt_fmt, nullptr, false, stream);
+}
+
+BNN_API int bnn_stoch_pack_fp4(const float* x, int64_t M, int64_t K, int64_t ldx, uint8_t* q4, int64_t ldq4,
+                               int8_t* qt, int64_t ldqt, int32_t qt_fmt, uint64_t seed, int32_t force,
+                               void* stream) {
+  const Stoch st = make_stoch(seed);
+  return sign_pack_fp4_impl("bnn_stoch_pack_fp4", x, M, K, ldx, q4, ldq4, qt, ldqt, qt_fmt, &st, force != 0, stream);
+}
+
+static int sign_f32_impl(const char* name, const float* x, float* y, int64_t n, const Stoch* st, void* stream);
 
 // bnn_sign_pack_fp4 + the fp32 sign write-back sout[m][k] = sign(x[m][k]) (row pitch K; may be x) from
 // one read of x when the 256 x 256-tile form applies; otherwise the two passes.
-BNN_API int bnn_sign_pack_fp4_out(const float* x, int64_t M, int64_t K, uint8_t* q4, int64_t ldq4, int8_t* qt,
-                                  int64_t ldqt, int32_t qt_fmt, float* sout, void* stream) {
+static int sign_pack_fp4_out_impl(const char* name, const float* x, int64_t M, int64_t K, uint8_t* q4, int64_t ldq4,
+                                  int8_t* qt, int64_t ldqt, int32_t qt_fmt, float* sout, const Stoch* st, bool force,
+                                  void* stream) {
   if (!sout) {
-    set_error("bnn_sign_pack_fp4_out: sout required");
+    set_error("%s: sout required", name);
     return kErrInval;
   }
-  if (sp_wide_ok(x, M, K, K, q4, ldq4, qt, ldqt, qt_fmt) && aligned16(sout)) {
-    hipLaunchKernelGGL((bn_apply_pack_fp4_k<0, 1>), dim3((unsigned)(K / AP_T), (unsigned)((M + AP_T - 1) / AP_T)),
-                       dim3(256), 0, S(stream), XIn{x, nullptr}, M, K, ColAffine{}, q4, ldq4,
-                       reinterpret_cast<uint8_t*>(qt), ldqt, qt_fmt == 2 ? ldqt / 32 : (int64_t)0, sout);
-    return check_launch("bnn_sign_pack_fp4_out");
+  if (x && sp_wide_ok(x, M, K, K, q4, ldq4, qt, ldqt, qt_fmt, force) && aligned16(q4) && ldq4 % 128 == 0 &&
+      qt_ok(qt, M, ldqt, qt_fmt) && aligned16(sout)) {
+    launch_wide_pack(x, M, K, q4, ldq4, qt, ldqt, qt_fmt, sout, st, stream);
+    return check_launch(name);
   }
-  const int rc = bnn_sign_pack_fp4(x, M, K, K, q4, ldq4, qt, ldqt, qt_fmt, stream);
+  // the two passes: the pack reads x before the write-back (sout may be x) replaces it; both draw the
+  // same (seed, m * K + k)
+  const int rc = sign_pack_fp4_impl(name, x, M, K, K, q4, ldq4, qt, ldqt, qt_fmt, st, false, stream);
   if (rc != 0) return rc;
-  return bnn_sign_f32(x, sout, M * K, stream);
+  return sign_f32_impl(name, x, sout, M * K, st, stream);
+}
+
+BNN_API int bnn_sign_pack_fp4_out(const float* x, int64_t M, int64_t K, uint8_t* q4, int64_t ldq4, int8_t* qt,
+                                  int64_t ldqt, int32_t qt_fmt, float* sout, void* stream) {
+  return sign_pack_fp4_out_impl("bnn_sign_pack_fp4_out", x, M, K, q4, ldq4, qt, ldqt, qt_fmt, sout, nullptr, false,
+                                stream);
+}
+
+BNN_API int bnn_stoch_pack_fp4_out(const float* x, int64_t M, int64_t K, uint8_t* q4, int64_t ldq4, int8_t* qt,
+                                   int64_t ldqt, int32_t qt_fmt, float* sout, uint64_t seed, int32_t force,
+                                   void* stream) {
+  const Stoch st = make_stoch(seed);
+  return sign_pack_fp4_out_impl("bnn_stoch_pack_fp4_out", x, M, K, q4, ldq4, qt, ldqt, qt_fmt, sout, &st, force != 0,
+                                stream);
 }
 
 // tuning hook (bnn_adam_pack_set_tile256): 1 (default) = the 256 x 256-tile kernel for grids of at
@@ -1126,16 +1207,28 @@ BNN_API int bnn_adam_clamp_pack_sched(float* p, const float* grad, float* exp_av
   return adam_clamp_pack_impl(p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
 }
 
-BNN_API int bnn_sign_f32(const float* x, float* y, int64_t n, void* stream) {
+static int sign_f32_impl(const char* name, const float* x, float* y, int64_t n, const Stoch* st, void* stream) {
   if (!x || !y || n < 0) {
-    set_error("bnn_sign_f32: bad arguments");
+    set_error("%s: bad arguments", name);
     return kErrInval;
   }
   if (n == 0) return 0;
   const int vec = aligned16(x) && aligned16(y);
-  hipLaunchKernelGGL(sign_f32_k, dim3(grid_cap((n / 4 + 255) / 256)), dim3(256), 0, S(stream), x, y,
-                     n, vec);
-  return check_launch("bnn_sign_f32");
+  if (st)
+    hipLaunchKernelGGL(sign_f32_k<1>, dim3(grid_cap((n / 4 + 255) / 256)), dim3(256), 0, S(stream), x, y, n, vec,
+                       *st);
+  else
+    hipLaunchKernelGGL(sign_f32_k<0>, dim3(grid_cap((n / 4 + 255) / 256)), dim3(256), 0, S(stream), x, y, n, vec);
+  return check_launch(name);
+}
+
+BNN_API int bnn_sign_f32(const float* x, float* y, int64_t n, void* stream) {
+  return sign_f32_impl("bnn_sign_f32", x, y, n, nullptr, stream);
+}
+
+BNN_API int bnn_binarize_stoch_f32(const float* x, float* y, int64_t n, uint64_t seed, void* stream) {
+  const Stoch st = make_stoch(seed);
+  return sign_f32_impl("bnn_binarize_stoch_f32", x, y, n, &st, stream);
 }
 
 BNN_API int bnn_sign_pack_bits(const float* x, int64_t M, int64_t K, int64_t ldx, uint32_t* sbits,
@@ -1218,15 +1311,16 @@ BNN_API int bnn_quant_cols_t(const float* x, int64_t M, int64_t N, int64_t ldx, 
 #ifndef AP_FAST_MIN_TILES
 #define AP_FAST_MIN_TILES 1024
 #endif
-BNN_API int bnn_bn_apply_pack(const float* x, int64_t M, int64_t C, const float* mean, const float* invstd,
-                              const float* mean_lo, const float* gamma, const float* beta, int32_t fmt, void* q,
-                              int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt, void* stream) {
+static int bn_apply_pack_impl(const char* name, const float* x, int64_t M, int64_t C, const float* mean,
+                              const float* invstd, const float* mean_lo, const float* gamma, const float* beta,
+                              int32_t fmt, void* q, int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt,
+                              const Stoch* st, bool force, void* stream) {
   const int64_t need = fmt == 1 ? round_up(C, 256) / 2 : round_up(C, TILE);
   const int qf = qt_fmt == 2 ? 1 : qt_fmt;   // 2 = FP4 transpose in the panel layout
   if (!x || !mean || !invstd || M < 0 || C < 0 || (fmt != 0 && fmt != 1) || (!q && !qt) ||
       (q && (ldq < need || ldq % (fmt == 1 ? 128 : TILE) != 0 || !aligned16(q))) || !qt_ok(qt, M, ldqt, qf)) {
-    set_error("bnn_bn_apply_pack: bad arguments (M=%lld C=%lld fmt=%d ldq=%lld ldqt=%lld)", (long long)M,
-              (long long)C, fmt, (long long)ldq, (long long)ldqt);
+    set_error("%s: bad arguments (M=%lld C=%lld fmt=%d ldq=%lld ldqt=%lld)", name, (long long)M, (long long)C, fmt,
+              (long long)ldq, (long long)ldqt);
     return kErrInval;
   }
   if (M == 0 && !qt) return 0;
@@ -1235,60 +1329,111 @@ BNN_API int bnn_bn_apply_pack(const float* x, int64_t M, int64_t C, const float*
   const int64_t gy = qt ? qt_tiles(ldqt, qf) : (M + TILE - 1) / TILE;
   if (gx == 0 || gy == 0) return 0;
   if (gy > 65535) {
-    set_error("bnn_bn_apply_pack: M too large for one launch (%lld)", (long long)M);
+    set_error("%s: M too large for one launch (%lld)", name, (long long)M);
     return kErrInval;
   }
   const ColAffine af{mean, mean_lo, invstd, gamma, beta,
                      aligned16(mean) && aligned16(invstd) && (!gamma || aligned16(gamma)) &&
                          (!beta || aligned16(beta)) && (!mean_lo || aligned16(mean_lo))};
-  const bool fast = fmt == 1 && q && qt && (qt_fmt == 1 || qt_fmt == 2) && C % AP_T == 0 && af.vec && vec &&
-                    (C / AP_T) * ((M + AP_T - 1) / AP_T) >= AP_FAST_MIN_TILES;
+  // force (the stochastic entry's argument, for tests): the 256 x 256 form at any grid the shape allows
+  const bool fast = fmt == 1 && q && qt && (qt_fmt == 1 || qt_fmt == 2) && C % AP_T == 0 && af.vec && vec && M > 0 &&
+                    C > 0 && (force || (C / AP_T) * ((M + AP_T - 1) / AP_T) >= AP_FAST_MIN_TILES);
   if (fast) {
-    hipLaunchKernelGGL((bn_apply_pack_fp4_k<0>), dim3((unsigned)(C / AP_T), (unsigned)((M + AP_T - 1) / AP_T)),
-                       dim3(256), 0, S(stream), XIn{x, nullptr}, M, C, af, reinterpret_cast<uint8_t*>(q), ldq,
-                       reinterpret_cast<uint8_t*>(qt), ldqt, qt_fmt == 2 ? ldqt / 32 : (int64_t)0);
-    return check_launch("bnn_bn_apply_pack");
+    const dim3 grid((unsigned)(C / AP_T), (unsigned)((M + AP_T - 1) / AP_T));
+    const int64_t pnks = qt_fmt == 2 ? ldqt / 32 : (int64_t)0;
+    if (st)
+      hipLaunchKernelGGL((bn_apply_pack_fp4_k<0, 0, 1>), grid, dim3(256), 0, S(stream), XIn{x, nullptr}, M, C, af,
+                         reinterpret_cast<uint8_t*>(q), ldq, reinterpret_cast<uint8_t*>(qt), ldqt, pnks, nullptr, *st);
+    else
+      hipLaunchKernelGGL((bn_apply_pack_fp4_k<0>), grid, dim3(256), 0, S(stream), XIn{x, nullptr}, M, C, af,
+                         reinterpret_cast<uint8_t*>(q), ldq, reinterpret_cast<uint8_t*>(qt), ldqt, pnks);
+    return check_launch(name);
   }
   // 4 row tiles per workgroup when that still leaves >= 8K workgroups (amortised parameter loads)
   const int rt = (gx * ((gy + 3) / 4) >= 8192) ? 4 : 1;
   const unsigned gyr = (unsigned)((gy + rt - 1) / rt);
-  if (fmt == 1)
+  if (st && fmt == 1)
+    hipLaunchKernelGGL((sign_pack_tile_k<1, 1, 0, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
+                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, AdamArgs{}, qt_fmt, *st);
+  else if (st)
+    hipLaunchKernelGGL((sign_pack_tile_k<0, 1, 0, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
+                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, AdamArgs{}, qt_fmt, *st);
+  else if (fmt == 1)
     hipLaunchKernelGGL((sign_pack_tile_k<1, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
                        C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, AdamArgs{}, qt_fmt);
   else
     hipLaunchKernelGGL((sign_pack_tile_k<0, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
                        C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, AdamArgs{}, qt_fmt);
-  return check_launch("bnn_bn_apply_pack");
+  return check_launch(name);
+}
+
+BNN_API int bnn_bn_apply_pack(const float* x, int64_t M, int64_t C, const float* mean, const float* invstd,
+                              const float* mean_lo, const float* gamma, const float* beta, int32_t fmt, void* q,
+                              int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt, void* stream) {
+  return bn_apply_pack_impl("bnn_bn_apply_pack", x, M, C, mean, invstd, mean_lo, gamma, beta, fmt, q, ldq, qt, ldqt,
+                            qt_fmt, nullptr, false, stream);
+}
+
+BNN_API int bnn_bn_apply_pack_stoch(const float* x, int64_t M, int64_t C, const float* mean, const float* invstd,
+                                    const float* mean_lo, const float* gamma, const float* beta, int32_t fmt, void* q,
+                                    int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt, uint64_t seed,
+                                    int32_t force, void* stream) {
+  const Stoch st = make_stoch(seed);
+  return bn_apply_pack_impl("bnn_bn_apply_pack_stoch", x, M, C, mean, invstd, mean_lo, gamma, beta, fmt, q, ldq, qt,
+                            ldqt, qt_fmt, &st, force != 0, stream);
 }
 
 // bnn_bn_apply_pack for the int16 form of the BatchNorm input (XIn z16: x = fl(I + xbias), the
 // output of bnn_gemm_fp4_i16): FP4 rows + FP4 transpose only, C % 256 == 0, any M.
-BNN_API int bnn_bn_apply_pack_i16(const int16_t* x16, const float* xbias, int64_t M, int64_t C, const float* mean,
-                                  const float* invstd, const float* mean_lo, const float* gamma, const float* beta,
-                                  uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldqt, int32_t qt_panel,
-                                  void* stream) {
+static int bn_apply_pack_i16_impl(const char* name, const int16_t* x16, const float* xbias, int64_t M, int64_t C,
+                                  const float* mean, const float* invstd, const float* mean_lo, const float* gamma,
+                                  const float* beta, uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldqt,
+                                  int32_t qt_panel, const Stoch* st, void* stream) {
   const ColAffine af{mean, mean_lo, invstd, gamma, beta,
                      aligned16(mean) && aligned16(invstd) && (!gamma || aligned16(gamma)) &&
                          (!beta || aligned16(beta)) && (!mean_lo || aligned16(mean_lo))};
   if (!x16 || (reinterpret_cast<uintptr_t>(x16) & 7) != 0 || (xbias && !aligned16(xbias)) || !mean || !invstd ||
       !af.vec || M <= 0 || C <= 0 || C % AP_T != 0 || !q || !qt || ldq < C / 2 || !aligned16(q) ||
       !qt_ok(reinterpret_cast<const int8_t*>(qt), M, ldqt, 1) || (M + AP_T - 1) / AP_T > 65535) {
-    set_error("bnn_bn_apply_pack_i16: bad arguments (M=%lld C=%lld ldq=%lld ldqt=%lld; C %% 256 == 0)", (long long)M,
+    set_error("%s: bad arguments (M=%lld C=%lld ldq=%lld ldqt=%lld; C %% 256 == 0)", name, (long long)M,
               (long long)C, (long long)ldq, (long long)ldqt);
     return kErrInval;
   }
-  hipLaunchKernelGGL((bn_apply_pack_fp4_k<1>), dim3((unsigned)(C / AP_T), (unsigned)((M + AP_T - 1) / AP_T)),
-                     dim3(256), 0, S(stream), XIn{x16, xbias}, M, C, af, q, ldq, qt, ldqt, qt_panel ? ldqt / 32 : (int64_t)0);
-  return check_launch("bnn_bn_apply_pack_i16");
+  const dim3 grid((unsigned)(C / AP_T), (unsigned)((M + AP_T - 1) / AP_T));
+  const int64_t pnks = qt_panel ? ldqt / 32 : (int64_t)0;
+  if (st)
+    hipLaunchKernelGGL((bn_apply_pack_fp4_k<1, 0, 1>), grid, dim3(256), 0, S(stream), XIn{x16, xbias}, M, C, af, q,
+                       ldq, qt, ldqt, pnks, nullptr, *st);
+  else
+    hipLaunchKernelGGL((bn_apply_pack_fp4_k<1>), grid, dim3(256), 0, S(stream), XIn{x16, xbias}, M, C, af, q, ldq, qt,
+                       ldqt, pnks);
+  return check_launch(name);
+}
+
+BNN_API int bnn_bn_apply_pack_i16(const int16_t* x16, const float* xbias, int64_t M, int64_t C, const float* mean,
+                                  const float* invstd, const float* mean_lo, const float* gamma, const float* beta,
+                                  uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldqt, int32_t qt_panel,
+                                  void* stream) {
+  return bn_apply_pack_i16_impl("bnn_bn_apply_pack_i16", x16, xbias, M, C, mean, invstd, mean_lo, gamma, beta, q, ldq,
+                                qt, ldqt, qt_panel, nullptr, stream);
+}
+
+BNN_API int bnn_bn_apply_pack_stoch_i16(const int16_t* x16, const float* xbias, int64_t M, int64_t C,
+                                        const float* mean, const float* invstd, const float* mean_lo,
+                                        const float* gamma, const float* beta, uint8_t* q, int64_t ldq, uint8_t* qt,
+                                        int64_t ldqt, int32_t qt_panel, uint64_t seed, void* stream) {
+  const Stoch st = make_stoch(seed);
+  return bn_apply_pack_i16_impl("bnn_bn_apply_pack_stoch_i16", x16, xbias, M, C, mean, invstd, mean_lo, gamma, beta, q,
+                                ldq, qt, ldqt, qt_panel, &st, stream);
 }
 
 // bnn_bn_apply_pack for the s20 form of the BatchNorm input (XIn XF 2: x = fl(fl(S * xscale) +
 // xbias) from the u8-pixel layer's 20-bit sums, bnn_gemm_i8_affine_bnstats_s20): FP4 rows + FP4
 // transpose only, C % 256 == 0, any M.
-BNN_API int bnn_bn_apply_pack_s20(const int16_t* xlo, const uint8_t* xhi, const float* xbias, float xscale, int64_t M,
-                                  int64_t C, const float* mean, const float* invstd, const float* mean_lo,
-                                  const float* gamma, const float* beta, uint8_t* q, int64_t ldq, uint8_t* qt,
-                                  int64_t ldqt, int32_t qt_panel, void* stream) {
+static int bn_apply_pack_s20_impl(const char* name, const int16_t* xlo, const uint8_t* xhi, const float* xbias,
+                                  float xscale, int64_t M, int64_t C, const float* mean, const float* invstd,
+                                  const float* mean_lo, const float* gamma, const float* beta, uint8_t* q, int64_t ldq,
+                                  uint8_t* qt, int64_t ldqt, int32_t qt_panel, const Stoch* st, void* stream) {
   const ColAffine af{mean, mean_lo, invstd, gamma, beta,
                      aligned16(mean) && aligned16(invstd) && (!gamma || aligned16(gamma)) &&
                          (!beta || aligned16(beta)) && (!mean_lo || aligned16(mean_lo))};
@@ -1296,14 +1441,37 @@ BNN_API int bnn_bn_apply_pack_s20(const int16_t* xlo, const uint8_t* xhi, const 
       (xbias && !aligned16(xbias)) || !mean || !invstd || !af.vec || M <= 0 || C <= 0 || C % AP_T != 0 || !q || !qt ||
       ldq < C / 2 || !aligned16(q) || !qt_ok(reinterpret_cast<const int8_t*>(qt), M, ldqt, 1) ||
       (M + AP_T - 1) / AP_T > 65535) {
-    set_error("bnn_bn_apply_pack_s20: bad arguments (M=%lld C=%lld ldq=%lld ldqt=%lld; C %% 256 == 0)", (long long)M,
+    set_error("%s: bad arguments (M=%lld C=%lld ldq=%lld ldqt=%lld; C %% 256 == 0)", name, (long long)M,
               (long long)C, (long long)ldq, (long long)ldqt);
     return kErrInval;
   }
-  hipLaunchKernelGGL((bn_apply_pack_fp4_k<2>), dim3((unsigned)(C / AP_T), (unsigned)((M + AP_T - 1) / AP_T)),
-                     dim3(256), 0, S(stream), XIn{xlo, xbias, xhi, xscale}, M, C, af, q, ldq, qt, ldqt,
-                     qt_panel ? ldqt / 32 : (int64_t)0);
-  return check_launch("bnn_bn_apply_pack_s20");
+  const dim3 grid((unsigned)(C / AP_T), (unsigned)((M + AP_T - 1) / AP_T));
+  const int64_t pnks = qt_panel ? ldqt / 32 : (int64_t)0;
+  if (st)
+    hipLaunchKernelGGL((bn_apply_pack_fp4_k<2, 0, 1>), grid, dim3(256), 0, S(stream), XIn{xlo, xbias, xhi, xscale}, M,
+                       C, af, q, ldq, qt, ldqt, pnks, nullptr, *st);
+  else
+    hipLaunchKernelGGL((bn_apply_pack_fp4_k<2>), grid, dim3(256), 0, S(stream), XIn{xlo, xbias, xhi, xscale}, M, C, af,
+                       q, ldq, qt, ldqt, pnks);
+  return check_launch(name);
+}
+
+BNN_API int bnn_bn_apply_pack_s20(const int16_t* xlo, const uint8_t* xhi, const float* xbias, float xscale, int64_t M,
+                                  int64_t C, const float* mean, const float* invstd, const float* mean_lo,
+                                  const float* gamma, const float* beta, uint8_t* q, int64_t ldq, uint8_t* qt,
+                                  int64_t ldqt, int32_t qt_panel, void* stream) {
+  return bn_apply_pack_s20_impl("bnn_bn_apply_pack_s20", xlo, xhi, xbias, xscale, M, C, mean, invstd, mean_lo, gamma,
+                                beta, q, ldq, qt, ldqt, qt_panel, nullptr, stream);
+}
+
+BNN_API int bnn_bn_apply_pack_stoch_s20(const int16_t* xlo, const uint8_t* xhi, const float* xbias, float xscale,
+                                        int64_t M, int64_t C, const float* mean, const float* invstd,
+                                        const float* mean_lo, const float* gamma, const float* beta, uint8_t* q,
+                                        int64_t ldq, uint8_t* qt, int64_t ldqt, int32_t qt_panel, uint64_t seed,
+                                        void* stream) {
+  const Stoch st = make_stoch(seed);
+  return bn_apply_pack_s20_impl("bnn_bn_apply_pack_stoch_s20", xlo, xhi, xbias, xscale, M, C, mean, invstd, mean_lo,
+                                gamma, beta, q, ldq, qt, ldqt, qt_panel, &st, stream);
 }
 
 namespace bnn {

@@ -67,6 +67,31 @@ int bnn_sign_f32(const float* x, float* y, int64_t n, bnn_stream_t stream);
 int bnn_sign_pack_fp4_out(const float* x, int64_t M, int64_t K, uint8_t* q4, int64_t ldq4, int8_t* qt,
                           int64_t ldqt, int32_t qt_fmt, float* sout, bnn_stream_t stream);
 
+/* Stochastic binarization -- Binarize(t, 'stoch') of :14-15, round(clamp((x+1)/2 + U(-.5,.5), 0, 1))*2 - 1
+ * -- as the same single pass as each deterministic entry above.  Element i = m*K + k (mod 2^32) of the
+ * logical row-major [M][K] input draws
+ *   p = min(max(fmaf(x, 0.5f, 0.5f), 0), 1),  t = (uint32_t)(p * 2^24),
+ *   s = isnan(x) ? 0 : ((hash(seed', i) >> 8) < t ? +1 : -1)
+ * with the dropout passes' counter-based hash and seed' = seed + ctr[0] * 0xD1B54A32D192ED03 while a
+ * device step counter is set (bnn_set_seed_counter).  x >= 1 gives +1 and x <= -1 gives -1 always; the
+ * result is never 0 except for NaN.  Every entry draws the same s for the same (x, seed, i), so the packed
+ * forms equal the deterministic packers applied to bnn_binarize_stoch_f32's output byte for byte (padding
+ * stays 0).  Arguments, layouts and checks are those of the deterministic twin:
+ *   bnn_binarize_stoch_f32  ~ bnn_sign_f32 (n = M*K; y may alias x)
+ *   bnn_stoch_pack_i8       ~ bnn_sign_pack_i8
+ *   bnn_stoch_pack_fp4      ~ bnn_sign_pack_fp4
+ *   bnn_stoch_pack_fp4_out  ~ bnn_sign_pack_fp4_out (sout may alias x)
+ * force != 0 takes the 256 x 256-tile form whenever the shape allows it, below the 1024-tile threshold
+ * too (same bytes either way; for tests). */
+int bnn_binarize_stoch_f32(const float* x, float* y, int64_t n, uint64_t seed, bnn_stream_t stream);
+int bnn_stoch_pack_i8(const float* x, int64_t M, int64_t K, int64_t ldx, int8_t* q, int64_t ldq, int8_t* qt,
+                      int64_t ldqt, uint64_t seed, bnn_stream_t stream);
+int bnn_stoch_pack_fp4(const float* x, int64_t M, int64_t K, int64_t ldx, uint8_t* q4, int64_t ldq4, int8_t* qt,
+                       int64_t ldqt, int32_t qt_fmt, uint64_t seed, int32_t force, bnn_stream_t stream);
+int bnn_stoch_pack_fp4_out(const float* x, int64_t M, int64_t K, uint8_t* q4, int64_t ldq4, int8_t* qt,
+                           int64_t ldqt, int32_t qt_fmt, float* sout, uint64_t seed, int32_t force,
+                           bnn_stream_t stream);
+
 /* Bit-planes for the XNOR-popcount path: word w of row m holds k = 32w..32w+31 (bit k%32);
  * sbits = 1 where x<0, nzbits = 1 where x!=0.  ldw >= ceil(K/32) words, padding words zeroed. */
 int bnn_sign_pack_bits(const float* x, int64_t M, int64_t K, int64_t ldx, uint32_t* sbits,
@@ -593,6 +618,25 @@ int bnn_bn_apply_pack(const float* x, int64_t M, int64_t C, const float* mean, c
                       const float* mean_lo, const float* gamma, const float* beta, int32_t fmt, void* q,
                       int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt, bnn_stream_t stream);
 
+/* bnn_bn_apply_pack with the stochastic draw (bnn_binarize_stoch_f32 above) of y in place of sign(y),
+ * element index m*C + c: stochastic activations of the next binarized layer with no fp32 activation written
+ * (Hardtanh in front changes nothing: the draw's clamp absorbs it).  Bit-identical to
+ * bnn_binarize_stoch_f32 applied to the y that bnn_bn_fwd_* writes, then packed.  _i16 / _s20: the compact
+ * forms of the BatchNorm input (bnn_bn_apply_pack_i16 / bnn_bn_apply_pack_s20 below), same draw.
+ * force != 0: the 256 x 256-tile form whenever the shape allows it (for tests). */
+int bnn_bn_apply_pack_stoch(const float* x, int64_t M, int64_t C, const float* mean, const float* invstd,
+                            const float* mean_lo, const float* gamma, const float* beta, int32_t fmt, void* q,
+                            int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt, uint64_t seed, int32_t force,
+                            bnn_stream_t stream);
+int bnn_bn_apply_pack_stoch_i16(const int16_t* x16, const float* xbias, int64_t M, int64_t C, const float* mean,
+                                const float* invstd, const float* mean_lo, const float* gamma, const float* beta,
+                                uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldqt, int32_t qt_panel, uint64_t seed,
+                                bnn_stream_t stream);
+int bnn_bn_apply_pack_stoch_s20(const int16_t* xlo, const uint8_t* xhi, const float* xbias, float xscale, int64_t M,
+                                int64_t C, const float* mean, const float* invstd, const float* mean_lo,
+                                const float* gamma, const float* beta, uint8_t* q, int64_t ldq, uint8_t* qt,
+                                int64_t ldqt, int32_t qt_panel, uint64_t seed, bnn_stream_t stream);
+
 /* The int16 form of the BatchNorm input (z16): x16 [M][C] the int16 dot products of
  * bnn_gemm_fp4_i16 (8-B aligned), xbias [C] that layer's bias (16-B aligned, nullable), read as
  * x = fl(x16 + xbias) -- the value the fp32 GEMM epilogue stores, so every result is bit-identical
@@ -772,7 +816,8 @@ int bnn_adam_clamp_pack(float* p, const float* grad, float* exp_avg, float* exp_
  * bnn_adam_clamp_sched / bnn_adam_clamp_pack_sched: bnn_adam_clamp / bnn_adam_clamp_pack with
  * those two values taken from sched[2 * ctr[0]] on the device.
  * bnn_set_seed_counter: process-wide; while non-NULL every dropout launch (bnn_bn_dropout_*,
- * bnn_bn_bwd_q6, bnn_dropout_mask) draws its mask from seed + ctr[0] * 0xD1B54A32D192ED03. */
+ * bnn_bn_bwd_q6, bnn_dropout_mask) and every stochastic-binarization launch (bnn_binarize_stoch_f32,
+ * bnn_stoch_pack_*, bnn_bn_apply_pack_stoch*) draws from seed + ctr[0] * 0xD1B54A32D192ED03. */
 int bnn_adam_schedule(float lr, float beta1, float beta2, int64_t step0, int64_t n, float* out);
 /* bnn_adam_clamp (or, with sched/ctr non-NULL, bnn_adam_clamp_sched) over up to 16 tensors in one
  * launch: host arrays of `count` device pointers, element counts, Adam step counts and clamp
