@@ -63,6 +63,10 @@ SIGNATURES = {
     "bnn_cross_entropy_workspace": (I64, [I64]),
     "bnn_cross_entropy_fwd": (I32, [P, P, I64, I64, I64, P, P, I64, P]),
     "bnn_cross_entropy_bwd": (I32, [P, P, I64, I64, I64, P, P, P, P]),
+    "bnn_hinge_ok": (I32, [I64]),
+    "bnn_hinge_workspace": (I64, [I64, I64]),
+    "bnn_hinge_fwd": (I32, [P, P, P, I64, I64, F32, I32, P, P, I64, P]),
+    "bnn_hinge_bwd": (I32, [P, P, P, I64, I64, F32, I32, P, P, P]),
     "bnn_unit_to_pixels": (I32, [P, I64, P, P, P]),
     "bnn_pixels_pack": (I32, [P, I64, I64, I64, P, I64, P, I64, P]),
     "bnn_row_sums": (I32, [P, I64, I64, I64, P, P]),

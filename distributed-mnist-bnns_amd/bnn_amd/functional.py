@@ -1279,6 +1279,81 @@ def cross_entropy(p, target, ignore_index=-100):
     return CrossEntropyFunction.apply(p, target, int(ignore_index))
 
 
+class HingeLossFunction(torch.autograd.Function):
+    """mean(max(0, margin - input * target)) (``squared``: of its square) over all elements of the [M, C]
+    fp32 logits (bnn_hinge_*): the reference's HingeLoss / SqrtHingeLossFunction (models/
+    binarized_modules.py:20-54).  ``target`` is int64 class indices [M] -- the +-1 one-vs-all target is
+    formed in the kernel -- or a dense fp32 target of input's shape.  One launch forward up to 16384 rows
+    (two beyond), one backward that recomputes the margins from the inputs; the loss and its incoming
+    gradient stay on the device (no host synchronisation)."""
+
+    @staticmethod
+    def forward(ctx, input, target, margin=1.0, squared=False):
+        _check(input)
+        x = input.contiguous()
+        target = target.contiguous()
+        dense = target.dtype != torch.int64
+        if dense:
+            _check(target)
+        M, C = x.shape
+        y, t = (None, target) if dense else (target, None)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        work = torch.empty((int(L.lib().bnn_hinge_workspace(M, C)),), dtype=torch.uint8, device=x.device)
+        with _timed("hinge_fwd", 0, (8 if dense else 4) * M * C + (0 if dense else 8 * M)):
+            L.call("bnn_hinge_fwd", L.ptr(x), L.ptr(y), L.ptr(t), M, C, float(margin), int(bool(squared)),
+                   L.ptr(loss), L.ptr(work), work.numel(), L.stream())
+        ctx.save_for_backward(x, target)
+        ctx.args = (float(margin), bool(squared))
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        x, target = ctx.saved_tensors
+        return hinge_loss_backward(x, target, go, *ctx.args), None, None, None
+
+
+def hinge_loss_backward(input, target, go, margin=1.0, squared=False):
+    """d hinge_loss(input, target, margin, squared) / d input times the scalar ``go`` (a device tensor),
+    from the inputs alone: bnn_hinge_bwd recomputes the margins."""
+    _check(input)
+    x = input.contiguous()
+    target = target.contiguous()
+    dense = target.dtype != torch.int64
+    if dense:
+        _check(target)
+    M, C = x.shape
+    y, t = (None, target) if dense else (target, None)
+    dx = torch.empty_like(x)
+    go = go.to(torch.float32).contiguous()
+    with _timed("hinge_bwd", 0, (12 if dense else 8) * M * C + (0 if dense else 8 * M)):
+        L.call("bnn_hinge_bwd", L.ptr(x), L.ptr(y), L.ptr(t), M, C, float(margin), int(bool(squared)), L.ptr(go),
+               L.ptr(dx), L.stream())
+    return dx
+
+
+def hinge_loss_ok(input, target):
+    """Whether hinge_loss takes (input, target): CUDA fp32 [M, C] logits with a class count libbnn has,
+    and int64 labels [M] or a dense fp32 target of input's shape that needs no gradient."""
+    if not (torch.is_tensor(input) and torch.is_tensor(target) and input.is_cuda and input.dim() == 2
+            and input.dtype == torch.float32 and input.shape[0] > 0 and target.device == input.device
+            and bool(L.lib().bnn_hinge_ok(input.shape[1]))):
+        return False
+    if target.dtype == torch.int64:
+        return target.dim() == 1 and target.shape[0] == input.shape[0]
+    return target.dtype == torch.float32 and target.shape == input.shape and not target.requires_grad
+
+
+def hinge_loss(input, target, margin=1.0, squared=False):
+    """The mean hinge (``squared``: squared hinge) loss of the logits against int64 labels or a dense
+    target (HingeLossFunction); raises for anything hinge_loss_ok refuses."""
+    _check(input)
+    if not hinge_loss_ok(input, target):
+        raise ValueError("bnn_amd: hinge_loss needs float32 CUDA [M, C] logits (M > 0, C in 2, 10, 16, 32, 64) and "
+                         f"int64 [M] labels or a float32 target of the same shape without grad; got "
+                         f"{tuple(input.shape)} {input.dtype} and {tuple(target.shape)} {target.dtype}")
+    return HingeLossFunction.apply(input, target, float(margin), bool(squared))
+
+
 # ----------------------------------------------------------------------------- conv2d
 def _pair_same(v, what):
     if isinstance(v, (tuple, list)):

@@ -43,11 +43,17 @@ def _configure(module, org_protocol, mutate_input, backend=None):
 
 
 class MLP(nn.Module):
-    """mnist-dist2.py:46-76 with explicit widths."""
+    """mnist-dist2.py:46-76 with explicit widths.
+
+    ``log_softmax=False`` makes forward return fc4's logits -- what a hinge criterion (nn.HingeLoss,
+    nn.SqrtHingeLoss) takes -- instead of their LogSoftmax; no parameter, buffer or state_dict key
+    depends on it.  ``inference.freeze`` ignores the switch: a frozen model returns log-probabilities
+    whatever the net was trained with, and its predict / accuracy are argmax-invariant."""
 
     def __init__(self, h1, h2, h3, p_drop=0.3, org_protocol=True, mutate_input=True, backend=None,
-                 fused_bn=False, normalize=None, dropin_bn=False, stochastic=False):
+                 fused_bn=False, normalize=None, dropin_bn=False, stochastic=False, log_softmax=True):
         super().__init__()
+        self.log_softmax = log_softmax
         # stochastic: fc2 and fc3 binarise their inputs stochastically in training mode (fc1 takes
         # pixels); eval mode and the frozen model stay deterministic
         # dropin_bn: bn1..bn3 are bnn_amd.nn.BatchNorm1d (torch's module on libbnn's passes), the
@@ -117,6 +123,9 @@ class MLP(nn.Module):
         with BF.bn_counter_batch():          # the BatchNorms' num_batches_tracked += 1 in one launch
             return self._forward(x)
 
+    def _out(self, z):
+        return self.logsoftmax(z) if self.log_softmax else z
+
     def _forward(self, x):
         x = x.view(-1, 28 * 28)
         z1 = self.fc1(x, emit_compact=True) if self._s20(x) else self.fc1(x)
@@ -137,7 +146,7 @@ class MLP(nn.Module):
         if (self.fused_bn and self.fused_head and self.training and self.bn3.training
                 and BF.head_fusable(x, self.bn3, self.fc4)):
             # drop -> bn3 -> htanh3 -> fc4 as one libbnn head: h3 is never written
-            return self.logsoftmax(BF.dropout_bn_hardtanh_linear(x, self.drop.p, self.bn3, self.fc4))
+            return self._out(BF.dropout_bn_hardtanh_linear(x, self.drop.p, self.bn3, self.fc4))
         if (self.fused_bn and self.training and self.drop.p > 0 and self.bn3.training and x.is_cuda
                 and x.dim() == 2 and x.shape[1] % 4 == 0):
             # drop -> bn3 -> htanh3 as one libbnn op (mask regenerated in every pass, never stored)
@@ -145,8 +154,7 @@ class MLP(nn.Module):
         else:
             x = self.drop(x)
             x = self._bnh(self.bn3, self.htanh3, x)
-        x = self.fc4(x)
-        return self.logsoftmax(x)
+        return self._out(self.fc4(x))
 
 
 def Net(infl_ratio=3, **kw):
@@ -165,8 +173,13 @@ def WideNet(width=8192, **kw):
 
 
 class BinCNN(nn.Module):
-    def __init__(self, num_classes=10, org_protocol=True, mutate_input=True, fused_bn=False, stochastic=False):
+    """BASELINE config 4 (module docstring).  ``log_softmax=False``: forward returns the classifier's
+    logits, as MLP's switch (same parameters and state_dict; ``inference.freeze`` ignores it)."""
+
+    def __init__(self, num_classes=10, org_protocol=True, mutate_input=True, fused_bn=False, stochastic=False,
+                 log_softmax=True):
         super().__init__()
+        self.log_softmax = log_softmax
         # stochastic: layer2's conv binarises its input stochastically in training mode (layer1 takes pixels)
         # fused_bn: BatchNorm2d -> Hardtanh -> MaxPool2d of each layer run as one libbnn op (same
         # parameters, buffers and math; the Sequential modules and state_dict are unchanged)
@@ -196,13 +209,16 @@ class BinCNN(nn.Module):
         with BF.bn_counter_batch():          # the BatchNorms' num_batches_tracked += 1 in one launch
             return self._forward(x)
 
+    def _out(self, z):
+        return self.logsoftmax(z) if self.log_softmax else z
+
     def _forward(self, x):
         out = self._layer(self.layer2, self._layer(self.layer1, x))
         out = out.reshape(out.size(0), -1)
         if self.fused_bn and BF.linear_nsmall_ok(out, self.fc.weight):
             # the fp32 classifier through libbnn's narrow-Linear kernels (same parameters and math)
-            return self.logsoftmax(BF.linear_nsmall(out, self.fc.weight, self.fc.bias))
-        return self.logsoftmax(self.fc(out))
+            return self._out(BF.linear_nsmall(out, self.fc.weight, self.fc.bias))
+        return self._out(self.fc(out))
 
 
 MODELS = {"mlp": Net, "small": SmallNet, "wide": WideNet, "cnn": BinCNN}

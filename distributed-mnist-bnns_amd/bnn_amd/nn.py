@@ -4,8 +4,8 @@ Names, constructor signatures and side effects follow the reference:
 
 * ``Binarize(tensor, quant_mode='det')``                   -- :11-15
 * ``HingeLoss``                                            -- :20-32
-* ``SqrtHingeLossFunction`` (stub: the reference's is a pre-0.4 autograd Function with a
-  ``pdb.set_trace()`` in backward, :34-54)
+* ``SqrtHingeLossFunction`` (a working static autograd Function; the reference's is a pre-0.4 one with
+  a ``pdb.set_trace()`` in backward, :34-54) and ``SqrtHingeLoss``, the same loss as a criterion module
 * ``Quantize(tensor, quant_mode='det', params=None, numBits=8)`` -- :56-63
 * ``BinarizeLinear(*kargs, **kwargs)`` (an ``nn.Linear``)   -- :68-85
 * ``BinarizeConv2d(*kargs, **kwargs)`` (an ``nn.Conv2d``)   -- :87-107
@@ -38,7 +38,7 @@ import torch.nn as nn
 
 from . import functional as BF
 
-__all__ = ["Binarize", "HingeLoss", "SqrtHingeLossFunction", "Quantize", "BinarizeLinear", "BatchNorm1d",
+__all__ = ["Binarize", "HingeLoss", "SqrtHingeLoss", "SqrtHingeLossFunction", "Quantize", "BinarizeLinear", "BatchNorm1d",
            "BinarizeConv2d", "CrossEntropyLoss"]
 
 
@@ -57,20 +57,56 @@ def Binarize(tensor, quant_mode="det"):
     return prob.round().mul_(2.0).sub_(1.0)
 
 
+def _one_vs_all(input, target):
+    """int64 class indices [M] against [M, C] logits as the +-1 one-vs-all target of input's shape; every
+    other target (any dtype or shape ``input * target`` takes, as the reference's input.mul(target)) as it is."""
+    if not (target.dtype == torch.int64 and target.dim() == 1 and input.dim() == 2
+            and target.shape[0] == input.shape[0]):
+        return target
+    cols = torch.arange(input.shape[1], device=input.device)
+    return torch.where(target.unsqueeze(1) == cols, 1.0, -1.0).to(input.dtype)
+
+
 class HingeLoss(nn.Module):
-    """mean(max(0, margin - input*target)), margin = 1 (reference :20-32)."""
+    """mean(max(0, margin - input*target)), margin = 1 (reference :20-32).  ``target`` is the dense +-1
+    target the reference takes, or int64 class indices [M] (against [M, C] logits) standing for their
+    one-vs-all target.  CUDA fp32 [M, C] logits with C in {2, 10, 16, 32, 64} against such labels or a
+    dense fp32 target run on libbnn (functional.hinge_loss: one launch forward up to 16384 rows, two
+    beyond, one backward, no host synchronisation); every other input and target -- any dtype or shape
+    ``input * target`` takes, an int64 dense target included -- keeps the torch ops unchanged."""
 
     def __init__(self):
         super().__init__()
         self.margin = 1.0
 
     def hinge_loss(self, input, target):
+        if BF.hinge_loss_ok(input, target):
+            return BF.hinge_loss(input, target, self.margin)
         # output[output.le(0)] = 0 (:27-29): relu zeroes the gradient where margin - x*t <= 0,
         # ties included, and keeps NaN, as the masked assignment does
-        return torch.relu(self.margin - input * target).mean()
+        return torch.relu(self.margin - input * _one_vs_all(input, target)).mean()
 
     def forward(self, input, target):
         return self.hinge_loss(input, target)
+
+
+def _sqrt_hinge(input, target, margin):
+    if BF.hinge_loss_ok(input, target):
+        return BF.hinge_loss(input, target, margin, squared=True)
+    return torch.relu(margin - input * _one_vs_all(input, target)).pow(2).mean()
+
+
+class SqrtHingeLoss(nn.Module):
+    """mean(max(0, margin - input*target)^2), margin = 1: the squared hinge of BinaryNet-style training,
+    what the reference's SqrtHingeLossFunction (:34-54) computes, as a criterion module.  Targets and
+    routing as HingeLoss (libbnn when functional.hinge_loss_ok holds, the torch ops otherwise)."""
+
+    def __init__(self):
+        super().__init__()
+        self.margin = 1.0
+
+    def forward(self, input, target):
+        return _sqrt_hinge(input, target, self.margin)
 
 
 class CrossEntropyLoss(nn.CrossEntropyLoss):
@@ -88,14 +124,29 @@ class CrossEntropyLoss(nn.CrossEntropyLoss):
         return super().forward(input, target)
 
 
+_REF_MARGIN = 1.0     # SqrtHingeLossFunction's margin (:37): forward and backward use this one constant
+
+
 class SqrtHingeLossFunction(torch.autograd.Function):
-    """Exported for import compatibility only.  The reference version (:34-54) is a legacy
-    non-static autograd.Function that drops into pdb in backward; no reference script uses it."""
+    """The reference's squared hinge (:34-54) as a static autograd.Function: ``apply(input, target)``
+    returns mean(max(0, 1 - input*target)^2), SqrtHingeLoss's scalar at the reference's margin of 1.
+    The reference version is a pre-0.4 non-static Function that drops into pdb in backward; this one keeps
+    its backward formula (:46-54), -2 * target * output * (output != 0) / numel times the incoming
+    gradient, and gives the target no gradient."""
 
     @staticmethod
     def forward(ctx, input, target):
-        raise NotImplementedError("SqrtHingeLossFunction is not part of the BNN hot path "
-                                  "(the reference implementation is non-functional)")
+        ctx.save_for_backward(input, target)
+        return _sqrt_hinge(input, target, _REF_MARGIN)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, target = ctx.saved_tensors
+        if BF.hinge_loss_ok(input, target):
+            return BF.hinge_loss_backward(input, target, grad_output, _REF_MARGIN, True), None
+        t = _one_vs_all(input, target)
+        output = torch.relu(_REF_MARGIN - input * t)
+        return (-2.0 * t * output * (output != 0)) / input.numel() * grad_output, None
 
 
 def Quantize(tensor, quant_mode="det", params=None, numBits=8):

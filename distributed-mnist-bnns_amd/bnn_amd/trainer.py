@@ -26,6 +26,7 @@ import torch.multiprocessing as mp
 
 from . import functional as BF
 from . import nets
+from . import nn as BNN
 from .checkpoint import load_checkpoint, save_checkpoint
 from .graph import GraphedStep
 from .data import load_idx_dataset, shard_indices, synthetic_mnist
@@ -75,6 +76,9 @@ def parse(argv=None):
                     "seeds and Adam as --graph draws them: an eager twin of a --graph run)")
     ap.add_argument("--stochastic", action="store_true", help="stochastic activation binarization in training "
                     "(Binarize(t, 'stoch') on the hidden layers' inputs; eval and --eval stay deterministic)")
+    ap.add_argument("--loss", default="ce", choices=("ce", "hinge", "sqhinge"), help="the criterion: ce = "
+                    "CrossEntropyLoss on the LogSoftmax output (mnist-dist2.py:118-137); hinge / sqhinge = the mean "
+                    "(squared) hinge of models/binarized_modules.py on the logits, one-vs-all +-1 targets")
     ap.add_argument("--csv-prefix", default=None, help="write <prefix>_BATCH_TIME.csv / _EPOCH_TIME.csv")
     ap.add_argument("--checkpoint", default=None, help="write a latent-weight checkpoint here after every epoch")
     ap.add_argument("--resume", default=None, help="resume from a checkpoint written by --checkpoint")
@@ -113,14 +117,18 @@ def train(gpu, args):
         else:
             dist.init_process_group(args.backend, init_method="env://", world_size=world, rank=rank)
     torch.cuda.manual_seed(args.seed)
+    kw = {} if args.loss == "ce" else {"log_softmax": False}      # the hinge criteria take the logits
     model = nets.MODELS[args.model](org_protocol=False, mutate_input=False,
-                                    fused_bn=True, stochastic=args.stochastic).to(device)
+                                    fused_bn=True, stochastic=args.stochastic, **kw).to(device)
     exchange = GradExchange(model) if world > 1 else None
     if args.graph and world > 1:
         raise SystemExit("--graph runs one process (the gradient exchange is not captured)")
     dstep = BF.DeviceStep(device).activate() if (args.graph or args.device_step) else None
     opt = LatentAdam(model.parameters(), lr=args.lr, clamp_params=nets.binary_params(model), device_step=dstep)
-    crit = torch.nn.CrossEntropyLoss()
+    if args.loss == "ce":
+        crit = torch.nn.CrossEntropyLoss()
+    else:
+        crit = BNN.HingeLoss() if args.loss == "hinge" else BNN.SqrtHingeLoss()     # on the int64 labels
     first_epoch = 1
     if args.resume:
         first_epoch = load_checkpoint(args.resume, model, opt, map_location=device) + 1

@@ -204,6 +204,133 @@ __global__ __launch_bounds__(CE_T) void ce_bwd_k(const float* __restrict__ p, co
   dp[e] = yi == ignore ? 0.f : g * (expf(p[e] - lse[i]) - (j == yi ? 1.f : 0.f));
 }
 
+// ----------------------------------------------------------------------------- hinge / squared hinge
+// HingeLoss and SqrtHingeLossFunction of models/binarized_modules.py:20-54 on the classifier's logits:
+// the mean over all M * C elements of h (or h * h), h = max(0, margin - x * t), with t a dense fp32
+// target (DENSE) or the +-1 one-vs-all target of an int64 label, formed here (a label is only compared
+// with j; one outside [0, C) makes t, and so the loss and the row's gradient, NaN).  No expf / logf,
+// nothing kept for the backward: it recomputes v from the inputs.
+
+// v = fl(margin - fl(x * t)): torch's margin - input * target, two roundings.  Contraction is switched
+// off for the expression: __fmul_rn / __fsub_rn are plain operators in HIP's headers, which the compiler
+// contracts into one fma once they are inlined (seen with a non-+-1 target, where x * t is inexact)
+__device__ __forceinline__ float hinge_v(float x, float t, float margin) {
+#pragma clang fp contract(off)
+  const float p = x * t;
+  return margin - p;
+}
+
+// the label form's target of column j (the reference's +-1 one-vs-all row)
+__device__ __forceinline__ float hinge_label_t(int64_t yi, int j, int C) {
+  return (yi < 0 || yi >= C) ? __builtin_nanf("") : (j == yi ? 1.f : -1.f);
+}
+
+// one row's terms summed in column order (double); output[output.le(0)] = 0 (:27-29): a tie gives 0,
+// NaN stays NaN
+template <int C, bool DENSE>
+__device__ __forceinline__ double hinge_row(const float* __restrict__ x, const int64_t* __restrict__ y,
+                                            const float* __restrict__ tg, int64_t i, float margin, int squared) {
+  float xv[C], tv[C];
+#pragma unroll
+  for (int j = 0; j < C; ++j) xv[j] = x[i * C + j];
+  if constexpr (DENSE) {
+#pragma unroll
+    for (int j = 0; j < C; ++j) tv[j] = tg[i * C + j];
+  } else {
+    const int64_t yi = y[i];
+#pragma unroll
+    for (int j = 0; j < C; ++j) tv[j] = hinge_label_t(yi, j, C);
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < C; ++j) {
+    const float v = hinge_v(xv[j], tv[j], margin);
+    const float h = (v <= 0.f) ? 0.f : v;
+    s += (double)(squared ? h * h : h);      // fl(h * h), widened before the add
+  }
+  return s;
+}
+
+// a workgroup's sum in thread order: a fixed shuffle tree per wave, then the waves in order (thread 0
+// returns the sum)
+template <int T>
+__device__ __forceinline__ double hinge_block_sum(double l) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) l += __shfl_xor(l, o, 64);
+  __shared__ double ws[T / 64];
+  if ((t & 63) == 0) ws[t >> 6] = l;
+  __syncthreads();
+  double s = 0.0;
+  if (t == 0) {
+#pragma unroll
+    for (int w = 0; w < T / 64; ++w) s += ws[w];
+  }
+  return s;
+}
+
+template <int C, bool DENSE>
+__global__ __launch_bounds__(CE_T) void hinge_fwd_k(const float* __restrict__ x, const int64_t* __restrict__ y,
+                                                   const float* __restrict__ tg, int64_t M, float margin,
+                                                   int squared, double* __restrict__ part) {
+  const int64_t i = (int64_t)blockIdx.x * CE_T + threadIdx.x;
+  const double l = i < M ? hinge_row<C, DENSE>(x, y, tg, i, margin, squared) : 0.0;
+  const double s = hinge_block_sum<CE_T>(l);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(CE_T) void hinge_fold_k(const double* __restrict__ part, int64_t nb, double count,
+                                                    float* __restrict__ loss) {
+  // one workgroup: thread t sums blocks t, t + 256, ... in order, then the fixed tree over threads
+  double s = 0.0;
+  for (int64_t b = threadIdx.x; b < nb; b += CE_T) s += part[b];
+  s = hinge_block_sum<CE_T>(s);
+  if (threadIdx.x == 0) loss[0] = (float)(s / count);
+}
+
+// small batches (M <= CE_ONE_MAX): the whole forward in ONE workgroup of 1024 threads, thread t taking
+// rows t, t + 1024, ... in order -- no second (fold) launch
+template <int C, bool DENSE>
+__global__ __launch_bounds__(CE_T1) void hinge_fwd1_k(const float* __restrict__ x, const int64_t* __restrict__ y,
+                                                     const float* __restrict__ tg, int64_t M, float margin,
+                                                     int squared, double count, float* __restrict__ loss) {
+  const int t = threadIdx.x;
+  double l = 0.0;
+  // U rows per trip, read unconditionally (clamped) so their loads are all in flight together; added
+  // in the same row order as one at a time
+  constexpr int U = C <= 16 ? 4 : 1;
+  for (int64_t i0 = t; i0 < M; i0 += U * CE_T1) {
+    double a[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      a[u] = hinge_row<C, DENSE>(x, y, tg, min(i0 + (int64_t)u * CE_T1, M - 1), margin, squared);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i0 + (int64_t)u * CE_T1 < M) l += a[u];
+  }
+  const double s = hinge_block_sum<CE_T1>(l);
+  if (t == 0) loss[0] = (float)(s / count);
+}
+
+// one thread per element (row-major, coalesced loads and stores), v recomputed from the inputs
+template <int C, bool DENSE>
+__global__ __launch_bounds__(CE_T) void hinge_bwd_k(const float* __restrict__ x, const int64_t* __restrict__ y,
+                                                   const float* __restrict__ tg, const float* __restrict__ go,
+                                                   int64_t M, float margin, int squared, float* __restrict__ dx) {
+  const int64_t e = (int64_t)blockIdx.x * CE_T + threadIdx.x;
+  if (e >= M * C) return;
+  const int64_t i = e / C;
+  const int j = (int)(e - i * C);
+  // products only, each rounded to fp32 (nothing to contract); the division is IEEE (hipcc's default)
+  const float g = go[0] / (float)(M * C);
+  float t;
+  if constexpr (DENSE) t = tg[e];
+  else t = hinge_label_t(y[i], j, C);
+  const float v = hinge_v(x[e], t, margin);
+  const float d = squared ? ((-2.f * t) * v) * g : -t * g;
+  dx[e] = (v <= 0.f) ? 0.f : d;
+}
+
 }  // namespace
 }  // namespace bnn
 
@@ -265,4 +392,57 @@ BNN_API int bnn_cross_entropy_bwd(const float* p, const int64_t* y, int64_t M, i
   BNN_CE_SWITCH((int)C, hipLaunchKernelGGL((ce_bwd_k<CV>), dim3((unsigned)((M * CV + CE_T - 1) / CE_T)), dim3(CE_T), 0, s,
                                             p, y, lse, cnt, go, M, ignore_index, dp));
   return check_launch("bnn_cross_entropy_bwd");
+}
+
+// ----------------------------------------------------------------------------- hinge entries
+BNN_API int bnn_hinge_ok(int64_t C) { return bnn_cross_entropy_ok(C); }
+
+// workspace: one double per 256-row block (the block + fold path's partial sums)
+BNN_API int64_t bnn_hinge_workspace(int64_t M, int64_t C) {
+  if (M <= 0 || !bnn_hinge_ok(C)) return 0;
+  return ((M + CE_T - 1) / CE_T) * (int64_t)sizeof(double);
+}
+
+static bool hinge_args_ok(const float* x, const int64_t* y, const float* t, int64_t M, int64_t C, int32_t squared) {
+  return M > 0 && x && ((y != nullptr) != (t != nullptr)) && bnn_hinge_ok(C) && (squared == 0 || squared == 1);
+}
+
+#define BNN_HINGE_LAUNCH(KERNEL, GRID, BLOCK, ...)                                                          \
+  if (t != nullptr) {                                                                                       \
+    BNN_CE_SWITCH((int)C, hipLaunchKernelGGL((KERNEL<CV, true>), dim3(GRID), dim3(BLOCK), 0, s, __VA_ARGS__)); \
+  } else {                                                                                                  \
+    BNN_CE_SWITCH((int)C, hipLaunchKernelGGL((KERNEL<CV, false>), dim3(GRID), dim3(BLOCK), 0, s, __VA_ARGS__)); \
+  }
+
+BNN_API int bnn_hinge_fwd(const float* x, const int64_t* y, const float* t, int64_t M, int64_t C, float margin,
+                          int32_t squared, float* loss, void* work, int64_t work_bytes, void* stream) {
+  if (!hinge_args_ok(x, y, t, M, C, squared) || !loss || !work || work_bytes < bnn_hinge_workspace(M, C)) {
+    set_error("bnn_hinge_fwd: bad arguments (M=%lld C=%lld squared=%d work=%lld; M > 0, C in {2,10,16,32,64}, "
+              "exactly one of y / t, squared 0 or 1, workspace bnn_hinge_workspace(M, C))", (long long)M,
+              (long long)C, (int)squared, (long long)work_bytes);
+    return kErrInval;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const double count = (double)(M * C);
+  if (M <= CE_ONE_MAX) {
+    BNN_HINGE_LAUNCH(hinge_fwd1_k, 1, CE_T1, x, y, t, M, margin, (int)squared, count, loss);
+    return check_launch("bnn_hinge_fwd");
+  }
+  double* part = reinterpret_cast<double*>(work);
+  const int64_t nb = (M + CE_T - 1) / CE_T;
+  BNN_HINGE_LAUNCH(hinge_fwd_k, (unsigned)nb, CE_T, x, y, t, M, margin, (int)squared, part);
+  hipLaunchKernelGGL(hinge_fold_k, dim3(1), dim3(CE_T), 0, s, part, nb, count, loss);
+  return check_launch("bnn_hinge_fwd");
+}
+
+BNN_API int bnn_hinge_bwd(const float* x, const int64_t* y, const float* t, int64_t M, int64_t C, float margin,
+                          int32_t squared, const float* go, float* dx, void* stream) {
+  if (!hinge_args_ok(x, y, t, M, C, squared) || !go || !dx) {
+    set_error("bnn_hinge_bwd: bad arguments (M=%lld C=%lld squared=%d; M > 0, C in {2,10,16,32,64}, exactly one "
+              "of y / t, squared 0 or 1)", (long long)M, (long long)C, (int)squared);
+    return kErrInval;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  BNN_HINGE_LAUNCH(hinge_bwd_k, (unsigned)((M * C + CE_T - 1) / CE_T), CE_T, x, y, t, go, M, margin, (int)squared, dx);
+  return check_launch("bnn_hinge_bwd");
 }

@@ -18,7 +18,7 @@ if _PKG_ROOT not in sys.path:
     sys.path.insert(0, _PKG_ROOT)
 
 from bnn_amd.nn import (Binarize, BinarizeConv2d, BinarizeLinear, HingeLoss,  # noqa: E402,F401
-                        Quantize, SqrtHingeLossFunction)
+                        Quantize, SqrtHingeLoss, SqrtHingeLossFunction)
 
-__all__ = ["Binarize", "HingeLoss", "SqrtHingeLossFunction", "Quantize", "BinarizeLinear",
+__all__ = ["Binarize", "HingeLoss", "SqrtHingeLoss", "SqrtHingeLossFunction", "Quantize", "BinarizeLinear",
            "BinarizeConv2d"]

@@ -776,6 +776,25 @@ int bnn_cross_entropy_fwd(const float* p, const int64_t* y, int64_t M, int64_t C
 int bnn_cross_entropy_bwd(const float* p, const int64_t* y, int64_t M, int64_t C, int64_t ignore_index,
                           const float* go, const void* work, float* dp, bnn_stream_t stream);
 
+/* The hinge criteria of models/binarized_modules.py:20-54 (HingeLoss, SqrtHingeLossFunction) on the
+ * classifier's logits x [M][C] fp32 (C as bnn_cross_entropy_ok): loss = mean over the M*C elements of
+ * h (squared = 0) or h*h (squared = 1), h = max(0, margin - x*t), a tie (margin - x*t == 0) counting as
+ * 0 and NaN staying NaN.  Exactly one target is non-null: y [M] int64 class indices -- t = +1 where
+ * j == y[i], else -1, formed in the kernel (a label is only compared, never an address; one outside
+ * [0, C) makes the loss and that row's gradient NaN) -- or t [M][C] fp32 of any values (the
+ * reference's input.mul(target)).  v = fl(margin - fl(x*t)) without contraction (torch's
+ * margin - input * target); the fp32 terms summed in double in a fixed order (deterministic; M <= 16384:
+ * one workgroup, one launch), loss[0] = fl(S / (M*C)) on the device.  bwd recomputes v and writes
+ * dx = (v <= 0) ? 0 : fl(-t*g) (hinge) or fl(fl(fl(-2*t)*v)*g) (squared), g = fl(go[0] / fl(M*C)) with
+ * go read on the device; nothing is kept from fwd (work, bnn_hinge_workspace(M, C) bytes, holds
+ * fwd's block sums only). */
+int bnn_hinge_ok(int64_t C);
+int64_t bnn_hinge_workspace(int64_t M, int64_t C);
+int bnn_hinge_fwd(const float* x, const int64_t* y, const float* t, int64_t M, int64_t C, float margin,
+                  int32_t squared, float* loss, void* work, int64_t work_bytes, bnn_stream_t stream);
+int bnn_hinge_bwd(const float* x, const int64_t* y, const float* t, int64_t M, int64_t C, float margin,
+                  int32_t squared, const float* go, float* dx, bnn_stream_t stream);
+
 /* ---------------------------------------------------------------- (3) STE backward helpers
  * Hardtanh backward: g_out = g_in * (-1 < x < 1) (strict), as nn.Hardtanh (mnist-dist2.py:51). */
 int bnn_hardtanh_bwd(const float* x, const float* g, float* out, int64_t n, bnn_stream_t stream);
