@@ -1441,12 +1441,23 @@ def _zq_fmt(x, binarize_input, stride, dilation, groups, C, KH, KW, H, W, pad, N
     return fmt
 
 
+def conv_out_hw(H, W, KH, KW, stride, padding, dilation):
+    """(OH, OW) of a convolution.  Raises ValueError when the dilated kernel is larger than the
+    padded input in either dimension (torch refuses the same shapes; the library's make_shape too)."""
+    eh, ew = dilation * (KH - 1) + 1, dilation * (KW - 1) + 1
+    if eh > H + 2 * padding or ew > W + 2 * padding:
+        raise ValueError(f"conv2d: dilated kernel ({eh} x {ew}) can't be greater than the padded input "
+                         f"({H + 2 * padding} x {W + 2 * padding})")
+    return (H + 2 * padding - eh) // stride + 1, (W + 2 * padding - ew) // stride + 1
+
+
 class BinaryConv2dFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, binarize_input, stride, padding, dilation, groups, emit_compact=False,
                 stochastic=None):
         global ZQ_HANDOFFS
         _check(x, weight, bias)
+        OH, OW = conv_out_hw(x.shape[2], x.shape[3], weight.shape[2], weight.shape[3], stride, padding, dilation)
         _conv_env()
         x = _c2d(x)
         if stochastic is not None and binarize_input:
@@ -1456,8 +1467,6 @@ class BinaryConv2dFunction(torch.autograd.Function):
         w = _c2d(weight.detach())
         N, C, H, W = x.shape
         Co, _, KH, KW = w.shape
-        OH = (H + 2 * padding - dilation * (KH - 1) - 1) // stride + 1
-        OW = (W + 2 * padding - dilation * (KW - 1) - 1) // stride + 1
         b = bias.detach() if bias is not None else None
         ctx.empty = N == 0
         zf = _zq_fmt(x, binarize_input, stride, dilation, groups, C, KH, KW, H, W, padding, N, Co) if emit_compact else 0

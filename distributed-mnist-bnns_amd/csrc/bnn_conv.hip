@@ -164,9 +164,12 @@ bool make_shape(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t 
   if (N < 0 || C <= 0 || H <= 0 || W <= 0 || Co <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 ||
       dil <= 0 || groups <= 0 || C % groups != 0 || Co % groups != 0)
     return false;
-  const int64_t oh = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  const int64_t ow = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  if (oh <= 0 || ow <= 0) return false;
+  // a dilated kernel larger than the padded input has no output (refused before the division: C's
+  // truncation would turn (-1) / 2 + 1 into one output row that reads and writes out of bounds)
+  const int64_t eh = dil * (KH - 1) + 1, ew = dil * (KW - 1) + 1;
+  if (eh > H + 2 * pad || ew > W + 2 * pad) return false;
+  const int64_t oh = (H + 2 * pad - eh) / stride + 1;
+  const int64_t ow = (W + 2 * pad - ew) / stride + 1;
   *s = ConvShape{N, C, H, W, Co, KH, KW, oh, ow, stride, pad, dil, groups};
   return true;
 }
@@ -1924,6 +1927,317 @@ BNN_API int bnn_conv_set_mfma(int32_t mode) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dispatch.  Each op has one table of the kernel instances it can launch -- (engine family, the two
+// template arguments that select the instance, the kernel) -- and one decision function that maps a
+// shape and the process-global switches to a (family, p0, p1) key plus the engine's geometry.  The
+// launching entry expands the table into its launch chain and bnn_conv_kernel / bnn_conv_kernel_at
+// expand it into names, so the query cannot disagree with the launch and a new table row is
+// launched, named and listed at once.  The rows keep the order the instances were first used in.
+#define BNN_CONV_FWD_INSTANCES(X) \
+  X(I8, 1, 0, conv_fwd_i8mfma_k<1>) \
+  X(I8, 2, 0, conv_fwd_i8mfma_k<2>) \
+  X(I8, 4, 0, conv_fwd_i8mfma_k<4>) \
+  X(C1, 8, 1, conv_fwd_bin_c1_k<8,1>) \
+  X(C1, 8, 2, conv_fwd_bin_c1_k<8,2>) \
+  X(C1, 16, 1, conv_fwd_bin_c1_k<16,1>) \
+  X(C1, 16, 2, conv_fwd_bin_c1_k<16,2>) \
+  X(C1, 32, 1, conv_fwd_bin_c1_k<32,1>) \
+  X(C1, 32, 2, conv_fwd_bin_c1_k<32,2>) \
+  X(C1, 64, 1, conv_fwd_bin_c1_k<64,1>) \
+  X(C1, 64, 2, conv_fwd_bin_c1_k<64,2>) \
+  X(BIN, 8, 0, conv_fwd_bin_tile_k<8>) \
+  X(BIN, 16, 0, conv_fwd_bin_tile_k<16>) \
+  X(BIN, 32, 0, conv_fwd_bin_tile_k<32>) \
+  X(BIN, 64, 0, conv_fwd_bin_tile_k<64>) \
+  X(F32, 8, 0, conv_fwd_f32_tile_k<8>) \
+  X(F32, 16, 0, conv_fwd_f32_tile_k<16>) \
+  X(F32, 32, 0, conv_fwd_f32_tile_k<32>) \
+  X(F32, 64, 0, conv_fwd_f32_tile_k<64>) \
+  X(GEN, 0, 0, conv_fwd_k)
+
+#define BNN_CONV_DATA_INSTANCES(X) \
+  X(B3, 1, 1, conv_bwd_data_bf3_k<1,1>) \
+  X(B3, 1, 2, conv_bwd_data_bf3_k<1,2>) \
+  X(B3, 1, 4, conv_bwd_data_bf3_k<1,4>) \
+  X(B3, 1, 8, conv_bwd_data_bf3_k<1,8>) \
+  X(B3, 1, 16, conv_bwd_data_bf3_k<1,16>) \
+  X(B3, 2, 1, conv_bwd_data_bf3_k<2,1>) \
+  X(B3, 2, 2, conv_bwd_data_bf3_k<2,2>) \
+  X(B3, 2, 4, conv_bwd_data_bf3_k<2,4>) \
+  X(B3, 2, 8, conv_bwd_data_bf3_k<2,8>) \
+  X(B3, 2, 16, conv_bwd_data_bf3_k<2,16>) \
+  X(MF, 1, 1, conv_bwd_data_mfma_k<1,1>) \
+  X(MF, 1, 2, conv_bwd_data_mfma_k<1,2>) \
+  X(MF, 1, 4, conv_bwd_data_mfma_k<1,4>) \
+  X(MF, 1, 8, conv_bwd_data_mfma_k<1,8>) \
+  X(MF, 1, 13, conv_bwd_data_mfma_k<1,13>) \
+  X(MF, 1, 16, conv_bwd_data_mfma_k<1,16>) \
+  X(MF, 2, 1, conv_bwd_data_mfma_k<2,1>) \
+  X(MF, 2, 2, conv_bwd_data_mfma_k<2,2>) \
+  X(MF, 2, 4, conv_bwd_data_mfma_k<2,4>) \
+  X(MF, 2, 8, conv_bwd_data_mfma_k<2,8>) \
+  X(MF, 2, 16, conv_bwd_data_mfma_k<2,16>) \
+  X(TILE, 8, 0, conv_bwd_data_tile_k<8>) \
+  X(TILE, 16, 0, conv_bwd_data_tile_k<16>) \
+  X(TILE, 32, 0, conv_bwd_data_tile_k<32>) \
+  X(TILE, 64, 0, conv_bwd_data_tile_k<64>) \
+  X(GEN, 0, 0, conv_bwd_data_k)
+
+#define BNN_CONV_FILT_INSTANCES(X) \
+  X(C1, 5, 5, conv_bwd_filter_c1_k<5,5>) \
+  X(C1, 3, 3, conv_bwd_filter_c1_k<3,3>) \
+  X(B3, 1, 1, conv_bwd_filter_bf3_k<1,1>) \
+  X(B3, 1, 2, conv_bwd_filter_bf3_k<1,2>) \
+  X(B3, 1, 4, conv_bwd_filter_bf3_k<1,4>) \
+  X(B3, 1, 8, conv_bwd_filter_bf3_k<1,8>) \
+  X(B3, 2, 1, conv_bwd_filter_bf3_k<2,1>) \
+  X(B3, 2, 2, conv_bwd_filter_bf3_k<2,2>) \
+  X(B3, 2, 4, conv_bwd_filter_bf3_k<2,4>) \
+  X(B3, 2, 8, conv_bwd_filter_bf3_k<2,8>) \
+  X(B3, 3, 1, conv_bwd_filter_bf3_k<3,1>) \
+  X(B3, 3, 2, conv_bwd_filter_bf3_k<3,2>) \
+  X(B3, 3, 4, conv_bwd_filter_bf3_k<3,4>) \
+  X(B3, 3, 8, conv_bwd_filter_bf3_k<3,8>) \
+  X(B3, 4, 1, conv_bwd_filter_bf3_k<4,1>) \
+  X(B3, 4, 2, conv_bwd_filter_bf3_k<4,2>) \
+  X(B3, 4, 4, conv_bwd_filter_bf3_k<4,4>) \
+  X(B3, 4, 8, conv_bwd_filter_bf3_k<4,8>) \
+  X(MF, 1, 0, conv_bwd_filter_mfma_k<1>) \
+  X(MF, 2, 0, conv_bwd_filter_mfma_k<2>) \
+  X(MF, 4, 0, conv_bwd_filter_mfma_k<4>) \
+  X(MF, 8, 0, conv_bwd_filter_mfma_k<8>) \
+  X(MF, 13, 0, conv_bwd_filter_mfma_k<13>) \
+  X(MF, 16, 0, conv_bwd_filter_mfma_k<16>) \
+  X(TILE, 8, 0, conv_bwd_filter_tile_k<8>) \
+  X(TILE, 16, 0, conv_bwd_filter_tile_k<16>) \
+  X(TILE, 32, 0, conv_bwd_filter_tile_k<32>) \
+  X(TILE, 64, 0, conv_bwd_filter_tile_k<64>) \
+  X(GEN, 0, 0, conv_bwd_filter_k)
+
+// kFamNone: nothing to convolve (an empty batch); kFamPopc: the popcount engine (bnn_conv_popc.hip,
+// which picks among its own kernels)
+enum ConvFam {
+  kFamNone, kFamPopc,
+  kFwdI8, kFwdC1, kFwdBIN, kFwdF32, kFwdGEN,
+  kDataB3, kDataMF, kDataTILE, kDataGEN,
+  kFiltC1, kFiltB3, kFiltMF, kFiltTILE, kFiltGEN,
+};
+
+struct FwdPick {
+  int fam = kFamNone, p0 = 0, p1 = 0;
+  int64_t lds = 0;
+  MfFwd mf;
+};
+struct DataPick {
+  int fam = kFamNone, p0 = 0, p1 = 0, ipb = 0;
+  int64_t lds = 0;
+  B3Data bd;
+  MfData md;
+};
+struct FiltPick {
+  int fam = kFamNone, p0 = 0, p1 = 0, ipb = 0;
+  int64_t lds = 0, nblk = 0, parts = 0;   // workgroups; float partials [parts][rco * rcombo + rco]
+  int rco = 0, rcombo = 0;
+  C1Filt cf;
+  B3Filt bf;
+  MfFilt mf;
+};
+
+// tiles per wave -> the kernels' MT template argument (the smallest instantiated value that holds it)
+static int mt_of(int per_wave, bool has13, int top) {
+  if (per_wave <= 1) return 1;
+  if (per_wave <= 2) return 2;
+  if (per_wave <= 4) return 4;
+  if (per_wave <= 8) return 8;
+  if (has13 && per_wave <= 13) return 13;
+  return top;
+}
+
+static FwdPick fwd_pick(const ConvShape& s, int binarize) {
+  FwdPick p;
+  if (s.N * s.Co * s.OH * s.OW == 0) return p;
+  if (popc_pick(s, binarize)) {
+    p.fam = kFamPopc;
+    return p;
+  }
+  if (binarize && g_conv_mfma && mf_fwd_geom(s, &p.mf, &p.lds)) {
+    const int cot = (p.mf.Co + 15) / 16;
+    p.fam = kFwdI8;
+    p.p0 = cot <= 2 ? cot : 4;
+    return p;
+  }
+  if (binarize && g_conv_mfma && s.C == 1 && s.KW <= 8 && tile_geom_ok(s)) {
+    const TileGeo g = geo(s);
+    const int Wq = (int)round_up(g.Wp, 4);
+    p.fam = kFwdC1;
+    p.p0 = pick_co(s.Co);
+    p.p1 = s.KW <= 4 ? 1 : 2;
+    p.lds = s.KH * p.p1 * p.p0 * 4 + g.Hp * Wq + 16;
+    return p;
+  }
+  if (tile_geom_ok(s) && fwd_tile_lds(s, binarize != 0) <= kMaxTileLds) {
+    p.fam = binarize ? kFwdBIN : kFwdF32;
+    p.p0 = pick_co(s.Co);
+    p.lds = fwd_tile_lds(s, binarize != 0);
+    return p;
+  }
+  p.fam = kFwdGEN;
+  p.lds = 0;
+  return p;
+}
+
+static DataPick data_pick(const ConvShape& s) {
+  DataPick p;
+  if (s.N * s.C * s.H * s.W == 0) return p;
+  if (g_conv_mfma == 1 && b3_data_geom(s, &p.bd, &p.lds)) {
+    p.fam = kDataB3;
+    p.ipb = b3_ipb(s.N);
+    p.p0 = p.bd.C <= 16 ? 1 : 2;
+    p.p1 = mt_of((p.bd.ntile_pix + B3_W - 1) / B3_W, false, 16);
+    return p;
+  }
+  if (g_conv_mfma && mf_data_geom(s, &p.md, &p.lds)) {
+    p.fam = kDataMF;
+    p.p0 = p.md.CIp == 16 ? 1 : 2;
+    p.p1 = mt_of((p.md.ntile_pix + 3) / 4, p.p0 == 1, 16);
+    return p;
+  }
+  if (tile_geom_ok(s) && bwd_data_tile_lds(s) <= kMaxTileLds) {
+    p.fam = kDataTILE;
+    p.p0 = pick_co(s.C);
+    p.lds = bwd_data_tile_lds(s);
+    return p;
+  }
+  p.fam = kDataGEN;
+  p.lds = 0;
+  return p;
+}
+
+static FiltPick filt_pick(const ConvShape& s, int binarize) {
+  FiltPick p;
+  if (s.N == 0) return p;
+  if (g_conv_c1f && g_conv_mfma != 0 && c1_filt_geom(s, &p.cf, &p.lds)) {
+    p.fam = kFiltC1;
+    p.p0 = (int)s.KH;
+    p.p1 = (int)s.KW;
+    p.nblk = p.parts = (s.N + C1F_SPB - 1) / C1F_SPB;
+    p.rco = (int)s.Co;
+    p.rcombo = (int)(s.KH * s.KW);
+    return p;
+  }
+  if (g_conv_mfma == 1 && b3_filt_geom(s, binarize, &p.bf, &p.lds)) {
+    p.fam = kFiltB3;
+    p.ipb = b3_ipb(s.N);
+    p.p0 = p.bf.NA;
+    p.p1 = mt_of((p.bf.ntn + p.bf.WT - 1) / p.bf.WT, false, 8);
+    p.nblk = (s.N + p.ipb - 1) / p.ipb;
+    p.parts = p.nblk * p.bf.KS;
+    p.rco = (int)s.Co;
+    p.rcombo = p.bf.ncombo;
+    return p;
+  }
+  if (g_conv_mfma && mf_filt_geom(s, &p.mf, &p.lds)) {
+    p.fam = kFiltMF;
+    p.p0 = mt_of((p.mf.ntiles + p.mf.WT - 1) / p.mf.WT, true, 16);
+    p.nblk = (s.N + MF_IPB - 1) / MF_IPB;
+    p.parts = p.nblk * p.mf.KS;
+    p.rco = (int)s.Co;
+    p.rcombo = p.mf.ncombo;
+    return p;
+  }
+  if (tile_geom_ok(s) && s.C * s.KH * s.KW <= 2 * TILE_T && filter_tile_lds(s) <= kMaxTileLds) {
+    p.fam = kFiltTILE;
+    p.p0 = pick_co(s.Co);
+    p.lds = filter_tile_lds(s);
+    p.nblk = (s.N + FILTER_SPB - 1) / FILTER_SPB;
+    p.parts = tile_filter_parts(s);
+    p.rco = p.p0;
+    p.rcombo = (int)(s.C * s.KH * s.KW);
+    return p;
+  }
+  p.fam = kFiltGEN;
+  p.lds = 0;
+  return p;
+}
+
+struct ConvInst {
+  int fam, p0, p1;
+  const char* name;
+};
+#define BNN_X(FAM, P0, P1, ...) {kFwd##FAM, P0, P1, #__VA_ARGS__},
+static const ConvInst kFwdInst[] = {BNN_CONV_FWD_INSTANCES(BNN_X)};
+#undef BNN_X
+#define BNN_X(FAM, P0, P1, ...) {kData##FAM, P0, P1, #__VA_ARGS__},
+static const ConvInst kDataInst[] = {BNN_CONV_DATA_INSTANCES(BNN_X)};
+#undef BNN_X
+#define BNN_X(FAM, P0, P1, ...) {kFilt##FAM, P0, P1, #__VA_ARGS__},
+static const ConvInst kFiltInst[] = {BNN_CONV_FILT_INSTANCES(BNN_X)};
+#undef BNN_X
+
+static const ConvInst* inst_table(int op, int* n) {
+  switch (op) {
+    case 0: *n = (int)(sizeof(kFwdInst) / sizeof(ConvInst)); return kFwdInst;
+    case 1: *n = (int)(sizeof(kDataInst) / sizeof(ConvInst)); return kDataInst;
+    case 2: *n = (int)(sizeof(kFiltInst) / sizeof(ConvInst)); return kFiltInst;
+    default: *n = 0; return nullptr;
+  }
+}
+
+static const char* inst_name(int op, int fam, int p0, int p1) {
+  int n = 0;
+  const ConvInst* t = inst_table(op, &n);
+  for (int i = 0; i < n; ++i)
+    if (t[i].fam == fam && t[i].p0 == p0 && t[i].p1 == p1) return t[i].name;
+  return "?";   // a decision the table has no row for: the launching entry fails with no_instance()
+}
+
+static int no_instance(const char* who) {
+  set_error("%s: the dispatch decision has no row in the kernel instance table", who);
+  return kErrInval;
+}
+
+// Host-only query (no GPU, nothing launched): the kernel instance the launching entry of `op`
+// (0 forward, 1 backward data, 2 backward filter) runs for a shape under the current switches, with
+// the run-time schedule choices that change control flow inside it appended ("rowt=", "WT=", "KS=",
+// "ipb=").  "" for arguments make_shape refuses, "none" for an empty batch (no conv kernel runs),
+// "popc" when the popcount engine takes the forward.  The string is valid until the thread's next call.
+BNN_API const char* bnn_conv_kernel(int32_t op, int32_t binarize_input, int64_t N, int64_t C, int64_t H, int64_t W,
+                                    int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad, int32_t dil,
+                                    int32_t groups) {
+  static thread_local char buf[96];
+  ConvShape s;
+  if (op < 0 || op > 2 || !make_shape(N, C, H, W, Co, KH, KW, stride, pad, dil, groups, &s)) return "";
+  if (op == 0) {
+    const FwdPick p = fwd_pick(s, binarize_input);
+    if (p.fam == kFamNone) return "none";
+    if (p.fam == kFamPopc) return "popc";
+    return inst_name(0, p.fam, p.p0, p.p1);
+  }
+  if (op == 1) {
+    const DataPick p = data_pick(s);
+    if (p.fam == kFamNone) return "none";
+    const char* name = inst_name(1, p.fam, p.p0, p.p1);
+    if (p.fam != kDataB3) return name;
+    snprintf(buf, sizeof(buf), "%s rowt=%d ipb=%d", name, p.bd.rowt, p.ipb);
+    return buf;
+  }
+  const FiltPick p = filt_pick(s, binarize_input);
+  if (p.fam == kFamNone) return "none";
+  const char* name = inst_name(2, p.fam, p.p0, p.p1);
+  if (p.fam == kFiltB3) snprintf(buf, sizeof(buf), "%s WT=%d KS=%d ipb=%d", name, p.bf.WT, p.bf.KS, p.ipb);
+  else if (p.fam == kFiltMF) snprintf(buf, sizeof(buf), "%s WT=%d KS=%d", name, p.mf.WT, p.mf.KS);
+  else return name;
+  return buf;
+}
+
+// The index-th instance `op` can launch, in table order; "" past the end (or for a bad op).
+BNN_API const char* bnn_conv_kernel_at(int32_t op, int32_t index) {
+  int n = 0;
+  const ConvInst* t = inst_table(op, &n);
+  return index >= 0 && index < n ? t[index].name : "";
+}
+
 BNN_API int bnn_conv2d_fwd(const float* x, int32_t binarize_input, const float* w_latent,
                            const float* bias, float* y, int64_t N, int64_t C, int64_t H, int64_t W,
                            int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad,
@@ -1933,61 +2247,30 @@ BNN_API int bnn_conv2d_fwd(const float* x, int32_t binarize_input, const float* 
     set_error("bnn_conv2d_fwd: bad arguments");
     return kErrInval;
   }
-  const int64_t total = N * Co * s.OH * s.OW;
-  if (total == 0) return 0;
+  const FwdPick pk = fwd_pick(s, binarize_input);
+  if (pk.fam == kFamNone) return 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (popc_pick(s, binarize_input)) return popc_run(s, x, w_latent, bias, y, 0, st, "bnn_conv2d_fwd");
-  MfFwd mf;
-  int64_t mlds = 0;
-  if (binarize_input && g_conv_mfma && mf_fwd_geom(s, &mf, &mlds)) {
-    const size_t lds = (size_t)mlds;
-    const dim3 grid((unsigned)((N + FW_IPB - 1) / FW_IPB));
-    const int cot = (mf.Co + 15) / 16;
-    if (cot == 1) BNN_TILE_LAUNCH(conv_fwd_i8mfma_k<1>, grid, dim3(MF_T), lds, st, x, w_latent, bias, y, N, mf);
-    else if (cot == 2) BNN_TILE_LAUNCH(conv_fwd_i8mfma_k<2>, grid, dim3(MF_T), lds, st, x, w_latent, bias, y, N, mf);
-    else BNN_TILE_LAUNCH(conv_fwd_i8mfma_k<4>, grid, dim3(MF_T), lds, st, x, w_latent, bias, y, N, mf);
-    return check_launch("bnn_conv2d_fwd");
-  }
-  if (binarize_input && g_conv_mfma && s.C == 1 && s.KW <= 8 && tile_geom_ok(s)) {
-    const TileGeo g = geo(s);
-    const int Wq = (int)round_up(g.Wp, 4), kwg = s.KW <= 4 ? 1 : 2;
-    const size_t lds = (size_t)(s.KH * kwg * pick_co(Co) * 4 + g.Hp * Wq + 16);
-#define BNN_C1(CO_, KG_) BNN_TILE_LAUNCH((conv_fwd_bin_c1_k<CO_, KG_>), dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g, Wq)
-    switch (pick_co(Co) * 4 + kwg) {
-      case 8 * 4 + 1: BNN_C1(8, 1); break;
-      case 8 * 4 + 2: BNN_C1(8, 2); break;
-      case 16 * 4 + 1: BNN_C1(16, 1); break;
-      case 16 * 4 + 2: BNN_C1(16, 2); break;
-      case 32 * 4 + 1: BNN_C1(32, 1); break;
-      case 32 * 4 + 2: BNN_C1(32, 2); break;
-      case 64 * 4 + 1: BNN_C1(64, 1); break;
-      default: BNN_C1(64, 2); break;
-    }
-#undef BNN_C1
-    return check_launch("bnn_conv2d_fwd");
-  }
-  if (tile_geom_ok(s) && fwd_tile_lds(s, binarize_input != 0) <= kMaxTileLds) {
-    const TileGeo g = geo(s);
-    const int CO = pick_co(Co);
-    const size_t lds = (size_t)fwd_tile_lds(s, binarize_input != 0);
-    if (binarize_input) {
-      switch (CO) {
-        case 8: BNN_TILE_LAUNCH(conv_fwd_bin_tile_k<8>, dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g); break;
-        case 16: BNN_TILE_LAUNCH(conv_fwd_bin_tile_k<16>, dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g); break;
-        case 32: BNN_TILE_LAUNCH(conv_fwd_bin_tile_k<32>, dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g); break;
-        default: BNN_TILE_LAUNCH(conv_fwd_bin_tile_k<64>, dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g); break;
-      }
-    } else {
-      switch (CO) {
-        case 8: BNN_TILE_LAUNCH(conv_fwd_f32_tile_k<8>, dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g); break;
-        case 16: BNN_TILE_LAUNCH(conv_fwd_f32_tile_k<16>, dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g); break;
-        case 32: BNN_TILE_LAUNCH(conv_fwd_f32_tile_k<32>, dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g); break;
-        default: BNN_TILE_LAUNCH(conv_fwd_f32_tile_k<64>, dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g); break;
-      }
-    }
-    return check_launch("bnn_conv2d_fwd");
-  }
-  hipLaunchKernelGGL(conv_fwd_k, dim3(grid_for(total)), dim3(256), 0, st, x, binarize_input, w_latent, bias, y, s);
+  if (pk.fam == kFamPopc) return popc_run(s, x, w_latent, bias, y, 0, st, "bnn_conv2d_fwd");
+  const int64_t total = N * Co * s.OH * s.OW;
+  const TileGeo g = geo(s);
+  const int Wq = (int)round_up(g.Wp, 4);
+  const size_t lds = (size_t)pk.lds;
+#define BNN_FWD_LAUNCH_I8(...) \
+  BNN_TILE_LAUNCH((__VA_ARGS__), dim3((unsigned)((N + FW_IPB - 1) / FW_IPB)), dim3(MF_T), lds, st, x, w_latent, bias, y, N, pk.mf)
+#define BNN_FWD_LAUNCH_C1(...) BNN_TILE_LAUNCH((__VA_ARGS__), dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g, Wq)
+#define BNN_FWD_LAUNCH_BIN(...) BNN_TILE_LAUNCH((__VA_ARGS__), dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g)
+#define BNN_FWD_LAUNCH_F32(...) BNN_TILE_LAUNCH((__VA_ARGS__), dim3(N), dim3(TILE_T), lds, st, x, w_latent, bias, y, g)
+#define BNN_FWD_LAUNCH_GEN(...) \
+  hipLaunchKernelGGL((__VA_ARGS__), dim3(grid_for(total)), dim3(256), 0, st, x, binarize_input, w_latent, bias, y, s)
+#define BNN_X(FAM, P0, P1, ...) \
+  if (pk.fam == kFwd##FAM && pk.p0 == P0 && pk.p1 == P1) BNN_FWD_LAUNCH_##FAM(__VA_ARGS__); else
+  BNN_CONV_FWD_INSTANCES(BNN_X) return no_instance("bnn_conv2d_fwd");
+#undef BNN_X
+#undef BNN_FWD_LAUNCH_I8
+#undef BNN_FWD_LAUNCH_C1
+#undef BNN_FWD_LAUNCH_BIN
+#undef BNN_FWD_LAUNCH_F32
+#undef BNN_FWD_LAUNCH_GEN
   return check_launch("bnn_conv2d_fwd");
 }
 
@@ -2088,57 +2371,28 @@ BNN_API int bnn_conv2d_bwd_data(const float* dy, const float* w_latent, float* d
     set_error("bnn_conv2d_bwd_data: bad arguments");
     return kErrInval;
   }
-  const int64_t total = N * C * H * W;
-  if (total == 0) return 0;
+  const DataPick pk = data_pick(s);
+  if (pk.fam == kFamNone) return 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  B3Data bd;
-  int64_t blds = 0;
-  if (g_conv_mfma == 1 && b3_data_geom(s, &bd, &blds)) {
-    const size_t lds = (size_t)blds;
-    const int ipb = b3_ipb(N);
-    const dim3 grid((unsigned)((N + ipb - 1) / ipb));
-    const int per_wave = (bd.ntile_pix + B3_W - 1) / B3_W;
-#define BNN_B3D(NT_, MT_) BNN_TILE_LAUNCH((conv_bwd_data_bf3_k<NT_, MT_>), grid, dim3(B3_T), lds, st, dy, w_latent, dx, N, bd, ipb)
-    if (bd.C <= 16) {
-      if (per_wave <= 1) BNN_B3D(1, 1); else if (per_wave <= 2) BNN_B3D(1, 2); else if (per_wave <= 4) BNN_B3D(1, 4);
-      else if (per_wave <= 8) BNN_B3D(1, 8); else BNN_B3D(1, 16);
-    } else {
-      if (per_wave <= 1) BNN_B3D(2, 1); else if (per_wave <= 2) BNN_B3D(2, 2); else if (per_wave <= 4) BNN_B3D(2, 4);
-      else if (per_wave <= 8) BNN_B3D(2, 8); else BNN_B3D(2, 16);
-    }
-#undef BNN_B3D
-    return check_launch("bnn_conv2d_bwd_data");
-  }
-  MfData md;
-  int64_t mlds = 0;
-  if (g_conv_mfma && mf_data_geom(s, &md, &mlds)) {
-    const size_t lds = (size_t)mlds;
-    const dim3 grid((unsigned)((N + MF_IPB - 1) / MF_IPB));
-    const int per_wave = (md.ntile_pix + 3) / 4;
-#define BNN_MFD(NT_, MT_) BNN_TILE_LAUNCH((conv_bwd_data_mfma_k<NT_, MT_>), grid, dim3(MF_T), lds, st, dy, w_latent, dx, N, md)
-    if (md.CIp == 16) {
-      if (per_wave <= 1) BNN_MFD(1, 1); else if (per_wave <= 2) BNN_MFD(1, 2); else if (per_wave <= 4) BNN_MFD(1, 4);
-      else if (per_wave <= 8) BNN_MFD(1, 8); else if (per_wave <= 13) BNN_MFD(1, 13); else BNN_MFD(1, 16);
-    } else {
-      if (per_wave <= 1) BNN_MFD(2, 1); else if (per_wave <= 2) BNN_MFD(2, 2); else if (per_wave <= 4) BNN_MFD(2, 4);
-      else if (per_wave <= 8) BNN_MFD(2, 8); else BNN_MFD(2, 16);
-    }
-#undef BNN_MFD
-    return check_launch("bnn_conv2d_bwd_data");
-  }
-  if (tile_geom_ok(s) && bwd_data_tile_lds(s) <= kMaxTileLds) {
-    const TileGeo g = geo(s);
-    const int CI = pick_co(C);
-    const size_t lds = (size_t)bwd_data_tile_lds(s);
-    switch (CI) {
-      case 8: BNN_TILE_LAUNCH(conv_bwd_data_tile_k<8>, dim3(N), dim3(TILE_T), lds, st, dy, w_latent, dx, g); break;
-      case 16: BNN_TILE_LAUNCH(conv_bwd_data_tile_k<16>, dim3(N), dim3(TILE_T), lds, st, dy, w_latent, dx, g); break;
-      case 32: BNN_TILE_LAUNCH(conv_bwd_data_tile_k<32>, dim3(N), dim3(TILE_T), lds, st, dy, w_latent, dx, g); break;
-      default: BNN_TILE_LAUNCH(conv_bwd_data_tile_k<64>, dim3(N), dim3(TILE_T), lds, st, dy, w_latent, dx, g); break;
-    }
-    return check_launch("bnn_conv2d_bwd_data");
-  }
-  hipLaunchKernelGGL(conv_bwd_data_k, dim3(grid_for(total)), dim3(256), 0, st, dy, w_latent, dx, s);
+  const int64_t total = N * C * H * W;
+  const TileGeo g = geo(s);
+  const size_t lds = (size_t)pk.lds;
+  const int ipb = pk.ipb;
+#define BNN_DATA_LAUNCH_B3(...) \
+  BNN_TILE_LAUNCH((__VA_ARGS__), dim3((unsigned)((N + ipb - 1) / ipb)), dim3(B3_T), lds, st, dy, w_latent, dx, N, pk.bd, ipb)
+#define BNN_DATA_LAUNCH_MF(...) \
+  BNN_TILE_LAUNCH((__VA_ARGS__), dim3((unsigned)((N + MF_IPB - 1) / MF_IPB)), dim3(MF_T), lds, st, dy, w_latent, dx, N, pk.md)
+#define BNN_DATA_LAUNCH_TILE(...) BNN_TILE_LAUNCH((__VA_ARGS__), dim3(N), dim3(TILE_T), lds, st, dy, w_latent, dx, g)
+#define BNN_DATA_LAUNCH_GEN(...) \
+  hipLaunchKernelGGL((__VA_ARGS__), dim3(grid_for(total)), dim3(256), 0, st, dy, w_latent, dx, s)
+#define BNN_X(FAM, P0, P1, ...) \
+  if (pk.fam == kData##FAM && pk.p0 == P0 && pk.p1 == P1) BNN_DATA_LAUNCH_##FAM(__VA_ARGS__); else
+  BNN_CONV_DATA_INSTANCES(BNN_X) return no_instance("bnn_conv2d_bwd_data");
+#undef BNN_X
+#undef BNN_DATA_LAUNCH_B3
+#undef BNN_DATA_LAUNCH_MF
+#undef BNN_DATA_LAUNCH_TILE
+#undef BNN_DATA_LAUNCH_GEN
   return check_launch("bnn_conv2d_bwd_data");
 }
 
@@ -2209,107 +2463,49 @@ BNN_API int bnn_conv2d_bwd_filter(const float* dy, const float* x, int32_t binar
   const int64_t nw = Co * (C / groups) * KH * KW;
   const int64_t nelem = nw + Co;
   const int64_t nchunks = filter_chunks(std::max<int64_t>(N, 1), nelem);
-  C1Filt cf;
-  int64_t clds = 0;
-  if (N > 0 && g_conv_c1f && g_conv_mfma != 0 && c1_filt_geom(s, &cf, &clds)) {
-    const int64_t nblk = (N + C1F_SPB - 1) / C1F_SPB;
-    const int64_t nel = nw + Co;
-    float* part = reinterpret_cast<float*>(work);
-    const size_t lds = (size_t)clds;
-    if (KH == 5) BNN_TILE_LAUNCH((conv_bwd_filter_c1_k<5, 5>), dim3((unsigned)nblk), dim3(C1F_T), lds, st, dy, x,
-                                 binarize_input, part, N, cf, db != nullptr);
-    else BNN_TILE_LAUNCH((conv_bwd_filter_c1_k<3, 3>), dim3((unsigned)nblk), dim3(C1F_T), lds, st, dy, x,
-                         binarize_input, part, N, cf, db != nullptr);
-    const int64_t nsl = filter_slices(nblk);
-    double* slice = reinterpret_cast<double*>(reinterpret_cast<char*>(work) +
-                                              round_up(nblk * nel * (int64_t)sizeof(float), 256));
-    hipLaunchKernelGGL(conv_filter_tile_reduce1_k, dim3((unsigned)((nel + 255) / 256), (unsigned)nsl), dim3(256), 0,
-                       st, part, nblk, nel, nsl, slice);
-    hipLaunchKernelGGL(conv_filter_tile_reduce2_k, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, slice,
-                       nsl, (int)Co, (int)(KH * KW), (int)Co, dw, db);
+  const FiltPick pk = filt_pick(s, binarize_input);
+  const TileGeo g = geo(s);
+  const size_t lds = (size_t)pk.lds;
+  const int ipb = pk.ipb;
+  // the tiled engines write float partials [parts][nel] that the two-stage reduce folds in double;
+  // the generic kernel and an empty batch write double partials [nchunks][nelem]
+  float* part = reinterpret_cast<float*>(work);
+  double* gpart = reinterpret_cast<double*>(work);
+  const unsigned nblk = (unsigned)pk.nblk;
+#define BNN_FILT_LAUNCH_C1(...) \
+  BNN_TILE_LAUNCH((__VA_ARGS__), dim3(nblk), dim3(C1F_T), lds, st, dy, x, binarize_input, part, N, pk.cf, db != nullptr)
+#define BNN_FILT_LAUNCH_B3(...) \
+  BNN_TILE_LAUNCH((__VA_ARGS__), dim3(nblk), dim3(B3_T), lds, st, dy, x, binarize_input, part, N, pk.bf, db != nullptr, ipb)
+#define BNN_FILT_LAUNCH_MF(...) \
+  BNN_TILE_LAUNCH((__VA_ARGS__), dim3(nblk), dim3(MF_T), lds, st, dy, x, binarize_input, part, N, pk.mf, db != nullptr)
+#define BNN_FILT_LAUNCH_TILE(...) \
+  BNN_TILE_LAUNCH((__VA_ARGS__), dim3(nblk), dim3(TILE_T), lds, st, dy, x, binarize_input, part, N, FILTER_SPB, g, db != nullptr)
+#define BNN_FILT_LAUNCH_GEN(...) \
+  hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)((nelem + 255) / 256), (unsigned)nchunks), dim3(256), 0, st, dy, x, \
+                     binarize_input, gpart, nelem, nchunks, s, db != nullptr)
+#define BNN_X(FAM, P0, P1, ...) \
+  if (pk.fam == kFilt##FAM && pk.p0 == P0 && pk.p1 == P1) BNN_FILT_LAUNCH_##FAM(__VA_ARGS__); else
+  if (pk.fam == kFamNone) (void)hipMemsetAsync(gpart, 0, nchunks * nelem * sizeof(double), st);   // N == 0
+  else BNN_CONV_FILT_INSTANCES(BNN_X) return no_instance("bnn_conv2d_bwd_filter");
+#undef BNN_X
+#undef BNN_FILT_LAUNCH_C1
+#undef BNN_FILT_LAUNCH_B3
+#undef BNN_FILT_LAUNCH_MF
+#undef BNN_FILT_LAUNCH_TILE
+#undef BNN_FILT_LAUNCH_GEN
+  if (pk.fam == kFamNone || pk.fam == kFiltGEN) {
+    hipLaunchKernelGGL(conv_bwd_filter_reduce_k, dim3((unsigned)((nelem + 255) / 256)), dim3(256), 0, st,
+                       gpart, nelem, nchunks, nw, dw, db);
     return check_launch("bnn_conv2d_bwd_filter");
   }
-  B3Filt bf;
-  int64_t blds = 0;
-  if (N > 0 && g_conv_mfma == 1 && b3_filt_geom(s, binarize_input, &bf, &blds)) {
-    const int ipb = b3_ipb(N);
-    const int64_t nblk = (N + ipb - 1) / ipb;
-    const int64_t parts = nblk * bf.KS;
-    const int64_t nel = (int64_t)Co * bf.ncombo + Co;
-    float* part = reinterpret_cast<float*>(work);
-    const size_t lds = (size_t)blds;
-    const int per_wave = (bf.ntn + bf.WT - 1) / bf.WT;
-#define BNN_B3F(NA_, MT_) BNN_TILE_LAUNCH((conv_bwd_filter_bf3_k<NA_, MT_>), dim3((unsigned)nblk), dim3(B3_T), lds, st, dy, x, binarize_input, part, N, bf, db != nullptr, ipb)
-#define BNN_B3F_MT(NA_) \
-    if (per_wave <= 1) BNN_B3F(NA_, 1); else if (per_wave <= 2) BNN_B3F(NA_, 2); else if (per_wave <= 4) BNN_B3F(NA_, 4); \
-    else BNN_B3F(NA_, 8);
-    if (bf.NA == 1) { BNN_B3F_MT(1) } else if (bf.NA == 2) { BNN_B3F_MT(2) } else if (bf.NA == 3) { BNN_B3F_MT(3) } else { BNN_B3F_MT(4) }
-#undef BNN_B3F_MT
-#undef BNN_B3F
-    const int64_t nsl = filter_slices(parts);
-    double* slice = reinterpret_cast<double*>(reinterpret_cast<char*>(work) +
-                                              round_up(parts * nel * (int64_t)sizeof(float), 256));
-    hipLaunchKernelGGL(conv_filter_tile_reduce1_k, dim3((unsigned)((nel + 255) / 256), (unsigned)nsl), dim3(256), 0,
-                       st, part, parts, nel, nsl, slice);
-    hipLaunchKernelGGL(conv_filter_tile_reduce2_k, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, slice,
-                       nsl, (int)Co, bf.ncombo, (int)Co, dw, db);
-    return check_launch("bnn_conv2d_bwd_filter");
-  }
-  MfFilt mf;
-  int64_t mlds = 0;
-  if (N > 0 && g_conv_mfma && mf_filt_geom(s, &mf, &mlds)) {
-    const int64_t nblk = (N + MF_IPB - 1) / MF_IPB;
-    const int64_t parts = nblk * mf.KS;
-    const int64_t nel = (int64_t)Co * mf.ncombo + Co;
-    float* part = reinterpret_cast<float*>(work);
-    const size_t lds = (size_t)mlds;
-    const int per_wave = (mf.ntiles + mf.WT - 1) / mf.WT;
-#define BNN_MFF(MT_) BNN_TILE_LAUNCH(conv_bwd_filter_mfma_k<MT_>, dim3((unsigned)nblk), dim3(MF_T), lds, st, dy, x, binarize_input, part, N, mf, db != nullptr)
-    if (per_wave <= 1) BNN_MFF(1); else if (per_wave <= 2) BNN_MFF(2); else if (per_wave <= 4) BNN_MFF(4);
-    else if (per_wave <= 8) BNN_MFF(8); else if (per_wave <= 13) BNN_MFF(13); else BNN_MFF(16);
-#undef BNN_MFF
-    const int64_t nsl = filter_slices(parts);
-    double* slice = reinterpret_cast<double*>(reinterpret_cast<char*>(work) +
-                                              round_up(parts * nel * (int64_t)sizeof(float), 256));
-    hipLaunchKernelGGL(conv_filter_tile_reduce1_k, dim3((unsigned)((nel + 255) / 256), (unsigned)nsl), dim3(256), 0,
-                       st, part, parts, nel, nsl, slice);
-    hipLaunchKernelGGL(conv_filter_tile_reduce2_k, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, slice,
-                       nsl, (int)Co, mf.ncombo, (int)Co, dw, db);
-    return check_launch("bnn_conv2d_bwd_filter");
-  }
-  if (N > 0 && tile_geom_ok(s) && C * KH * KW <= 2 * TILE_T && filter_tile_lds(s) <= kMaxTileLds) {
-    const TileGeo g = geo(s);
-    const int CO = pick_co(Co);
-    const int ncombo = (int)(C * KH * KW);
-    const int64_t nblk = (N + FILTER_SPB - 1) / FILTER_SPB;
-    const int64_t parts = tile_filter_parts(s);
-    float* part = reinterpret_cast<float*>(work);
-    const size_t lds = (size_t)filter_tile_lds(s);
-    switch (CO) {
-      case 8: BNN_TILE_LAUNCH(conv_bwd_filter_tile_k<8>, dim3((unsigned)nblk), dim3(TILE_T), lds, st, dy, x, binarize_input, part, N, FILTER_SPB, g, db != nullptr); break;
-      case 16: BNN_TILE_LAUNCH(conv_bwd_filter_tile_k<16>, dim3((unsigned)nblk), dim3(TILE_T), lds, st, dy, x, binarize_input, part, N, FILTER_SPB, g, db != nullptr); break;
-      case 32: BNN_TILE_LAUNCH(conv_bwd_filter_tile_k<32>, dim3((unsigned)nblk), dim3(TILE_T), lds, st, dy, x, binarize_input, part, N, FILTER_SPB, g, db != nullptr); break;
-      default: BNN_TILE_LAUNCH(conv_bwd_filter_tile_k<64>, dim3((unsigned)nblk), dim3(TILE_T), lds, st, dy, x, binarize_input, part, N, FILTER_SPB, g, db != nullptr); break;
-    }
-    const int64_t nel = (int64_t)CO * ncombo + CO;
-    const int64_t nsl = filter_slices(parts);
-    double* slice = reinterpret_cast<double*>(reinterpret_cast<char*>(work) +
-                                              round_up(parts * nel * (int64_t)sizeof(float), 256));
-    hipLaunchKernelGGL(conv_filter_tile_reduce1_k, dim3((unsigned)((nel + 255) / 256), (unsigned)nsl), dim3(256), 0,
-                       st, part, parts, nel, nsl, slice);
-    hipLaunchKernelGGL(conv_filter_tile_reduce2_k, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, slice,
-                       nsl, CO, ncombo, (int)Co, dw, db);
-    return check_launch("bnn_conv2d_bwd_filter");
-  }
-  double* part = reinterpret_cast<double*>(work);
-  if (N == 0) {
-    (void)hipMemsetAsync(part, 0, nchunks * nelem * sizeof(double), st);
-  } else {
-    hipLaunchKernelGGL(conv_bwd_filter_k, dim3((unsigned)((nelem + 255) / 256), (unsigned)nchunks),
-                       dim3(256), 0, st, dy, x, binarize_input, part, nelem, nchunks, s, db != nullptr);
-  }
-  hipLaunchKernelGGL(conv_bwd_filter_reduce_k, dim3((unsigned)((nelem + 255) / 256)), dim3(256), 0, st,
-                     part, nelem, nchunks, nw, dw, db);
+  const int64_t parts = pk.parts, nel = (int64_t)pk.rco * pk.rcombo + pk.rco;
+  const int64_t nsl = filter_slices(parts);
+  double* slice = reinterpret_cast<double*>(reinterpret_cast<char*>(work) +
+                                            round_up(parts * nel * (int64_t)sizeof(float), 256));
+  hipLaunchKernelGGL(conv_filter_tile_reduce1_k, dim3((unsigned)((nel + 255) / 256), (unsigned)nsl), dim3(256), 0,
+                     st, part, parts, nel, nsl, slice);
+  hipLaunchKernelGGL(conv_filter_tile_reduce2_k, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, slice,
+                     nsl, pk.rco, pk.rcombo, (int)Co, dw, db);
   return check_launch("bnn_conv2d_bwd_filter");
 }
 

@@ -460,6 +460,21 @@ int bnn_bn2d_set_rows(int32_t on);
  * fragment ds_read_b128, 400 = conflict-free); -1 where the kernel does not take the shape. */
 int bnn_conv_bf3_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
                       int32_t stride, int32_t pad, int32_t dil, int32_t groups, int64_t* out);
+/* Host-only dispatch query (needs no GPU, launches nothing): the kernel template instance that
+ * bnn_conv2d_fwd (op 0), bnn_conv2d_bwd_data (op 1) or bnn_conv2d_bwd_filter (op 2) runs for a shape
+ * under the current bnn_conv_set_mfma / _c1_filter / _popc settings, e.g. "conv_fwd_bin_c1_k<8,2>".
+ * The run-time schedule choices that change control flow inside a kernel are appended:
+ * "conv_bwd_data_bf3_k<1,2> rowt=1 ipb=8", "conv_bwd_filter_bf3_k<2,4> WT=8 KS=1 ipb=8",
+ * "conv_bwd_filter_mfma_k<4> WT=4 KS=1".  "" for a shape the entries refuse (a dilated kernel larger
+ * than the padded input included), "none" for an empty batch, "popc" when the popcount engine takes
+ * the forward.  The entries and the query share one decision function per op.  binarize_input is
+ * ignored by op 1.  The string is valid until the calling thread's next query.
+ * bnn_conv_kernel_at: the index-th instance op can launch (the table the launch chain is generated
+ * from, without schedule suffixes); "" past the end. */
+const char* bnn_conv_kernel(int32_t op, int32_t binarize_input, int64_t N, int64_t C, int64_t H, int64_t W,
+                            int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad, int32_t dil,
+                            int32_t groups);
+const char* bnn_conv_kernel_at(int32_t op, int32_t index);
 
 /* ---------------------------------------------------------------- BatchNorm1d (+ Hardtanh)
  * The layers between the binarized GEMMs in the reference Net (mnist-dist2.py:52-74):

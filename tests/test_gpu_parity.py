@@ -244,7 +244,8 @@ def test_conv_cnn_shapes_vs_oracle(F):
     (2, 64, 6, 7, 64, 1, 0, True, True),
     (11, 3, 9, 12, 3, 7, 3, False, False),
     (4, 20, 5, 5, 64, 5, 4, True, True),
-    # ... and shapes that take the generic kernels (stride 2 / pad > K-1 / C > 64)
+    # ... and shapes that take the generic kernels (pad > K-1 / C > 64; stride, dilation and groups
+    # are covered by tests/test_gpu_conv_dispatch.py)
     (3, 4, 9, 9, 6, 3, 3, True, True),
     (2, 80, 5, 5, 8, 3, 1, True, True),
 ])
