@@ -97,6 +97,8 @@ SIGNATURES = {
     "bnn_conv_kernel": (ctypes.c_char_p, [I32, I32, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32]),
     "bnn_conv_kernel_at": (ctypes.c_char_p, [I32, I32]),
     "bnn_bn_workspace": (I64, [I64, I64]),
+    "bnn_bn_plan": (I32, [I64, I64, ctypes.POINTER(I64)]),
+    "bnn_bn2d_plan": (I32, [I64, I64, I64, I64, I32, ctypes.POINTER(I64)]),
     "bnn_bn_fwd_train": (I32, [P, I64, I64, P, P, P, P, F32, F32, P, P, P, P, I32, P, P]),
     "bnn_bn_fwd_final_parts": (I32, [P, I64, I64, I64, I64, P, P, F32, F32, P, P, P, P]),
     "bnn_bn_fwd_eval": (I32, [P, I64, I64, P, P, P, P, F32, P, I32, P, P]),

@@ -1325,17 +1325,19 @@ inline int grid_for(int64_t n) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384));
 }
 
-bool bn_args_ok(const float* x, int64_t M, int64_t C) {
-  return x && M > 0 && C > 0 && C % 4 == 0 && aligned16(x) && (C / 4) * bn_chunks(M, C) < (1LL << 31) &&
+// the shapes the BatchNorm1d entries take (bnn_bn_plan answers -1 for the others)
+bool bn_shape_ok(int64_t M, int64_t C) {
+  return M > 0 && C > 0 && C % 4 == 0 && (C / 4) * bn_chunks(M, C) < (1LL << 31) &&
          (M + apply_rows(M, C) - 1) / apply_rows(M, C) <= 65535;
 }
+
+bool bn_args_ok(const float* x, int64_t M, int64_t C) { return x && aligned16(x) && bn_shape_ok(M, C); }
 
 bool vec_ok(const float* p) { return p == nullptr || aligned16(p); }
 
 // the int16 form (XIn z16): 8-B aligned values (4 per 8-B load), 16-B aligned bias or none
 bool bn_args_ok16(const XIn& in, int64_t M, int64_t C) {
-  return in.p && (reinterpret_cast<uintptr_t>(in.p) & 7) == 0 && vec_ok(in.bias) && M > 0 && C > 0 && C % 4 == 0 &&
-         (C / 4) * bn_chunks(M, C) < (1LL << 31) && (M + apply_rows(M, C) - 1) / apply_rows(M, C) <= 65535;
+  return in.p && (reinterpret_cast<uintptr_t>(in.p) & 7) == 0 && vec_ok(in.bias) && bn_shape_ok(M, C);
 }
 
 // the s20 form (XIn XF 2): the int16 plane as above, the nibble plane 2-B aligned (4 per 2-B load)
@@ -1782,11 +1784,16 @@ __global__ __launch_bounds__(256) void bn2d_bwd_apply_k(X2 x, const float* __res
   }
 }
 
-bool bn2_args_ok(const float* x, int64_t N, int64_t C, int64_t H, int64_t W, int pool) {
-  if (!x || N <= 0 || C <= 0 || H <= 0 || W <= 0 || !aligned16(x) || C > 65535) return false;
+// the shapes the BatchNorm2d entries take (bnn_bn2d_plan answers -1 for the others)
+bool bn2_shape_ok(int64_t N, int64_t C, int64_t H, int64_t W, int pool) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || C > 65535) return false;
   if ((H * W) % 4 != 0) return false;
   if (pool != 0 && (pool != 2 || H % 2 != 0 || W % 2 != 0)) return false;
   return (N + bn2_chunk_images(N, C) - 1) / bn2_chunk_images(N, C) <= 65535;
+}
+
+bool bn2_args_ok(const float* x, int64_t N, int64_t C, int64_t H, int64_t W, int pool) {
+  return x && aligned16(x) && bn2_shape_ok(N, C, H, W, pool);
 }
 
 }  // namespace
@@ -1818,6 +1825,23 @@ BNN_API int64_t bnn_dropout_keep_bits_bytes(int64_t M, int64_t C) {
 BNN_API int64_t bnn_bn_workspace(int64_t M, int64_t C) {
   // two double partial arrays [R][C] + two float vectors [C]
   return 2 * bn_chunks(M, C) * C * (int64_t)sizeof(double) + 2 * round_up(C * 4, 256);
+}
+
+// Host-only: what the BatchNorm1d entries launch for [M][C] -- the same decision functions the
+// launches below consume (bn_chunk_rows, bn_chunks, apply_rows, apply_grid, keep_bits_fused).
+// out[0] rows per reduction chunk, [1] chunk count R, [2] rows per apply workgroup, [3], [4] the
+// apply grid (x, y), [5] 1 where the forward statistics pass writes the keep-bit plane.
+// -1 (out untouched) for a shape the entries refuse.  Launches nothing, needs no GPU.
+BNN_API int bnn_bn_plan(int64_t M, int64_t C, int64_t* out) {
+  if (!out || !bn_shape_ok(M, C)) return -1;
+  const dim3 g = apply_grid(M, C);
+  out[0] = bn_chunk_rows(M, C);
+  out[1] = bn_chunks(M, C);
+  out[2] = apply_rows(M, C);
+  out[3] = g.x;
+  out[4] = g.y;
+  out[5] = keep_bits_fused(M, C) ? 1 : 0;
+  return 0;
 }
 
 static int bn_fwd_train_impl(XIn xin, bool z16, int64_t M, int64_t C, const float* gamma, const float* beta,
@@ -2381,6 +2405,38 @@ BNN_API int bnn_bn2d_set_rows(int32_t on) {
   return 0;
 }
 
+// The BatchNorm2d dispatch, one decision per pass; the launches below and bnn_bn2d_plan both call
+// these.  Statistics: 1 = the flattened kernel (bn2d_fwd_stats_flat_k), 0 = the window kernel
+// (bn2d_reduce_k<0>).  The others: 14 / 7 = the row kernels' PW (28- / 14-wide pooled planes),
+// 0 = the window-per-thread kernels.
+static int bn2_fwd_stats_kind(int64_t CR, int64_t H, int64_t W) {
+  return (g_bn2_rows && (H * W) % 4 == 0 && CR * (H * W / 4) < (1LL << 30)) ? 1 : 0;
+}
+static int bn2_rows_pw(bool rows_on, int32_t pool, int64_t W) {
+  return (pool && rows_on && (W == 28 || W == 14)) ? (int)(W / 2) : 0;
+}
+static int bn2_fwd_apply_kind(int32_t pool, int64_t W) { return bn2_rows_pw(g_bn2_rows != 0, pool, W); }
+static int bn2_bwd_stats_kind(int32_t pool, int64_t W) { return bn2_rows_pw(g_bn2_rows != 0, pool, W); }
+static int bn2_bwd_apply_kind(int32_t pool, int64_t W) { return bn2_rows_pw(g_bn2_rows == 2, pool, W); }
+
+// Host-only: what the BatchNorm2d train entries launch for [N][C][H][W] under the current
+// bnn_bn2d_set_rows.  out[0] images per chunk CR, [1] chunk count R, [2] forward statistics
+// (1 flat, 0 window), [3] forward apply, [4] backward statistics, [5] backward apply (14 / 7 the
+// row kernels, 0 the window kernels), [6] the bnn_bn2d_set_rows value in force.  -1 (out
+// untouched) for a shape the entries refuse.  Launches nothing, needs no GPU.
+BNN_API int bnn_bn2d_plan(int64_t N, int64_t C, int64_t H, int64_t W, int32_t pool, int64_t* out) {
+  if (!out || !bn2_shape_ok(N, C, H, W, pool)) return -1;
+  const int64_t CR = bn2_chunk_images(N, C);
+  out[0] = CR;
+  out[1] = (N + CR - 1) / CR;
+  out[2] = bn2_fwd_stats_kind(CR, H, W);
+  out[3] = bn2_fwd_apply_kind(pool, W);
+  out[4] = bn2_bwd_stats_kind(pool, W);
+  out[5] = bn2_bwd_apply_kind(pool, W);
+  out[6] = g_bn2_rows;
+  return 0;
+}
+
 static int bn2d_fwd_train_impl(X2 x, int xf, int64_t N, int64_t C, int64_t H, int64_t W, const float* gamma,
                                const float* beta, float* running_mean, float* running_var, float momentum,
                                float eps, float* save_mean, float* save_invstd, float* y, int32_t hardtanh,
@@ -2396,7 +2452,7 @@ static int bn2d_fwd_train_impl(X2 x, int xf, int64_t N, int64_t C, int64_t H, in
   const int64_t CR = bn2_chunk_images(N, C), R = (N + CR - 1) / CR;
   double* p0 = reinterpret_cast<double*>(work);
   double* p1 = p0 + R * C;
-  if (g_bn2_rows && (H * W) % 4 == 0 && CR * (H * W / 4) < (1LL << 30)) {   // flattened, batched loads
+  if (bn2_fwd_stats_kind(CR, H, W)) {   // flattened, batched loads
     BN2_XF_SWITCH(xf, hipLaunchKernelGGL((bn2d_fwd_stats_flat_k<XFV>), dim3((unsigned)C, (unsigned)R), dim3(BN2_T), 0,
                                          s, x, N, C, (int)(H * W), CR, p0, p1));
   } else {
@@ -2407,9 +2463,9 @@ static int bn2d_fwd_train_impl(X2 x, int xf, int64_t N, int64_t C, int64_t H, in
   hipLaunchKernelGGL(bn_fwd_final_k, ffin_grid(C), dim3(256), 0, s, p0, p1, N, C, R,
                      momentum, eps, running_mean, running_var, save_mean, save_invstd, nullptr, CR, H * W);
   const int64_t outs = pool ? N * C * (H / 2) * (W / 2) : N * C * H * W / 4;
-  if (pool && g_bn2_rows && (W == 28 || W == 14)) {   // the BinCNN's pooled layers: one row per thread
+  if (const int pw = bn2_fwd_apply_kind(pool, W)) {   // the BinCNN's pooled layers: one row per thread
     const dim3 rg((unsigned)((N * C * (H / 2) + 255) / 256));
-    if (W == 28)
+    if (pw == 14)
       BN2_XF_SWITCH(xf, hipLaunchKernelGGL((bn2d_apply_rows_k<14, XFV>), rg, dim3(256), 0, s, x, N, C, (int)H,
                                            save_mean, save_invstd, gamma, beta, hardtanh, y));
     else
@@ -2475,8 +2531,8 @@ static int bn2d_bwd_impl(X2 x, int xf, const float* dy, int64_t N, int64_t C, in
   double* p1 = p0 + R * C;
   float* k0 = k0_out ? k0_out : reinterpret_cast<float*>(p1 + R * C);
   float* k1 = k1_out ? k1_out : reinterpret_cast<float*>(reinterpret_cast<char*>(p1 + R * C) + round_up(C * 4, 256));
-  if (pool && g_bn2_rows && (W == 28 || W == 14)) {   // the BinCNN's pooled layers: row-batched loads
-    if (W == 28)
+  if (const int pw = bn2_bwd_stats_kind(pool, W)) {   // the BinCNN's pooled layers: row-batched loads
+    if (pw == 14)
       BN2_XF_SWITCH(xf, hipLaunchKernelGGL((bn2d_bwd_stats_rows_k<14, XFV>), dim3((unsigned)C, (unsigned)R),
                                            dim3(BN2_T), 0, s, x, dy, N, C, (int)H, CR, save_mean, save_invstd, gamma,
                                            beta, hardtanh, p0, p1));
@@ -2497,9 +2553,9 @@ static int bn2d_bwd_impl(X2 x, int xf, const float* dy, int64_t N, int64_t C, in
     // (the row form, bn2d_bwd_apply_rows_k, is built for A/B only -- g_bn2_rows == 2: its two
     // full-resolution output rows per thread write 8-B pieces 224 B apart, 186 vs 70 us on the
     // BinCNN's first layer, profiles/r04_cnn_bn2d_rows.log)
-    if (pool && g_bn2_rows == 2 && (W == 28 || W == 14)) {
+    if (const int pw = bn2_bwd_apply_kind(pool, W)) {
       const dim3 rg((unsigned)((N * C * (H / 2) + 255) / 256));
-      if (W == 28)
+      if (pw == 14)
         BN2_XF_SWITCH(xf, hipLaunchKernelGGL((bn2d_bwd_apply_rows_k<14, XFV>), rg, dim3(256), 0, s, x, dy, N, C,
                                              (int)H, save_mean, save_invstd, gamma, beta, hardtanh, k0, k1, inv_n, dx));
       else

@@ -492,6 +492,12 @@ const char* bnn_conv_kernel_at(int32_t op, int32_t index);
  * gets the sign of the exact difference, as the reference's (double-accumulated) CPU BatchNorm
  * gives it.  Pass the same save_mean_lo to the backward / apply-pack calls (NULL = 0). */
 int64_t bnn_bn_workspace(int64_t M, int64_t C);
+/* Host-only plan query (needs no GPU, launches nothing): the schedule the BatchNorm1d entries run
+ * for [M][C], from the decision functions the launches consume.  out[6]: rows per reduction chunk,
+ * chunk count R = ceil(M / rows), rows per workgroup of the elementwise passes, their grid (x, y),
+ * and 1 where the forward statistics pass of bnn_bn_dropout_fwd_train writes the keep-bit plane
+ * itself (0: a kernel of its own does).  -1 for a shape the entries refuse. */
+int bnn_bn_plan(int64_t M, int64_t C, int64_t* out);
 int bnn_bn_fwd_train(const float* x, int64_t M, int64_t C, const float* gamma, const float* beta,
                      float* running_mean, float* running_var, float momentum, float eps,
                      float* save_mean, float* save_invstd, float* save_mean_lo, float* y, int32_t hardtanh,
@@ -525,6 +531,14 @@ int bnn_bn_bwd_eval(const float* x, const float* dy, int64_t M, int64_t C, const
  * full-resolution output or pooling indices are stored.  `work` scratch of
  * bnn_bn2d_workspace(N, C) bytes.  Deterministic. */
 int64_t bnn_bn2d_workspace(int64_t N, int64_t C);
+/* Host-only plan query (needs no GPU, launches nothing): what the BatchNorm2d train entries run for
+ * [N][C][H][W] under the current bnn_bn2d_set_rows; the entries and the query call one decision
+ * function per pass.  out[7]: images per chunk CR, chunk count R = ceil(N / CR), the forward
+ * statistics kernel (1 flattened, 0 window), then the forward apply, the backward statistics and
+ * the backward apply (14 / 7: the row kernels of 28- / 14-wide pooled planes, 0: the
+ * window-per-thread kernels), and the bnn_bn2d_set_rows value in force.  -1 for a shape the
+ * entries refuse. */
+int bnn_bn2d_plan(int64_t N, int64_t C, int64_t H, int64_t W, int32_t pool, int64_t* out);
 int bnn_bn2d_fwd_train(const float* x, int64_t N, int64_t C, int64_t H, int64_t W, const float* gamma,
                        const float* beta, float* running_mean, float* running_var, float momentum,
                        float eps, float* save_mean, float* save_invstd, float* y, int32_t hardtanh,
