@@ -24,6 +24,7 @@ __all__ = [
     "KernelTimer", "timing", "sign", "sign_pack", "sign_pack_bits", "quant_rows", "quant_cols_t", "gemm_i8", "gemm_xnor",
     "quant6_rows", "quant6_cols_t", "gemm_fp6", "set_digit_gemm",
     "binary_linear", "binary_conv2d", "hardtanh_backward", "adam_clamp_", "adam_clamp_pack_", "packed_weight",
+    "sgd_clamp_", "sgd_clamp_multi_", "sgd_clamp_pack_",
     "invalidate_packed", "batch_norm_hardtanh",
     "bn_hardtanh_binary_linear", "batch_norm2d_hardtanh_pool", "dropout_batch_norm_hardtanh", "dropout_mask",
     "BinaryLinearFunction", "BinaryConv2dFunction",
@@ -421,6 +422,42 @@ def adam_clamp_pack_(p, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.
             L.call("bnn_adam_clamp_pack", L.ptr(p), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), N, K,
                    float(lr), float(beta1), float(beta2), float(eps), int(step), float(grad_scale),
                    int(bool(clamp)), *tail)
+    _bump(p)
+    ent["key"] = _pack_key(p)           # the operands just written match the bumped version
+    return True
+
+
+def _sgd_omd(dampening):
+    """The multiplier 1 - dampening that libbnn's SGD entries take, formed in double as torch forms
+    its ``alpha`` (the C side casts it to float)."""
+    return 1.0 - float(dampening)
+
+
+def sgd_clamp_pack_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
+                    grad_scale=1.0, clamp=True):
+    """bnn_sgd_clamp on a 2-D latent weight that also rewrites its cached packed operands (see
+    packed_weight), as adam_clamp_pack_ does for Adam.  ``buf`` is the momentum buffer (None exactly
+    when momentum is 0); ``first``: it holds nothing yet and is only written.  Returns False
+    (nothing done) when ``p`` has no valid cache."""
+    if _ADAM_TILE256[0] is not None:
+        L.call("bnn_adam_pack_set_tile256", int(_ADAM_TILE256[0] != "0"))
+        _ADAM_TILE256[0] = None
+    ent = getattr(p, "_bnn_pack", None)
+    if ent is None or ent["key"] != _pack_key(p) or p.dim() != 2:
+        return False
+    _check(p, grad, buf)
+    for t in (p, grad, buf):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("sgd_clamp_pack_: tensors must be contiguous")
+    N, K = p.shape
+    q, qt = ent["q"], ent["qt"]
+    streams = 3 if buf is None else (4 if first else 5)
+    nbytes = 4 * streams * N * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
+    with _timed("sign_pack_tile_k<sgd>", 0, nbytes):
+        L.call("bnn_sgd_clamp_pack", L.ptr(p), L.ptr(grad), L.ptr(buf), N, K, float(lr), float(momentum),
+               _sgd_omd(dampening), float(weight_decay), int(bool(nesterov)), int(bool(first)), float(grad_scale),
+               int(bool(clamp)), 1 if ent["fmt"] == "fp4" else 0, L.ptr(q), q.shape[1] if q is not None else 0,
+               L.ptr(qt), qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
     _bump(p)
     ent["key"] = _pack_key(p)           # the operands just written match the bumped version
     return True
@@ -1647,6 +1684,49 @@ def adam_clamp_multi_(items, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.
         vp = [ctypes.cast(a, ctypes.c_void_p) for a in arr + [nn_, st, cl]]
         L.call("bnn_adam_clamp_multi", k, *vp, float(lr), float(beta1), float(beta2), float(eps), L.ptr(sched),
                L.ptr(ctr), float(grad_scale), L.stream())
+
+
+def sgd_clamp_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
+               grad_scale=1.0, clamp=True):
+    """In-place fused SGD (torch.optim.SGD's formula, bit-identical to its CPU fp32 result) + clamp to
+    [-1, 1] on a latent weight.  ``buf``: the momentum buffer, None exactly when momentum is 0;
+    ``first``: the buffer holds nothing yet (it becomes the gradient, torch's clone rule)."""
+    _check(p, grad, buf)
+    invalidate_packed(p)        # a raw in-place write: cached packed operands would go stale
+    for t in (p, grad, buf):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("sgd_clamp_: tensors must be contiguous")
+    _bump(p)
+    with _timed("sgd_clamp_k", 0, 4 * p.numel() * (3 if buf is None else (4 if first else 5))):
+        L.call("bnn_sgd_clamp", L.ptr(p), L.ptr(grad), L.ptr(buf), p.numel(), float(lr), float(momentum),
+               _sgd_omd(dampening), float(weight_decay), int(bool(nesterov)), int(bool(first)), float(grad_scale),
+               int(bool(clamp)), L.stream())
+
+
+def sgd_clamp_multi_(items, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0):
+    """sgd_clamp_ on several tensors in one launch per ADAM_MULTI_MAX: items = [(p, grad, buf, first,
+    clamp)] (buf None when momentum is 0), bit-identical per tensor to sgd_clamp_ (bnn_sgd_clamp_multi)."""
+    import ctypes
+    for i in range(0, len(items), ADAM_MULTI_MAX):
+        chunk = items[i:i + ADAM_MULTI_MAX]
+        nbytes = 0
+        for p, g, b, first, _ in chunk:
+            _check(p, g, b)
+            invalidate_packed(p)
+            for t in (p, g, b):
+                if t is not None and not t.is_contiguous():
+                    raise ValueError("sgd_clamp_multi_: tensors must be contiguous")
+            _bump(p)
+            nbytes += 4 * p.numel() * (3 if b is None else (4 if first else 5))
+        k = len(chunk)
+        arr = [(ctypes.c_void_p * k)(*[None if it[j] is None else it[j].data_ptr() for it in chunk]) for j in range(3)]
+        nn_ = (ctypes.c_int64 * k)(*[it[0].numel() for it in chunk])
+        fi = (ctypes.c_int32 * k)(*[int(bool(it[3])) for it in chunk])
+        cl = (ctypes.c_int32 * k)(*[int(bool(it[4])) for it in chunk])
+        vp = [ctypes.cast(a, ctypes.c_void_p) for a in arr + [nn_, fi, cl]]
+        with _timed("sgd_clamp_multi_k", 0, nbytes):
+            L.call("bnn_sgd_clamp_multi", k, *vp, float(lr), float(momentum), _sgd_omd(dampening),
+                   float(weight_decay), int(bool(nesterov)), float(grad_scale), L.stream())
 
 
 # ----------------------------------------------------------------------------- BatchNorm1d (+ Hardtanh)

@@ -25,7 +25,7 @@ input; ``stoch_salt`` numbers the site (functional.stochastic_s
 
 Two class attributes switch behaviour for the build's own trainer:
   ``org_protocol = False`` keeps the latent weight in the Parameter itself (no ``.org``,
-  binarised on the fly inside the kernel; pair it with ``bnn_amd.optim.LatentAdam``), and
+  binarised on the fly inside the kernel; pair it with ``bnn_amd.optim.LatentAdam`` or ``LatentSGD``), and
   ``mutate_input = False`` skips materialising ``sign(input)`` in fp32 (nothing reads it).
 
 A ``uint8`` input to a 784-input ``BinarizeLinear`` is taken as the raw pixels the reference's

@@ -19,6 +19,11 @@ per-forward sign-pack of the weight.
 With ``device_step`` (a ``functional.DeviceStep``) the step is graph-capturable: the bias
 corrections come from a device table indexed by the device step counter (bit-identical to the
 per-launch values), and the counter is advanced on the device after the last update.
+
+``LatentSGD`` is the same fusion around ``torch.optim.SGD``, the optimizer of the reference's ConvNet
+scripts (mnist.py, mnist-dist.py, mnist-mixed.py) and DDP demos (mnist-distributed-BNNS2.py): momentum,
+dampening, weight decay and Nesterov as torch computes them, the clamp, and the re-pack of a binarized
+layer's weight in one pass (bnn_sgd_clamp_pack).
 """
 import os
 
@@ -177,6 +182,89 @@ class LatentAdam(torch.optim.Optimizer):
                                      sched=sched, ctr=ds.ctr if sched is not None else None)
         for side, main in joined.values():
             main.wait_stream(side)
+        if ds is not None:
+            ds.advance()
+        return loss
+
+
+class LatentSGD(torch.optim.Optimizer):
+    """``torch.optim.SGD`` (momentum, dampening, weight decay, Nesterov) fused with clamp(-1, 1) for the
+    parameters in ``clamp_params``; bit-identical to torch's CPU fp32 step followed by ``clamp_``.
+
+    State is torch's: ``momentum_buffer`` per parameter, allocated on the parameter's first step and
+    absent when momentum is 0, so a ``torch.optim.SGD`` state_dict loads.  ``maximize`` is not built.
+
+    With ``device_step`` the step advances the device counter after the last update (dropout and
+    stochastic-binarization seeds move) and can be captured by ``graph.GraphedStep``: nothing in the
+    update depends on the step count, so there is no device table.  A parameter's first step
+    allocates its buffer and cannot be captured (GraphedStep's warm-up runs it eagerly).  lr and the
+    other hyper-parameters are passed to the kernels by value: a captured step keeps the values of
+    its capture, and a changed lr needs a recapture, as with LatentAdam.
+    """
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False,
+                 clamp_params=(), grad_scale=1.0, device_step=None):
+        # torch.optim.SGD's own checks and messages
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                        nesterov=nesterov, maximize=False)
+        super().__init__(params, defaults)
+        self._clamp = {id(p) for p in clamp_params}
+        self.grad_scale = grad_scale
+        self.device_step = device_step
+
+    @staticmethod
+    def _refuse_maximize(groups):
+        if any(g.get("maximize", False) for g in groups):
+            raise ValueError("LatentSGD: maximize=True is not supported")
+
+    def add_param_group(self, param_group):
+        self._refuse_maximize([param_group])
+        super().add_param_group(param_group)
+
+    def load_state_dict(self, state_dict):
+        self._refuse_maximize(state_dict["param_groups"])
+        super().load_state_dict(state_dict)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        ds = self.device_step
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        self._refuse_maximize(self.param_groups)
+        for group in self.param_groups:
+            mu = group["momentum"]
+            hyper = dict(momentum=mu, dampening=group["dampening"], weight_decay=group["weight_decay"],
+                         nesterov=group["nesterov"], grad_scale=self.grad_scale)
+            small = []                # plain SGD + clamp tensors: one multi-tensor launch per 16
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                buf, first = None, False
+                if mu != 0:
+                    buf = (self.state.get(p) or {}).get("momentum_buffer")
+                    if buf is None:
+                        if capturing:
+                            raise RuntimeError("LatentSGD: a captured step cannot be a parameter's first (it "
+                                               "allocates the momentum buffer); run one eager step before capturing")
+                        buf = torch.empty_like(p, memory_format=torch.contiguous_format)
+                        self.state[p]["momentum_buffer"] = buf
+                        first = True
+                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                clamp = id(p) in self._clamp
+                # a binarized layer's weight also gets its next-forward ternary operands rewritten in the
+                # same pass (bnn_sgd_clamp_pack); anything else: plain fused SGD + clamp
+                if not BF.sgd_clamp_pack_(p, g, buf, group["lr"], first=first, clamp=clamp, **hyper):
+                    small.append((p, g, buf, first, clamp))
+            if small:
+                BF.sgd_clamp_multi_(small, group["lr"], **hyper)
         if ds is not None:
             ds.advance()
         return loss

@@ -7,7 +7,8 @@
 
 Flags keep the reference's names (-n/--nodes, -g/--gpus, -nr/--nr, --epochs, --seed, --lr,
 --log-interval; mnist-dist2.py:23-37).  Semantics kept: batch 64 by default (:88), Adam(lr) on
-the latent weights (:91), DistributedSampler order with seed 0 and no set_epoch (:100-108),
+the latent weights (:91; --optimizer sgd: the SGD of the ConvNet scripts, fused as LatentSGD),
+DistributedSampler order with seed 0 and no set_epoch (:100-108),
 1-based epochs with the per-batch ``lr *= 0.1`` whenever ``epoch % 40 == 0`` (:126-127), the
 .org restore -> step -> clamp protocol (:131-137, here fused into LatentAdam), AverageMeter batch
 timing and the reference's log line (:139-146), optional CSVs in the reference's format
@@ -31,7 +32,7 @@ from .checkpoint import load_checkpoint, save_checkpoint
 from .graph import GraphedStep
 from .data import load_idx_dataset, shard_indices, synthetic_mnist
 from .inference import freeze
-from .optim import LatentAdam
+from .optim import LatentAdam, LatentSGD
 from .parallel import GradExchange
 
 EVAL_SEED = 4321     # --eval's held-out synthetic samples (the training set is seed 1234)
@@ -73,12 +74,19 @@ def parse(argv=None):
     ap.add_argument("--no-lr-quirk", action="store_true", help="drop the per-batch lr*=0.1 at epoch%%40==0")
     ap.add_argument("--lr-quirk-period", type=int, default=40, help="the 40 of epoch%%40==0 (mnist-dist2.py:126)")
     ap.add_argument("--device-step", action="store_true", help="eager steps on the device step counter (dropout "
-                    "seeds and Adam as --graph draws them: an eager twin of a --graph run)")
+                    "seeds and the optimizer as --graph draws them: an eager twin of a --graph run)")
     ap.add_argument("--stochastic", action="store_true", help="stochastic activation binarization in training "
                     "(Binarize(t, 'stoch') on the hidden layers' inputs; eval and --eval stay deterministic)")
     ap.add_argument("--loss", default="ce", choices=("ce", "hinge", "sqhinge"), help="the criterion: ce = "
                     "CrossEntropyLoss on the LogSoftmax output (mnist-dist2.py:118-137); hinge / sqhinge = the mean "
                     "(squared) hinge of models/binarized_modules.py on the logits, one-vs-all +-1 targets")
+    ap.add_argument("--optimizer", default="adam", choices=("adam", "sgd"), help="adam = LatentAdam "
+                    "(mnist-dist2.py:91); sgd = LatentSGD, torch.optim.SGD of the reference's ConvNet scripts (mnist.py, mnist-dist.py, "
+                    "mnist-mixed.py, mnist-distributed-BNNS2.py), with the flags below")
+    ap.add_argument("--momentum", type=float, default=0.0, help="--optimizer sgd")
+    ap.add_argument("--dampening", type=float, default=0.0, help="--optimizer sgd")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="--optimizer sgd")
+    ap.add_argument("--nesterov", action="store_true", help="--optimizer sgd")
     ap.add_argument("--csv-prefix", default=None, help="write <prefix>_BATCH_TIME.csv / _EPOCH_TIME.csv")
     ap.add_argument("--checkpoint", default=None, help="write a latent-weight checkpoint here after every epoch")
     ap.add_argument("--resume", default=None, help="resume from a checkpoint written by --checkpoint")
@@ -88,6 +96,26 @@ def parse(argv=None):
     ap.add_argument("--master-addr", default=os.environ.get("MASTER_ADDR", "127.0.0.1"))
     ap.add_argument("--master-port", default=os.environ.get("MASTER_PORT", "23456"))
     return ap.parse_args(argv)
+
+
+def optimizer_kind(state_dict):
+    """"adam" / "sgd": which optimizer wrote this state_dict, told from its param_groups."""
+    groups = state_dict.get("param_groups") or [{}]
+    if "betas" in groups[0]:
+        return "adam"
+    if "momentum" in groups[0]:
+        return "sgd"
+    return None
+
+
+def check_resume_optimizer(path, want, map_location=None):
+    """--resume: end with a SystemExit when the checkpoint's optimizer state is the other optimizer's."""
+    blob = torch.load(path, map_location=map_location, weights_only=True)
+    opt_sd = blob.get("optimizer") if isinstance(blob, dict) else None
+    have = optimizer_kind(opt_sd) if opt_sd else None
+    if have is not None and have != want:
+        raise SystemExit(f"--resume {path}: the checkpoint holds --optimizer {have} state, this run has "
+                         f"--optimizer {want}; resume with --optimizer {have}")
 
 
 def load_dataset(args, device, rank, as_u8=True):
@@ -124,13 +152,19 @@ def train(gpu, args):
     if args.graph and world > 1:
         raise SystemExit("--graph runs one process (the gradient exchange is not captured)")
     dstep = BF.DeviceStep(device).activate() if (args.graph or args.device_step) else None
-    opt = LatentAdam(model.parameters(), lr=args.lr, clamp_params=nets.binary_params(model), device_step=dstep)
+    if args.optimizer == "sgd":
+        opt = LatentSGD(model.parameters(), lr=args.lr, momentum=args.momentum, dampening=args.dampening,
+                        weight_decay=args.weight_decay, nesterov=args.nesterov,
+                        clamp_params=nets.binary_params(model), device_step=dstep)
+    else:
+        opt = LatentAdam(model.parameters(), lr=args.lr, clamp_params=nets.binary_params(model), device_step=dstep)
     if args.loss == "ce":
         crit = torch.nn.CrossEntropyLoss()
     else:
         crit = BNN.HingeLoss() if args.loss == "hinge" else BNN.SqrtHingeLoss()     # on the int64 labels
     first_epoch = 1
     if args.resume:
+        check_resume_optimizer(args.resume, args.optimizer, map_location="cpu")
         first_epoch = load_checkpoint(args.resume, model, opt, map_location=device) + 1
     data, targets = load_dataset(args, device, rank, as_u8=args.model != "cnn" and not args.fp32_input)
     idx = torch.tensor(shard_indices(len(data), world, rank), device=device)
@@ -182,7 +216,7 @@ def train(gpu, args):
                 loss = crit(model(x), y)
                 if quirk:
                     opt.param_groups[0]["lr"] *= 0.1
-                    graphed = None          # the captured step holds the old lr's Adam schedule
+                    graphed = None          # the captured step holds the old lr (Adam's schedule, SGD's argument)
                 loss.backward()
                 if exchange is not None:
                     exchange.finish()
@@ -226,6 +260,7 @@ def train(gpu, args):
 
 
 def main(argv=None):
+    """Run the trainer; a single-process run returns the trained model."""
     args = parse(argv)
     if "RANK" in os.environ and "WORLD_SIZE" in os.environ:
         train(int(os.environ.get("LOCAL_RANK", 0)), args)
@@ -234,7 +269,7 @@ def main(argv=None):
         os.environ.setdefault("MASTER_PORT", str(args.master_port))
         mp.spawn(train, nprocs=args.gpus, args=(args,))
     else:
-        train(0, args)
+        return train(0, args)
 
 
 if __name__ == "__main__":

@@ -273,6 +273,41 @@ __device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v,
   return pi;
 }
 
+// torch.optim.SGD single-tensor math in fp32 (grad.add(p, alpha=wd), buf.mul_(mu).add_(grad,
+// alpha=1-dampening), grad.add(buf, alpha=mu), p.add_(grad, alpha=-lr)), then the latent clamp.  Every
+// add(.., alpha=..) of torch is one fused multiply-add here: that form equals torch's CPU fp32 result bit
+// for bit, the separately rounded one does not.  Shared by bnn_sgd_clamp, bnn_sgd_clamp_multi
+// and the fused bnn_sgd_clamp_pack so all three produce bit-identical latent weights and buffers.
+struct SgdArgs {
+  const float* g;
+  float* buf;        // momentum_buffer; null exactly when mu == 0
+  float lr, mu, omd, wd, gscale;   // omd = (float)(1 - dampening), formed in double by the caller
+  int nesterov;
+  int first;         // no momentum buffer yet: buf = g (torch's clone(grad)), written without being read
+  int clamp;
+};
+
+__device__ __forceinline__ float sgd_elem(float p, float g, float& buf, const SgdArgs& a) {
+  // no mul+add contraction beyond the explicit fmaf: every kernel that inlines this rounds identically
+#pragma clang fp contract(off)
+  float gi = g * a.gscale;
+  if (a.wd != 0.f) gi = fmaf(a.wd, p, gi);
+  if (a.mu != 0.f) {
+    buf = a.first ? gi : fmaf(a.omd, gi, a.mu * buf);
+    gi = a.nesterov ? fmaf(a.mu, buf, gi) : buf;
+  }
+  float pi = fmaf(-a.lr, gi, p);
+  if (a.clamp) pi = fminf(fmaxf(pi, -1.f), 1.f);
+  return pi;
+}
+
+// Argument checks shared by the three bnn_sgd_* entries (host): torch's own constraints
+inline bool sgd_hyper_ok(float lr, float mu, float omd, float wd, int nesterov) {
+  if (!(lr >= 0.f) || !(mu >= 0.f) || !(wd >= 0.f) || !(omd == omd)) return false;
+  if (nesterov && (mu <= 0.f || omd != 1.f)) return false;
+  return true;
+}
+
 // Fused nn.Dropout(p) in front of a BatchNorm (mnist-dist2.py:69-70: fc3 -> drop -> bn3).  The
 // keep mask is a counter-based hash of (seed, element index), so forward statistics, forward
 // apply and both backward passes regenerate the same mask without storing it; kept elements are

@@ -55,13 +55,26 @@ struct ColAffine {
   int vec;             // all four 16-B aligned -> float4 parameter loads
 };
 
-// One 4-element run of a latent-weight row updated in place by Adam + clamp (ADAM mode of
-// sign_pack_tile_k: the fused latent update of mnist-dist2.py:131-137 that also writes the next
-// forward's ternary operands).  p, g, m, v share the row-major [M][K] layout; off = the row's
-// offset, columns k..k+3; sg = the new signs (0 beyond K).
-__device__ __forceinline__ void adam4(float* __restrict__ prow, int64_t off, int64_t k, int64_t K, bool vec,
-                                      const AdamArgs& a, int (&sg)[4]) {
-  if (vec && k + 4 <= K) {
+// The latent update a packing kernel fuses: an update policy U says which element runs and which state
+// streams it loads and stores, and is all that sign_pack_tile_k / adam_pack_fp4_k know of an optimizer.
+// The weight and the policy's streams share one row-major layout: prow = the weight's row, off = that
+// row's offset in the streams, k = the column.
+//   U::Args                  the kernel argument (gradient, state streams, hyper-parameters)
+//   U::resolve(a)            the arguments of this launch (device-step table lookups)
+//   U::run4(prow, off, k, a) updates the weights prow[k .. k+3] and their state in place (16-B aligned
+//                            float4 runs),
+//   U::run1(prow, off, k, a) or one element; both return the new weight(s)
+//   U::null(a), U::vec(a)    host: a needed pointer is null / every stream is 16-B aligned
+// NoUpdate marks the kernels that only pack.
+struct NoUpdate {
+  struct Args {};
+};
+
+// Adam + clamp (adam_elem): g, m, v read; m, v written -- 7 fp32 streams with p
+struct AdamUpdate {
+  using Args = AdamArgs;
+  static __device__ __forceinline__ Args resolve(const Args& a) { return adam_resolve(a); }
+  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a) {
     const float4 pv = *reinterpret_cast<const float4*>(prow + k);
     const float4 gv = *reinterpret_cast<const float4*>(a.g + off + k);
     float4 mv = *reinterpret_cast<const float4*>(a.m + off + k);
@@ -74,40 +87,90 @@ __device__ __forceinline__ void adam4(float* __restrict__ prow, int64_t off, int
     *reinterpret_cast<float4*>(prow + k) = np;
     *reinterpret_cast<float4*>(a.m + off + k) = mv;
     *reinterpret_cast<float4*>(a.v + off + k) = vv;
+    return np;
+  }
+  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a) {
+    float mm = a.m[off + k], vv = a.v[off + k];
+    const float np = adam_elem(prow[k], a.g[off + k], mm, vv, a);
+    prow[k] = np;
+    a.m[off + k] = mm;
+    a.v[off + k] = vv;
+    return np;
+  }
+  static bool null(const Args& a) { return !a.g || !a.m || !a.v; }
+  static bool vec(const Args& a) { return aligned16(a.g) && aligned16(a.m) && aligned16(a.v); }
+};
+
+// SGD + clamp (sgd_elem).  BUF = what happens to the momentum buffer: 0 none (momentum 0: g read, 3 fp32
+// streams with p), 1 written only (a parameter's first step: 4 streams), 2 read and written (5 streams).
+// A template parameter, not a branch on a.mu / a.first: the loads of an unrolled run stay together.
+template <int BUF>
+struct SgdUpdate {
+  using Args = SgdArgs;
+  static __device__ __forceinline__ Args resolve(const Args& a) { return a; }
+  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a) {
+    const float4 pv = *reinterpret_cast<const float4*>(prow + k);
+    const float4 gv = *reinterpret_cast<const float4*>(a.g + off + k);
+    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (BUF == 2) bv = *reinterpret_cast<const float4*>(a.buf + off + k);
+    float4 np;
+    np.x = sgd_elem(pv.x, gv.x, bv.x, a);
+    np.y = sgd_elem(pv.y, gv.y, bv.y, a);
+    np.z = sgd_elem(pv.z, gv.z, bv.z, a);
+    np.w = sgd_elem(pv.w, gv.w, bv.w, a);
+    *reinterpret_cast<float4*>(prow + k) = np;
+    if constexpr (BUF != 0) *reinterpret_cast<float4*>(a.buf + off + k) = bv;
+    return np;
+  }
+  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a) {
+    float bb = 0.f;
+    if constexpr (BUF == 2) bb = a.buf[off + k];
+    const float np = sgd_elem(prow[k], a.g[off + k], bb, a);
+    prow[k] = np;
+    if constexpr (BUF != 0) a.buf[off + k] = bb;
+    return np;
+  }
+  static bool null(const Args& a) { return !a.g || (BUF != 0 && !a.buf); }
+  static bool vec(const Args& a) { return aligned16(a.g) && (BUF == 0 || aligned16(a.buf)); }
+};
+
+// One 4-element run of a latent-weight row updated in place (the update mode of sign_pack_tile_k: the
+// fused latent update of mnist-dist2.py:131-137 that also writes the next forward's ternary operands).
+// p and the policy's streams share the row-major [M][K] layout; prow = the weight's row, off = the row's
+// offset, columns k..k+3; sg = the new signs (0 beyond K).
+template <class U>
+__device__ __forceinline__ void update4(float* __restrict__ prow, int64_t off, int64_t k, int64_t K, bool vec,
+                                        const typename U::Args& a, int (&sg)[4]) {
+  if (vec && k + 4 <= K) {
+    const float4 np = U::run4(prow, off, k, a);
     sg[0] = tsign(np.x), sg[1] = tsign(np.y), sg[2] = tsign(np.z), sg[3] = tsign(np.w);
   } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       sg[j] = 0;
-      if (k + j < K) {
-        float mm = a.m[off + k + j], vv = a.v[off + k + j];
-        const float np = adam_elem(prow[k + j], a.g[off + k + j], mm, vv, a);
-        prow[k + j] = np;
-        a.m[off + k + j] = mm;
-        a.v[off + k + j] = vv;
-        sg[j] = tsign(np);
-      }
+      if (k + j < K) sg[j] = tsign(U::run1(prow, off, k + j, a));
     }
   }
 }
 
 // One 64x64 tile of x -> ternary rows (q: FMT 0 = int8 per element, FMT 1 = FP4 e2m1 nibbles,
 // element k in byte k/2, low nibble for even k) and/or the transposed int8 tile (qt).
-// ADAM = 1: x is a latent weight updated in place first (adam4), and its new sign is packed.
-// PK_COAL 1: the non-Adam modes load whole 256-B row runs too (below); 0: 16 columns per lane
+// U != NoUpdate: x is a latent weight updated in place first (update4), and its new sign is packed.
+// PK_COAL 1: the pack-only modes load whole 256-B row runs too (below); 0: 16 columns per lane
 #ifndef PK_COAL
 #define PK_COAL 1
 #endif
-// ST = 1: the sign is the stochastic draw ssign() of element m * K + k with st's seed (never with ADAM);
+// ST = 1: the sign is the stochastic draw ssign() of element m * K + k with st's seed (never with an update);
 // padding elements stay 0.
-template <int FMT, int AFF = 0, int ADAM = 0, int ST = 0>
+template <int FMT, int AFF = 0, class U = NoUpdate, int ST = 0>
 __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict__ x, int64_t M,
                                                         int64_t K, int64_t ldx, int8_t* __restrict__ q,
                                                         int64_t ldq, int8_t* __restrict__ qt,
                                                         int64_t ldqt, int vec, ColAffine af = {},
                                                         int rtiles = 1, int64_t ntiles_y = 0,
-                                                        AdamArgs ad = {}, int qt4 = 0, Stoch st = {}) {
-  static_assert(!ST || (PK_COAL && !ADAM), "the stochastic draw is built into the row-run form only");
+                                                        typename U::Args ad = {}, int qt4 = 0, Stoch st = {}) {
+  constexpr bool UPD = !std::is_same<U, NoUpdate>::value;
+  static_assert(!ST || (PK_COAL && !UPD), "the stochastic draw is built into the row-run form only");
   // qt4 = 1: the transpose is written as FP4 nibbles (qt rows of ldqt BYTES, element m in byte
   // m/2), the B operand of the FP6 digit GEMMs (bnn_gemm6.hip); 2: the same nibbles in that GEMM's
   // panel layout ([K/512][ldqt/32][512][32 B], bnn_fp4_panelize); else int8 (rows of ldqt elements)
@@ -163,18 +226,18 @@ __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict_
   const int64_t m0 = ty * TILE;
   const int64_t m = m0 + r;
   int s[16];
-  if constexpr (ADAM) {
+  if constexpr (UPD) {
     // the update as whole 256-B row runs (16 lanes x float4 per row, 16 rows per pass: every wave
     // load instruction covers 4 full rows; lane = 16 consecutive floats moved 64-B pieces), the new
     // signs through the LDS tile into the row-run layout the packing below uses
-    const AdamArgs a = adam_resolve(ad);
+    const typename U::Args a = U::resolve(ad);
     const int ar = t >> 4, ac = (t & 15) * 4;
 #pragma unroll
     for (int pr = 0; pr < TILE / 16; ++pr) {
       const int rr = ar + 16 * pr;
       const int64_t mr = m0 + rr;
       int sg[4] = {0, 0, 0, 0};
-      if (mr < M) adam4(const_cast<float*>(x) + mr * ldx, mr * ldx, k0 + ac, K, vec, a, sg);
+      if (mr < M) update4<U>(const_cast<float*>(x) + mr * ldx, mr * ldx, k0 + ac, K, vec, a, sg);
 #pragma unroll
       for (int j = 0; j < 4; ++j) tile[rr][ac + j] = sg[j];
     }
@@ -184,7 +247,7 @@ __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict_
     if (qt != nullptr) __syncthreads();   // read before the transpose below rewrites the tile
   } else {
 #if PK_COAL
-    // as the ADAM mode: every wave load instruction covers 4 whole 256-B row runs (lane = 4
+    // as the update mode: every wave load instruction covers 4 whole 256-B row runs (lane = 4
     // consecutive columns), the signs go through the LDS tile into the 16-column layout below.
     // The same per-element arithmetic as the 16-column form (bit-identical).
     const int ar = t >> 4, ac = (t & 15) * 4;
@@ -408,16 +471,17 @@ __global__ __launch_bounds__(256) void bn_apply_pack_fp4_k(XIn xin, int64_t M, i
   }
 }
 
-// bnn_adam_clamp_pack on 256 x 256 tiles (the layout of bn_apply_pack_fp4_k): phase 1 updates
-// each 1-KiB row run of p with Adam + clamp (p, g, m, v read and p, m, v written as whole-line
+// bnn_adam_clamp_pack / bnn_sgd_clamp_pack on 256 x 256 tiles (the layout of bn_apply_pack_fp4_k): phase 1
+// updates each 1-KiB row run of p with the policy U (Adam: p, g, m, v read and p, m, v written as whole-line
 // float4 runs; sign_pack_tile_k's 64 x 64 tiles move 64-B pieces), packs the new signs into the FP4
 // rows and the LDS nibble image; phase 2 writes the FP4 transpose (plain or panel layout) exactly
-// as bn_apply_pack_fp4_k does.  Same element arithmetic (adam_elem) as sign_pack_tile_k<1, 0, 1>.
-__global__ __launch_bounds__(256) void adam_pack_fp4_k(float* __restrict__ p, AdamArgs a0, int64_t N, int64_t K,
-                                                       uint8_t* __restrict__ q, int64_t ldq,
+// as bn_apply_pack_fp4_k does.  Same element arithmetic (U::run4) as sign_pack_tile_k<1, 0, U>.
+template <class U>
+__global__ __launch_bounds__(256) void adam_pack_fp4_k(float* __restrict__ p, typename U::Args a0, int64_t N,
+                                                       int64_t K, uint8_t* __restrict__ q, int64_t ldq,
                                                        uint8_t* __restrict__ qt, int64_t ldqt, int64_t pnks) {
   __shared__ uint32_t img[AP_T * AP_LD];
-  const AdamArgs a = adam_resolve(a0);
+  const typename U::Args a = U::resolve(a0);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int64_t k0 = (int64_t)blockIdx.x * AP_T, m0 = (int64_t)blockIdx.y * AP_T;
   const int64_t cb = k0 + 4 * lane;
@@ -426,18 +490,7 @@ __global__ __launch_bounds__(256) void adam_pack_fp4_k(float* __restrict__ p, Ad
   for (int i = 0; i < AP_T / 4; ++i) {
     const int r = wave + 4 * i;
     const int64_t off = (m0 + r) * K + cb;            // N % 256 == 0: every row is in range
-    const float4 pv = *reinterpret_cast<const float4*>(p + off);
-    const float4 gv = *reinterpret_cast<const float4*>(a.g + off);
-    float4 mv = *reinterpret_cast<const float4*>(a.m + off);
-    float4 vv = *reinterpret_cast<const float4*>(a.v + off);
-    float4 np;
-    np.x = adam_elem(pv.x, gv.x, mv.x, vv.x, a);
-    np.y = adam_elem(pv.y, gv.y, mv.y, vv.y, a);
-    np.z = adam_elem(pv.z, gv.z, mv.z, vv.z, a);
-    np.w = adam_elem(pv.w, gv.w, mv.w, vv.w, a);
-    *reinterpret_cast<float4*>(p + off) = np;
-    *reinterpret_cast<float4*>(a.m + off) = mv;
-    *reinterpret_cast<float4*>(a.v + off) = vv;
+    const float4 np = U::run4(p + off, off, 0, a);
     const uint32_t code = fp4_code(tsign(np.x)) | (fp4_code(tsign(np.y)) << 4) | (fp4_code(tsign(np.z)) << 8) |
                           (fp4_code(tsign(np.w)) << 12);
     *reinterpret_cast<uint16_t*>(q + (m0 + r) * ldq + k0 / 2 + 2 * lane) = (uint16_t)code;
@@ -990,8 +1043,8 @@ static int sign_pack_i8_impl(const char* name, const float* x, int64_t M, int64_
     return kErrInval;
   }
   if (st)
-    hipLaunchKernelGGL((sign_pack_tile_k<0, 0, 0, 1>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x,
-                       M, K, ldx, q, ldq, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0, AdamArgs{}, 0, *st);
+    hipLaunchKernelGGL((sign_pack_tile_k<0, 0, NoUpdate, 1>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x,
+                       M, K, ldx, q, ldq, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0, NoUpdate::Args{}, 0, *st);
   else
     hipLaunchKernelGGL(sign_pack_tile_k<0>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x,
                        M, K, ldx, q, ldq, qt, ldqt, vec);
@@ -1062,13 +1115,13 @@ static int sign_pack_fp4_impl(const char* name, const float* x, int64_t M, int64
     return kErrInval;
   }
   if (st)
-    hipLaunchKernelGGL((sign_pack_tile_k<1, 0, 0, 1>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x,
+    hipLaunchKernelGGL((sign_pack_tile_k<1, 0, NoUpdate, 1>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x,
                        M, K, ldx, reinterpret_cast<int8_t*>(q4), ldq4, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0,
-                       AdamArgs{}, qt_fmt, *st);
+                       NoUpdate::Args{}, qt_fmt, *st);
   else
     hipLaunchKernelGGL(sign_pack_tile_k<1>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), x, M, K,
                        ldx, reinterpret_cast<int8_t*>(q4), ldq4, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0,
-                       AdamArgs{}, qt_fmt);
+                       NoUpdate::Args{}, qt_fmt);
   return check_launch(name);
 }
 
@@ -1133,23 +1186,22 @@ BNN_API int bnn_adam_pack_set_tile256(int32_t on) {
   return 0;
 }
 
-static int adam_clamp_pack_impl(float* p, const AdamArgs& a, int64_t N, int64_t K, int32_t fmt, void* q,
-                                int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt, void* stream) {
-  const float* grad = a.g;
-  const float* exp_avg = a.m;
-  const float* exp_avg_sq = a.v;
-  if (!p || !grad || !exp_avg || !exp_avg_sq || N <= 0 || K <= 0 || (fmt != 0 && fmt != 1) || (!q && !qt)) {
-    set_error("bnn_adam_clamp_pack: bad arguments (N=%lld K=%lld fmt=%d)", (long long)N, (long long)K, fmt);
+// the fused update + pack of policy U (AdamUpdate / SgdUpdate): one argument contract and one dispatch
+template <class U>
+static int update_pack_impl(const char* name, float* p, const typename U::Args& a, int64_t N, int64_t K,
+                            int32_t fmt, void* q, int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt,
+                            void* stream) {
+  if (!p || U::null(a) || N <= 0 || K <= 0 || (fmt != 0 && fmt != 1) || (!q && !qt)) {
+    set_error("%s: bad arguments (N=%lld K=%lld fmt=%d)", name, (long long)N, (long long)K, fmt);
     return kErrInval;
   }
   if (q && (fmt == 0 ? (ldq % TILE != 0 || ldq < round_up(K, TILE))
                      : (ldq % 128 != 0 || 2 * ldq < round_up(K, 256))) ) {
-    set_error("bnn_adam_clamp_pack: ldq=%lld does not cover K=%lld in fmt %d", (long long)ldq, (long long)K, fmt);
+    set_error("%s: ldq=%lld does not cover K=%lld in fmt %d", name, (long long)ldq, (long long)K, fmt);
     return kErrInval;
   }
   if ((q && !aligned16(q)) || !qt_ok(qt, N, ldqt, qt_fmt)) {
-    set_error("bnn_adam_clamp_pack: ldqt=%lld does not cover N=%lld in qt_fmt %d", (long long)ldqt, (long long)N,
-              qt_fmt);
+    set_error("%s: ldqt=%lld does not cover N=%lld in qt_fmt %d", name, (long long)ldqt, (long long)N, qt_fmt);
     return kErrInval;
   }
   // every element of p is visited exactly once: the grid spans K (and the q padding) x N (and
@@ -1157,26 +1209,26 @@ static int adam_clamp_pack_impl(float* p, const AdamArgs& a, int64_t N, int64_t 
   const int64_t gx = q ? (fmt == 0 ? ldq : 2 * ldq) / TILE : (K + TILE - 1) / TILE;
   const int64_t gy = qt ? qt_tiles(ldqt, qt_fmt) : (N + TILE - 1) / TILE;
   if (gy > 65535 || gx > 0x7fffffff) {
-    set_error("bnn_adam_clamp_pack: N too large for one launch (%lld)", (long long)N);
+    set_error("%s: N too large for one launch (%lld)", name, (long long)N);
     return kErrInval;
   }
-  const int vec = aligned16(p) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) && (K % 4 == 0);
+  const int vec = aligned16(p) && U::vec(a) && (K % 4 == 0);
   if (fmt == 1 && q && qt && (qt_fmt == 1 || qt_fmt == 2) && vec && N % AP_T == 0 && K % AP_T == 0 &&
       2 * ldq == K && 2 * ldqt == N &&
       (ADAM_TILE256 == 2 || (ADAM_TILE256 == 1 && (K / AP_T) * (N / AP_T) >= ADAM_T256_MIN_TILES))) {
     // whole 256 x 256 tiles, no padding: the 1-KiB-run form
-    hipLaunchKernelGGL(adam_pack_fp4_k, dim3((unsigned)(K / AP_T), (unsigned)(N / AP_T)), dim3(256), 0, S(stream), p,
+    hipLaunchKernelGGL(adam_pack_fp4_k<U>, dim3((unsigned)(K / AP_T), (unsigned)(N / AP_T)), dim3(256), 0, S(stream), p,
                        a, N, K, reinterpret_cast<uint8_t*>(q), ldq, reinterpret_cast<uint8_t*>(qt), ldqt,
                        qt_fmt == 2 ? ldqt / 32 : (int64_t)0);
-    return check_launch("bnn_adam_clamp_pack");
+    return check_launch(name);
   }
   if (fmt == 0)
-    hipLaunchKernelGGL((sign_pack_tile_k<0, 0, 1>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), p, N,
+    hipLaunchKernelGGL((sign_pack_tile_k<0, 0, U>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), p, N,
                        K, K, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0, a, qt_fmt);
   else
-    hipLaunchKernelGGL((sign_pack_tile_k<1, 0, 1>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), p, N,
+    hipLaunchKernelGGL((sign_pack_tile_k<1, 0, U>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, S(stream), p, N,
                        K, K, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, ColAffine{}, 1, (int64_t)0, a, qt_fmt);
-  return check_launch("bnn_adam_clamp_pack");
+  return check_launch(name);
 }
 
 BNN_API int bnn_adam_clamp_pack(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t N,
@@ -1190,7 +1242,7 @@ BNN_API int bnn_adam_clamp_pack(float* p, const float* grad, float* exp_avg, flo
   float step_size, bc2_sqrt;
   adam_bias_correction(lr, beta1, beta2, step, &step_size, &bc2_sqrt);
   const AdamArgs a{grad, exp_avg, exp_avg_sq, beta1, beta2, eps, step_size, bc2_sqrt, grad_scale, clamp};
-  return adam_clamp_pack_impl(p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
+  return update_pack_impl<AdamUpdate>("bnn_adam_clamp_pack", p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
 }
 
 BNN_API int bnn_adam_clamp_pack_sched(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t N,
@@ -1204,7 +1256,22 @@ BNN_API int bnn_adam_clamp_pack_sched(float* p, const float* grad, float* exp_av
   AdamArgs a{grad, exp_avg, exp_avg_sq, beta1, beta2, eps, 0.f, 1.f, grad_scale, clamp};
   a.sched = sched;
   a.ctr = ctr;
-  return adam_clamp_pack_impl(p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
+  return update_pack_impl<AdamUpdate>("bnn_adam_clamp_pack", p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
+}
+
+BNN_API int bnn_sgd_clamp_pack(float* p, const float* grad, float* buf, int64_t N, int64_t K, float lr,
+                               float momentum, float omd, float weight_decay, int32_t nesterov, int32_t first,
+                               float grad_scale, int32_t clamp, int32_t fmt, void* q, int64_t ldq, int8_t* qt,
+                               int64_t ldqt, int32_t qt_fmt, void* stream) {
+  if ((momentum != 0.f && !buf) || !sgd_hyper_ok(lr, momentum, omd, weight_decay, nesterov)) {
+    set_error("bnn_sgd_clamp_pack: bad hyper-parameters or no momentum buffer");
+    return kErrInval;
+  }
+  const SgdArgs a{grad, buf, lr, momentum, omd, weight_decay, grad_scale, nesterov != 0, first != 0, clamp};
+  const char* name = "bnn_sgd_clamp_pack";
+  if (momentum == 0.f) return update_pack_impl<SgdUpdate<0>>(name, p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
+  if (first) return update_pack_impl<SgdUpdate<1>>(name, p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
+  return update_pack_impl<SgdUpdate<2>>(name, p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
 }
 
 static int sign_f32_impl(const char* name, const float* x, float* y, int64_t n, const Stoch* st, void* stream) {
@@ -1353,17 +1420,17 @@ static int bn_apply_pack_impl(const char* name, const float* x, int64_t M, int64
   const int rt = (gx * ((gy + 3) / 4) >= 8192) ? 4 : 1;
   const unsigned gyr = (unsigned)((gy + rt - 1) / rt);
   if (st && fmt == 1)
-    hipLaunchKernelGGL((sign_pack_tile_k<1, 1, 0, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
-                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, AdamArgs{}, qt_fmt, *st);
+    hipLaunchKernelGGL((sign_pack_tile_k<1, 1, NoUpdate, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
+                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, NoUpdate::Args{}, qt_fmt, *st);
   else if (st)
-    hipLaunchKernelGGL((sign_pack_tile_k<0, 1, 0, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
-                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, AdamArgs{}, qt_fmt, *st);
+    hipLaunchKernelGGL((sign_pack_tile_k<0, 1, NoUpdate, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
+                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, NoUpdate::Args{}, qt_fmt, *st);
   else if (fmt == 1)
     hipLaunchKernelGGL((sign_pack_tile_k<1, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
-                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, AdamArgs{}, qt_fmt);
+                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, NoUpdate::Args{}, qt_fmt);
   else
     hipLaunchKernelGGL((sign_pack_tile_k<0, 1>), dim3((unsigned)gx, gyr), dim3(256), 0, S(stream), x, M,
-                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, AdamArgs{}, qt_fmt);
+                       C, C, reinterpret_cast<int8_t*>(q), ldq, qt, ldqt, vec, af, rt, gy, NoUpdate::Args{}, qt_fmt);
   return check_launch(name);
 }
 

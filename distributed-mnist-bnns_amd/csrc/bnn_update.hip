@@ -180,6 +180,88 @@ BNN_API int bnn_adam_clamp_multi(int32_t count, float* const* p, const float* co
   return check_launch("bnn_adam_clamp_multi");
 }
 
+// torch.optim.SGD + clamp (math: sgd_elem in bnn_common.h): 5 fp32 streams (p, g, buf read; p, buf
+// written), 2 + 1 without momentum.  Nothing depends on the step count, so a captured step replays
+// these launches as they are.
+namespace bnn {
+namespace {
+
+// one tensor's grid-stride pass; rd / wr (uniform): the momentum buffer is read / written
+__device__ __forceinline__ void sgd_span(float* __restrict__ p, int64_t n, const SgdArgs& a) {
+  const bool wr = a.mu != 0.f, rd = wr && !a.first;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float bi = rd ? a.buf[i] : 0.f;
+    p[i] = sgd_elem(p[i], a.g[i], bi, a);
+    if (wr) a.buf[i] = bi;
+  }
+}
+
+__global__ __launch_bounds__(256) void sgd_clamp_k(float* __restrict__ p, int64_t n, SgdArgs a) { sgd_span(p, n, a); }
+
+struct SgdMulti {
+  float* p[ADAM_MT];
+  const float* g[ADAM_MT];
+  float* buf[ADAM_MT];
+  int64_t n[ADAM_MT];
+  int first[ADAM_MT], clamp[ADAM_MT];
+  float lr, mu, omd, wd, gscale;
+  int nesterov;
+};
+
+__global__ __launch_bounds__(256) void sgd_clamp_multi_k(SgdMulti sm) {
+  const int j = blockIdx.y;
+  const SgdArgs a{sm.g[j], sm.buf[j], sm.lr, sm.mu, sm.omd, sm.wd, sm.gscale, sm.nesterov, sm.first[j], sm.clamp[j]};
+  sgd_span(sm.p[j], sm.n[j], a);
+}
+
+}  // namespace
+}  // namespace bnn
+
+BNN_API int bnn_sgd_clamp(float* p, const float* grad, float* buf, int64_t n, float lr, float momentum, float omd,
+                          float weight_decay, int32_t nesterov, int32_t first, float grad_scale, int32_t clamp,
+                          void* stream) {
+  if (n < 0 || (n > 0 && (!p || !grad)) || (momentum != 0.f && !buf) ||
+      !sgd_hyper_ok(lr, momentum, omd, weight_decay, nesterov)) {
+    set_error("bnn_sgd_clamp: bad arguments");
+    return kErrInval;
+  }
+  if (n == 0) return 0;
+  const SgdArgs a{grad, buf, lr, momentum, omd, weight_decay, grad_scale, nesterov != 0, first != 0, clamp};
+  hipLaunchKernelGGL(sgd_clamp_k, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, n, a);
+  return check_launch("bnn_sgd_clamp");
+}
+
+BNN_API int bnn_sgd_clamp_multi(int32_t count, float* const* p, const float* const* grad, float* const* buf,
+                                const int64_t* n, const int32_t* first, const int32_t* clamp, float lr,
+                                float momentum, float omd, float weight_decay, int32_t nesterov, float grad_scale,
+                                void* stream) {
+  if (count < 0 || count > ADAM_MT || (count > 0 && (!p || !grad || !n || !first || !clamp)) ||
+      (count > 0 && momentum != 0.f && !buf) || !sgd_hyper_ok(lr, momentum, omd, weight_decay, nesterov)) {
+    set_error("bnn_sgd_clamp_multi: bad arguments (count %d, at most %d tensors per launch)", count, ADAM_MT);
+    return kErrInval;
+  }
+  SgdMulti sm{};
+  int64_t nmax = 0;
+  int k = 0;
+  for (int j = 0; j < count; ++j) {
+    if (n[j] < 0 || (n[j] > 0 && (!p[j] || !grad[j] || (momentum != 0.f && !buf[j])))) {
+      set_error("bnn_sgd_clamp_multi: bad tensor %d", j);
+      return kErrInval;
+    }
+    if (n[j] == 0) continue;
+    sm.p[k] = p[j], sm.g[k] = grad[j], sm.buf[k] = momentum != 0.f ? buf[j] : nullptr, sm.n[k] = n[j];
+    sm.first[k] = first[j] != 0, sm.clamp[k] = clamp[j];
+    nmax = std::max(nmax, n[j]);
+    ++k;
+  }
+  if (k == 0) return 0;
+  sm.lr = lr, sm.mu = momentum, sm.omd = omd, sm.wd = weight_decay, sm.gscale = grad_scale, sm.nesterov = nesterov != 0;
+  const unsigned gx = (unsigned)std::min<int64_t>((nmax + 255) / 256, 1024);
+  hipLaunchKernelGGL(sgd_clamp_multi_k, dim3(gx, (unsigned)k), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), sm);
+  return check_launch("bnn_sgd_clamp_multi");
+}
+
 BNN_API int bnn_adam_schedule(float lr, float beta1, float beta2, int64_t step0, int64_t n, float* out) {
   if (!out || n < 0 || step0 < 1) {
     set_error("bnn_adam_schedule: bad arguments");

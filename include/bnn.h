@@ -885,6 +885,37 @@ int bnn_adam_clamp_pack_sched(float* p, const float* grad, float* exp_avg, float
 int bnn_counter_add(int64_t* ctr, int64_t v, bnn_stream_t stream);
 int bnn_set_seed_counter(const int64_t* ctr);
 
+/* ---------------------------------------------------------------- fused latent SGD
+ * torch.optim.SGD (mnist.py / mnist-dist.py / mnist-mixed.py / mnist-distributed-BNNS2.py) on the latent
+ * weight, then, if clamp != 0, p <- clamp(p, -1, 1), in one pass.  Per element, with one fused
+ * multiply-add wherever torch has an add(.., alpha=..):
+ *   g = grad * grad_scale;  if weight_decay != 0: g = fma(weight_decay, p, g)
+ *   if momentum != 0:       buf = first ? g : fma(omd, g, momentum * buf)
+ *                           g = nesterov ? fma(momentum, buf, g) : buf
+ *   p = fma(-lr, g, p)
+ * which equals torch's CPU fp32 result bit for bit.  omd = (float)(1 - dampening), formed in double by the
+ * caller (torch's alpha).  first != 0: the parameter has no momentum buffer yet -- buf is written (= g,
+ * torch's clone(grad)) without being read.  buf may be NULL exactly when momentum == 0 (p, grad read; p
+ * written).  Nothing depends on a step count: a captured step replays these launches unchanged.
+ * BNN_EINVAL: null pointers with n > 0, buf == NULL with momentum != 0, nesterov with momentum <= 0 or
+ * omd != 1, negative lr / momentum / weight_decay, count > 16, the pack entry's ldq / ldqt conditions. */
+int bnn_sgd_clamp(float* p, const float* grad, float* buf, int64_t n, float lr, float momentum, float omd,
+                  float weight_decay, int32_t nesterov, int32_t first, float grad_scale, int32_t clamp,
+                  bnn_stream_t stream);
+/* bnn_sgd_clamp over up to 16 tensors in one launch (host arrays of `count` device pointers, element
+ * counts, first and clamp flags; buf may be NULL when momentum == 0); bit-identical per tensor. */
+int bnn_sgd_clamp_multi(int32_t count, float* const* p, const float* const* grad, float* const* buf,
+                        const int64_t* n, const int32_t* first, const int32_t* clamp, float lr, float momentum,
+                        float omd, float weight_decay, int32_t nesterov, float grad_scale, bnn_stream_t stream);
+/* bnn_sgd_clamp fused with the next forward's weight packing: the contract of bnn_adam_clamp_pack (p
+ * [N][K] row-major, grad and buf alike; q / qt / fmt / qt_fmt / ldq / ldqt as there; the same kernels
+ * with the SGD element, the same bnn_adam_pack_set_tile256 hook).  p, buf bit-identical to bnn_sgd_clamp;
+ * q, qt bit-identical to sign-packing the updated weight, zero padding included. */
+int bnn_sgd_clamp_pack(float* p, const float* grad, float* buf, int64_t N, int64_t K, float lr, float momentum,
+                       float omd, float weight_decay, int32_t nesterov, int32_t first, float grad_scale,
+                       int32_t clamp, int32_t fmt, void* q, int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt,
+                       bnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
