@@ -1,188 +1,117 @@
-"""ctypes binding of libbnn.so (C ABI declared in include/bnn.h).
+"""ctypes binding of libbnn.so, derived from the C ABI's one declaration, include/bnn.h.
 
-The library is the product: there is no CPU fallback.  Loading fails loudly when the .so is
-missing, and every op raises when handed a non-ROCm tensor.
+The library is the product: there is no CPU fallback.  Loading fails loudly when the .so or the
+header is missing, and every op raises when handed a non-ROCm tensor.  Pointer parameters take
+tensors directly and check their dtype against the pointee type the header declares.
 """
 import ctypes
 import os
+import re
 
-import torch  # noqa: F401  -- load torch's HIP runtime first so libbnn binds to the same one
+import torch  # load torch's HIP runtime first so libbnn binds to the same one
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libbnn.so")
+DEFAULT_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "bnn.h")
 
-P = ctypes.c_void_p
-I64 = ctypes.c_int64
-I32 = ctypes.c_int32
-F32 = ctypes.c_float
-U64 = ctypes.c_uint64
+_RESTYPES = {"int": ctypes.c_int32, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
+_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "float": ctypes.c_float, "double": ctypes.c_double, "bnn_stream_t": ctypes.c_void_p}
 
-# name -> (restype, argtypes); must match include/bnn.h
-SIGNATURES = {
-    "bnn_version": (I32, []),
-    "bnn_last_error": (ctypes.c_char_p, []),
-    "bnn_sign_pack_i8": (I32, [P, I64, I64, I64, P, I64, P, I64, P]),
-    "bnn_sign_pack_fp4": (I32, [P, I64, I64, I64, P, I64, P, I64, I32, P]),
-    "bnn_sign_pack_fp4_out": (I32, [P, I64, I64, P, I64, P, I64, I32, P, P]),
-    "bnn_sign_f32": (I32, [P, P, I64, P]),
-    "bnn_binarize_stoch_f32": (I32, [P, P, I64, U64, P]),
-    "bnn_stoch_pack_i8": (I32, [P, I64, I64, I64, P, I64, P, I64, U64, P]),
-    "bnn_stoch_pack_fp4": (I32, [P, I64, I64, I64, P, I64, P, I64, I32, U64, I32, P]),
-    "bnn_stoch_pack_fp4_out": (I32, [P, I64, I64, P, I64, P, I64, I32, P, U64, I32, P]),
-    "bnn_bn_apply_pack_stoch": (I32, [P, I64, I64, P, P, P, P, P, I32, P, I64, P, I64, I32, U64, I32, P]),
-    "bnn_bn_apply_pack_stoch_i16": (I32, [P, P, I64, I64, P, P, P, P, P, P, I64, P, I64, I32, U64, P]),
-    "bnn_bn_apply_pack_stoch_s20": (I32, [P, P, P, F32, I64, I64, P, P, P, P, P, P, I64, P, I64, I32, U64, P]),
-    "bnn_sign_pack_bits": (I32, [P, I64, I64, I64, P, P, I64, P]),
-    "bnn_quant_rows": (I32, [P, I64, I64, I64, P, I64, I64, P, P]),
-    "bnn_quant_cols_workspace": (I64, [I64, I64]),
-    "bnn_quant_cols_t": (I32, [P, I64, I64, I64, P, I64, I64, P, P, P, P]),
-    "bnn_quant_cols_t_dsum": (I32, [P, I64, I64, I64, P, I64, I64, P, P, P, P, P]),
-    "bnn_gemm_i8": (I32, [P, I64, I64, I32, P, I64, I64, I32, P, P, P, P, I64, I64, I64, I64, P]),
-    "bnn_gemm_i8_affine": (I32, [P, I64, I64, I32, P, I64, I64, I32, P, P, P, P, P, ctypes.c_double, P, I64,
-                                 I64, I64, I64, P]),
-    "bnn_gemm_i8_bnstats_chunk": (I64, [I64, I64]),
-    "bnn_gemm_fp4_bnstats_chunk": (I64, [I64, I64, I64]),
-    "bnn_gemm_fp4_bnstats": (I32, [P, I64, P, I64, P, P, P, I64, P, I64, I64, I64, F32, ctypes.c_uint64, P, I64,
-                                   P]),
-    "bnn_gemm_i8_bnstats_ok": (I32, [I64, I64, I64, I64, I64]),
-    "bnn_gemm_i8_s20_ok": (I32, [I64, I64, I64, I64, ctypes.c_double]),
-    "bnn_gemm_i8_affine_bnstats_s20": (I32, [P, I64, P, I64, P, ctypes.c_double, I64, P, P, I64, I64, I64, I64, P,
-                                             I64, P, P, P]),
-    "bnn_bn_apply_pack_s20": (I32, [P, P, P, F32, I64, I64, P, P, P, P, P, P, I64, P, I64, I32, P]),
-    "bnn_bn_bwd_i8cols_s20": (I32, [P, P, P, F32, P, I64, I64, P, P, P, P, P, I32, P, P, P, I64, I64, P, P, P, P,
-                                    P]),
-    "bnn_bn_bwd_i8cols_s20_pre": (I32, [P, P, P, F32, P, I64, I64, P, P, P, P, P, I32, P, P, P, I64, I64, P, P, P,
-                                        P, P]),
-    "bnn_gemm_i8_affine_bnstats": (I32, [P, I64, P, I64, P, P, P, ctypes.c_double, P, I64, I64, I64, I64, P, I64,
-                                         P]),
-    "bnn_linear_nsmall_workspace": (I64, [I64, I64, I64]),
-    "bnn_linear_nsmall_fwd": (I32, [P, I64, I64, P, P, I64, P, P]),
-    "bnn_linear_nsmall_bwd": (I32, [P, P, P, I64, I64, I64, P, P, P, P, I64, P]),
-    "bnn_col_sums_narrow": (I32, [P, I64, I64, I64, P, P]),
-    "bnn_cross_entropy_ok": (I32, [I64]),
-    "bnn_cross_entropy_workspace": (I64, [I64]),
-    "bnn_cross_entropy_fwd": (I32, [P, P, I64, I64, I64, P, P, I64, P]),
-    "bnn_cross_entropy_bwd": (I32, [P, P, I64, I64, I64, P, P, P, P]),
-    "bnn_hinge_ok": (I32, [I64]),
-    "bnn_hinge_workspace": (I64, [I64, I64]),
-    "bnn_hinge_fwd": (I32, [P, P, P, I64, I64, F32, I32, P, P, I64, P]),
-    "bnn_hinge_bwd": (I32, [P, P, P, I64, I64, F32, I32, P, P, P]),
-    "bnn_unit_to_pixels": (I32, [P, I64, P, P, P]),
-    "bnn_pixels_pack": (I32, [P, I64, I64, I64, P, I64, P, I64, P]),
-    "bnn_row_sums": (I32, [P, I64, I64, I64, P, P]),
-    "bnn_gemm_fp4": (I32, [P, I64, P, I64, P, P, I64, I64, I64, I64, P]),
-    "bnn_gemm_fp4_i16": (I32, [P, I64, P, I64, P, I64, I64, I64, I64, P]),
-    "bnn_gemm_fp4_bnsign": (I32, [P, I64, P, I64, P, P, P, P, P, P, I64, I64, I64, I64, P]),
-    "bnn_gemm_i8_affine_bnsign": (I32, [P, I64, P, I64, P, P, P, ctypes.c_double, P, P, P, P, P, I64, I64, I64, I64,
-                                        P]),
-    "bnn_gemm_set_variant": (I32, [I32]),
-    "bnn_gemm_set_raster": (I32, [I32]),
-    "bnn_adam_pack_set_tile256": (I32, [I32]),
-    "bnn_gemm_i8_kernel": (ctypes.c_char_p, [I32, I32, I64, I64, I64]),
-    "bnn_gemm_xnor": (I32, [P, P, I64, P, P, I64, P, P, I64, I64, I64, I64, P]),
-    "bnn_conv2d_fwd": (I32, [P, I32, P, P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, P]),
-    "bnn_conv2d_bwd_data": (I32, [P, P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, P]),
-    "bnn_conv2d_bwd_filter_workspace": (I64, [I64, I64, I64, I64, I64, I32]),
-    "bnn_conv2d_bwd_filter": (I32, [P, P, I32, P, P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32,
-                                    I32, P]),
-    "bnn_conv_set_mfma": (I32, [I32]),
-    "bnn_conv_set_c1_filter": (I32, [I32]),
-    "bnn_conv_set_popc": (I32, [I32]),
-    "bnn_bn2d_set_rows": (I32, [I32]),
-    "bnn_bn2d_bwd_stats_q": (I32, [P, P, I32, P, I64, I64, I64, I64, P, P, P, P, I32, I32, P, P, P, P, P, P]),
-    "bnn_conv2d_bwd_filter_bn_ok": (I32, [I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32]),
-    "bnn_conv2d_bwd_filter_bn": (I32, [P, P, I32, P, P, P, P, P, P, P, F32, I32, P, I32, P, P, P, I64, I64, I64, I64,
-                                       I64, I64, I64, I32, I32, I32, I32, P]),
-    "bnn_conv_bf3_plan": (I32, [I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, P]),
-    "bnn_conv_kernel": (ctypes.c_char_p, [I32, I32, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32]),
-    "bnn_conv_kernel_at": (ctypes.c_char_p, [I32, I32]),
-    "bnn_bn_workspace": (I64, [I64, I64]),
-    "bnn_bn_plan": (I32, [I64, I64, ctypes.POINTER(I64)]),
-    "bnn_bn2d_plan": (I32, [I64, I64, I64, I64, I32, ctypes.POINTER(I64)]),
-    "bnn_bn_fwd_train": (I32, [P, I64, I64, P, P, P, P, F32, F32, P, P, P, P, I32, P, P]),
-    "bnn_bn_fwd_final_parts": (I32, [P, I64, I64, I64, I64, P, P, F32, F32, P, P, P, P]),
-    "bnn_bn_fwd_eval": (I32, [P, I64, I64, P, P, P, P, F32, P, I32, P, P]),
-    "bnn_bn_bwd": (I32, [P, P, I64, I64, P, P, P, P, P, I32, P, P, P, P, P]),
-    "bnn_bn_bwd_eval": (I32, [P, P, I64, I64, P, P, P, P, I32, P, P, P, P, P]),
-    "bnn_bn2d_workspace": (I64, [I64, I64]),
-    "bnn_bn2d_fwd_train": (I32, [P, I64, I64, I64, I64, P, P, P, P, F32, F32, P, P, P, I32, I32, P, P]),
-    "bnn_bn2d_fwd_eval": (I32, [P, I64, I64, I64, I64, P, P, P, P, F32, P, I32, I32, P, P]),
-    "bnn_bn2d_bwd": (I32, [P, P, I64, I64, I64, I64, P, P, P, P, I32, I32, P, P, P, P, P]),
-    "bnn_bn2d_bwd_eval": (I32, [P, P, I64, I64, I64, I64, P, P, P, P, I32, I32, P, P, P, P, P]),
-    "bnn_bn2d_fwd_train_q": (I32, [P, P, I32, I64, I64, I64, I64, P, P, P, P, F32, F32, P, P, P, I32, I32, P, P]),
-    "bnn_bn2d_bwd_q": (I32, [P, P, I32, P, I64, I64, I64, I64, P, P, P, P, I32, I32, P, P, P, P, P]),
-    "bnn_conv2d_fwd_q": (I32, [P, P, P, I32, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, P]),
-    "bnn_conv2d_fwd_q_ok": (I32, [I32, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32]),
-    "bnn_conv2d_fwd_bnsign_pool_ok": (I32, [I32, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32]),
-    "bnn_conv2d_fwd_bnsign_pool": (I32, [P, I32, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32,
-                                         I32, I32, P]),
-    "bnn_conv2d_fwd_bn_pool_linear_ok": (I32, [I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, I32]),
-    "bnn_conv2d_fwd_bn_pool_linear": (I32, [P, P, P, P, P, P, P, P, P, I32, P, I64, I64, I64, I64, I64, I64, I64, I32,
-                                            I32, I32, I32, P]),
-    "bnn_bn_dropout_fwd_train": (I32, [P, I64, I64, P, P, P, P, F32, F32, P, P, P, P, I32, F32, U64, P, P, P]),
-    "bnn_dropout_keep_bits_bytes": (I64, [I64, I64]),
-    "bnn_bn_set_head_reduce_cols": (I32, [I32]),
-    "bnn_gemm_i8_bnstats_set_tile": (I32, [I32]),
-    "bnn_bn_dropout_bwd": (I32, [P, P, I64, I64, P, P, P, P, P, I32, F32, U64, P, P, P, P, P]),
-    "bnn_bn_bwd_q6": (I32, [P, P, I64, I64, P, P, P, P, P, I32, F32, U64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "bnn_dropout_mask": (I32, [I64, F32, U64, P, P]),
-    "bnn_bn_head_workspace": (I64, [I64, I64, I32]),
-    "bnn_bn_head_fwd": (I32, [P, I64, I64, P, P, P, P, P, F32, U64, P, P, I32, P, P, P]),
-    "bnn_bn_head_eval": (I32, [P, P, P, I64, I64, P, P, P, P, P, I32, P, P, P]),
-    "bnn_bn_head_bwd_q6": (I32, [P, P, P, I32, I64, I64, P, P, P, P, P, F32, U64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "bnn_bn_apply_pack": (I32, [P, I64, I64, P, P, P, P, P, I32, P, I64, P, I64, I32, P]),
-    "bnn_bn_fwd_train_i16": (I32, [P, P, I64, I64, P, P, P, P, F32, F32, P, P, P, F32, U64, P, P, P]),
-    "bnn_bn_apply_pack_i16": (I32, [P, P, I64, I64, P, P, P, P, P, P, I64, P, I64, I32, P]),
-    "bnn_bn_bwd_q6_i16": (I32, [P, P, P, I64, I64, P, P, P, P, P, I32, F32, U64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "bnn_bn_head_fwd_i16": (I32, [P, P, I64, I64, P, P, P, P, P, F32, U64, P, P, I32, P, P, P]),
-    "bnn_bn_head_bwd_q6_i16": (I32, [P, P, P, P, I32, I64, I64, P, P, P, P, P, F32, U64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "bnn_bn_bwd_i8cols_workspace": (I64, [I64, I64]),
-    "bnn_bn_bwd_i8cols": (I32, [P, P, I64, I64, P, P, P, P, P, I32, P, P, P, I64, I64, P, P, P, P, P]),
-    "bnn_bn_bwd_i8cols_pre": (I32, [P, P, I64, I64, P, P, P, P, P, I32, P, P, P, I64, I64, P, P, P, P, P]),
-    "bnn_bn_bwd_stats_pre": (I32, [P, I64, I64, I64, I32, P, P, P, P, P, P, P, P]),
-    "bnn_bn_bwd_q6_pre": (I32, [P, P, I64, I64, P, P, P, P, P, I32, F32, U64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "bnn_bn_bwd_q6_i16_pre": (I32, [P, P, P, I64, I64, P, P, P, P, P, I32, F32, U64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "bnn_gemm_fp6_bnstats_rows": (I64, [I64]),
-    "bnn_gemm_fp6_bnstats": (I32, [P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, P, P, I32, P, P, P, P, P, I32, I32, P, P]),
-    "bnn_hardtanh_bwd": (I32, [P, P, P, I64, P]),
-    "bnn_adam_clamp": (I32, [P, P, P, P, I64, F32, F32, F32, F32, I64, F32, I32, P]),
-    "bnn_adam_clamp_pack": (I32, [P, P, P, P, I64, I64, F32, F32, F32, F32, I64, F32, I32, I32, P, I64, P, I64, I32,
-                                  P]),
-    "bnn_adam_schedule": (I32, [F32, F32, F32, I64, I64, P]),
-    "bnn_adam_clamp_multi": (I32, [I32, P, P, P, P, P, P, P, F32, F32, F32, F32, P, P, F32, P]),
-    "bnn_adam_clamp_sched": (I32, [P, P, P, P, I64, F32, F32, F32, P, P, F32, I32, P]),
-    "bnn_adam_clamp_pack_sched": (I32, [P, P, P, P, I64, I64, F32, F32, F32, P, P, F32, I32, I32, P, I64, P, I64,
-                                        I32, P]),
-    "bnn_sgd_clamp": (I32, [P, P, P, I64, F32, F32, F32, F32, I32, I32, F32, I32, P]),
-    "bnn_sgd_clamp_multi": (I32, [I32, P, P, P, P, P, P, F32, F32, F32, F32, I32, F32, P]),
-    "bnn_sgd_clamp_pack": (I32, [P, P, P, I64, I64, F32, F32, F32, F32, I32, I32, F32, I32, I32, P, I64, P, I64, I32,
-                                 P]),
-    "bnn_counter_add": (I32, [P, I64, P]),
-    "bnn_set_seed_counter": (I32, [P]),
-    "bnn_quant6_scale_rows": (I64, [I64]),
-    "bnn_quant6_rows": (I32, [P, I64, I64, I64, I64, P, P, P, P, P]),
-    "bnn_quant6_cols_workspace": (I64, [I64, I64]),
-    "bnn_quant6_cols_t": (I32, [P, I64, I64, I64, I64, P, P, P, P, P, P]),
-    "bnn_gemm_fp6": (I32, [P, P, P, I64, P, P, I64, P, P, I64, I64, I64, I64, P]),
-    "bnn_gemm_fp6_workspace": (I64, [I64, I64, I64]),
-    "bnn_gemm_fp6_ws": (I32, [P, P, P, I64, P, P, I64, P, P, I64, I64, I64, I64, P, I64, P]),
-    "bnn_fp4_panel_bytes": (I64, [I64, I64]),
-    "bnn_fp4_panelize": (I32, [P, I64, I64, I64, P, P]),
-    "bnn_gemm_fp6_panel_ws": (I32, [P, P, P, I64, P, P, I64, P, P, I64, I64, I64, I64, P, I64, P]),
-    "bnn_gemm_fp6_kernel": (ctypes.c_char_p, [I64, I64]),
-    "bnn_gemm_fp6_kernel_k": (ctypes.c_char_p, [I64, I64, I64]),
-    "bnn_gemm_fp6_kernel_kr": (ctypes.c_char_p, [I64, I64, I64, I32]),
-    "bnn_gemm_fp6_set_variant": (I32, [I32]),
-    "bnn_gemm_fp6_set_persistent": (I32, [I32]),
-    "bnn_gemm_fp6_set_half": (I32, [I32, ctypes.c_double]),
-    "bnn_gemm_fp6_set_half_group": (I32, [I32]),
-}
+
+def _ints(size):
+    """The integer dtypes of one element size: the sign is not checked (uint32_t keep-bit planes are
+    int32 tensors, FP4 bytes travel through int8_t* and uint8_t*)."""
+    names = {1: ("int8", "uint8"), 2: ("int16", "uint16"), 4: ("int32", "uint32"), 8: ("int64", "uint64")}[size]
+    return frozenset(getattr(torch, n) for n in names if hasattr(torch, n))
+
+
+# pointee -> tensor dtypes a pointer to it takes (None: anything)
+_POINTEES = {"float": frozenset({torch.float32}), "double": frozenset({torch.float64}),
+             "int8_t": _ints(1), "uint8_t": _ints(1), "int16_t": _ints(2), "int32_t": _ints(4),
+             "uint32_t": _ints(4), "int64_t": _ints(8), "void": None}
+
+
+class Pointer:
+    """argtype of one pointer parameter.  ctypes calls from_param per argument: a tensor is checked
+    against the header's pointee type and passed as its data_ptr(); anything else (None, an int, a
+    c_void_p, a ctypes array or byref) goes through c_void_p.from_param as before.  Host and device
+    pointers are not told apart here (functional._check is the device check)."""
+    __slots__ = ("entry", "decl", "dtypes")
+
+    def __init__(self, entry, decl, dtypes):
+        self.entry, self.decl, self.dtypes = entry, decl, dtypes
+
+    def from_param(self, v):
+        if isinstance(v, torch.Tensor):
+            if self.dtypes is not None and v.dtype not in self.dtypes:
+                raise TypeError(f"{self.entry}: parameter `{self.decl}` takes "
+                                f"{' / '.join(sorted(str(d) for d in self.dtypes))}, got a {v.dtype} tensor")
+            # a c_void_p, never the bare int: ctypes would marshal that as a 32-bit C int
+            return ctypes.c_void_p(v.data_ptr())
+        return ctypes.c_void_p.from_param(v)
+
+    def __repr__(self):
+        return f"Pointer({self.entry}: {self.decl})"
+
+
+def _argtype(entry, decl):
+    ctype, _name = re.fullmatch(r"(.*?)\s*(\w+)", decl).groups()
+    if "*" not in ctype:
+        if ctype not in _SCALARS:
+            raise ValueError(f"bnn.h: {entry}: unknown parameter type in `{decl}`")
+        return _SCALARS[ctype]
+    pointee = ctype.replace("const", "").replace(" ", "")
+    if pointee.count("*") > 1:          # arrays of pointers (the multi-tensor entries)
+        return Pointer(entry, decl, None)
+    if pointee[:-1] not in _POINTEES:
+        raise ValueError(f"bnn.h: {entry}: unknown pointee type in `{decl}`")
+    return Pointer(entry, decl, _POINTEES[pointee[:-1]])
+
+
+def parse_header(text):
+    """name -> (restype, [argtypes]) of every bnn_* declaration in the header's text.  Total: an
+    unknown type or a declaration this did not parse raises."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    sigs = {}
+    for res, name, params in re.findall(r"\b(int|int64_t|const char\*)\s+(bnn_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        sigs[name] = (_RESTYPES[res], [] if params == ["void"] else [_argtype(name, p) for p in params])
+    seen = len(re.findall(r"\bbnn_\w+\s*\(", text))
+    if seen != len(sigs):
+        raise ValueError(f"bnn.h: {seen} bnn_*( declarations, {len(sigs)} parsed")
+    return sigs
+
 
 _lib = None
+_signatures = None
 
 
 def library_path():
     return os.environ.get("BNN_LIB", DEFAULT_PATH)
+
+
+def header_path():
+    return os.environ.get("BNN_HEADER", DEFAULT_HEADER)
+
+
+def signatures():
+    """The header's prototypes as ctypes signatures, parsed once."""
+    global _signatures
+    if _signatures is None:
+        path = header_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"bnn.h not found at {path}: the binding is derived from it "
+                               "(set BNN_HEADER if it lives elsewhere)")
+        with open(path) as f:
+            _signatures = parse_header(f.read())
+    return _signatures
+
+
+def __getattr__(name):
+    if name == "SIGNATURES":
+        return signatures()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def lib():
@@ -196,7 +125,7 @@ def lib():
                 "`make -C distributed-mnist-bnns_amd/csrc` (or __graft_entry__.build()). "
                 "The BNN hot path has no CPU fallback.")
         L = ctypes.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in signatures().items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -12,7 +12,7 @@ Semantics restated from the reference operator module (models/binarized_modules.
 Every op here runs on ROCm tensors through libbnn.so; there is no CPU fallback.
 """
 import contextlib
-
+import ctypes
 import itertools
 import os
 
@@ -124,7 +124,7 @@ def sign(x, out=None):
     y = torch.empty_like(x) if out is None else out
     if x.numel() == 0:            # empty tensors have no device pointer; nothing to compute
         return y
-    L.call("bnn_sign_f32", L.ptr(x), L.ptr(y), x.numel(), L.stream())
+    L.call("bnn_sign_f32", x, y, x.numel(), L.stream())
     return y
 
 
@@ -142,7 +142,7 @@ def binarize_stochastic(x, seed, out=None):
     if x.numel() == 0:
         return y
     with _timed("stoch_f32_k", 0, 8 * x.numel()):
-        L.call("bnn_binarize_stoch_f32", L.ptr(x), L.ptr(y), x.numel(), _u64(seed), L.stream())
+        L.call("bnn_binarize_stoch_f32", x, y, x.numel(), _u64(seed), L.stream())
     return y
 
 
@@ -164,11 +164,11 @@ def sign_pack(x, want_q=True, want_qt=False, stochastic=None):
     nbytes = 4 * M * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
     with _timed("sign_pack_tile_k" if stochastic is None else "stoch_pack_tile_k", 0, nbytes):
         if stochastic is None:
-            L.call("bnn_sign_pack_i8", L.ptr(x), M, K, K, L.ptr(q), q.shape[1] if q is not None else 0,
-                   L.ptr(qt), qt.shape[1] if qt is not None else 0, L.stream())
+            L.call("bnn_sign_pack_i8", x, M, K, K, q, q.shape[1] if q is not None else 0, qt,
+                   qt.shape[1] if qt is not None else 0, L.stream())
         else:
-            L.call("bnn_stoch_pack_i8", L.ptr(x), M, K, K, L.ptr(q), q.shape[1] if q is not None else 0,
-                   L.ptr(qt), qt.shape[1] if qt is not None else 0, _u64(stochastic), L.stream())
+            L.call("bnn_stoch_pack_i8", x, M, K, K, q, q.shape[1] if q is not None else 0, qt,
+                   qt.shape[1] if qt is not None else 0, _u64(stochastic), L.stream())
     return q, qt
 
 
@@ -210,12 +210,12 @@ def sign_pack_fp4(x, want_qt=False, qt_fmt="i8", want_q=True, stochastic=None, f
     nbytes = 4 * M * K + (q4.numel() if q4 is not None else 0) + (qt.numel() if qt is not None else 0)
     with _timed("sign_pack_tile_k<1>" if stochastic is None else "stoch_pack_tile_k<1>", 0, nbytes):
         if stochastic is None:
-            L.call("bnn_sign_pack_fp4", L.ptr(x), M, K, K, L.ptr(q4), q4.shape[1] if q4 is not None else 0,
-                   L.ptr(qt), qt.shape[1] if qt is not None else 0, _QT_CODE[qt_fmt], L.stream())
+            L.call("bnn_sign_pack_fp4", x, M, K, K, q4, q4.shape[1] if q4 is not None else 0, qt,
+                   qt.shape[1] if qt is not None else 0, _QT_CODE[qt_fmt], L.stream())
         else:
-            L.call("bnn_stoch_pack_fp4", L.ptr(x), M, K, K, L.ptr(q4), q4.shape[1] if q4 is not None else 0,
-                   L.ptr(qt), qt.shape[1] if qt is not None else 0, _QT_CODE[qt_fmt], _u64(stochastic),
-                   int(bool(force)), L.stream())
+            L.call("bnn_stoch_pack_fp4", x, M, K, K, q4, q4.shape[1] if q4 is not None else 0, qt,
+                   qt.shape[1] if qt is not None else 0, _QT_CODE[qt_fmt], _u64(stochastic), int(bool(force)),
+                   L.stream())
     return q4, qt
 
 
@@ -246,11 +246,10 @@ def sign_pack_fp4_writeback(x, want_qt=False, stochastic=None, force=False):
     with _timed("sign_pack_fp4_out" if stochastic is None else "stoch_pack_fp4_out", 0,
                 8 * M * K + q4.numel() + qt.numel()):
         if stochastic is None:
-            L.call("bnn_sign_pack_fp4_out", L.ptr(x), M, K, L.ptr(q4), q4.shape[1], L.ptr(qt), qt.shape[1],
-                   _QT_CODE["fp4p"], L.ptr(s), L.stream())
+            L.call("bnn_sign_pack_fp4_out", x, M, K, q4, q4.shape[1], qt, qt.shape[1], _QT_CODE["fp4p"], s, L.stream())
         else:
-            L.call("bnn_stoch_pack_fp4_out", L.ptr(x), M, K, L.ptr(q4), q4.shape[1], L.ptr(qt), qt.shape[1],
-                   _QT_CODE["fp4p"], L.ptr(s), _u64(stochastic), int(bool(force)), L.stream())
+            L.call("bnn_stoch_pack_fp4_out", x, M, K, q4, q4.shape[1], qt, qt.shape[1], _QT_CODE["fp4p"], s,
+                   _u64(stochastic), int(bool(force)), L.stream())
     return s, q4, qt
 
 
@@ -267,7 +266,7 @@ def sign_pack_bits(x, words=None):
     kw = words if words is not None else round_up((K + 31) // 32, 32)
     sb = torch.empty((M, kw), dtype=torch.int32, device=x.device)
     nz = torch.empty((M, kw), dtype=torch.int32, device=x.device)
-    L.call("bnn_sign_pack_bits", L.ptr(x), M, K, K, L.ptr(sb), L.ptr(nz), kw, L.stream())
+    L.call("bnn_sign_pack_bits", x, M, K, K, sb, nz, kw, L.stream())
     return sb, nz
 
 
@@ -280,7 +279,7 @@ def quant_rows(x):
     dg = torch.empty((3, M, ldq), dtype=torch.int8, device=x.device)
     sc = torch.empty((M,), dtype=torch.float32, device=x.device)
     with _timed("quant_rows_k", 0, 4 * M * K + dg.numel() + 4 * M):
-        L.call("bnn_quant_rows", L.ptr(x), M, K, K, L.ptr(dg), ldq, M * ldq, L.ptr(sc), L.stream())
+        L.call("bnn_quant_rows", x, M, K, K, dg, ldq, M * ldq, sc, L.stream())
     return dg, sc
 
 
@@ -297,8 +296,7 @@ def quant_cols_t(x, want_colsum=False, want_dsum=False):
     ds = torch.empty((N,), dtype=torch.int64, device=x.device) if want_dsum else None
     ws = torch.empty((L.lib().bnn_quant_cols_workspace(M, N),), dtype=torch.uint8, device=x.device)
     with _timed("quant_cols_t", 0, 4 * M * N + dg.numel() + 8 * N):
-        L.call("bnn_quant_cols_t_dsum", L.ptr(x), M, N, N, L.ptr(dg), ldqt, N * ldqt, L.ptr(sc), L.ptr(cs),
-               L.ptr(ds), L.ptr(ws), L.stream())
+        L.call("bnn_quant_cols_t_dsum", x, M, N, N, dg, ldqt, N * ldqt, sc, cs, ds, ws, L.stream())
     return (dg, sc, cs, ds) if want_dsum else (dg, sc, cs)
 
 
@@ -360,7 +358,7 @@ class DeviceStep:
         torch's CPU generator) + the device counter, in eager and captured steps alike."""
         global _DEVICE_STEP
         self.base_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        L.call("bnn_set_seed_counter", L.ptr(self.ctr))
+        L.call("bnn_set_seed_counter", self.ctr)
         self.active = True
         _DEVICE_STEP = self
         return self
@@ -373,7 +371,7 @@ class DeviceStep:
             _DEVICE_STEP = None
 
     def advance(self):
-        L.call("bnn_counter_add", L.ptr(self.ctr), 1, L.stream())
+        L.call("bnn_counter_add", self.ctr, 1, L.stream())
         self.steps += 1
 
     def note_replays(self, n):
@@ -385,7 +383,7 @@ def adam_schedule(lr, beta1, beta2, step0, n, device):
     """[n, 2] fp32 (step_size, sqrt(bias_correction2)) for Adam steps step0 .. step0+n-1, computed
     by libbnn's host code exactly as the per-launch form does, copied to ``device``."""
     host = torch.empty((n, 2), dtype=torch.float32)
-    L.call("bnn_adam_schedule", float(lr), float(beta1), float(beta2), int(step0), int(n), L.ptr(host))
+    L.call("bnn_adam_schedule", float(lr), float(beta1), float(beta2), int(step0), int(n), host)
     return host.to(device)
 
 
@@ -411,17 +409,15 @@ def adam_clamp_pack_(p, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.
     N, K = p.shape
     q, qt = ent["q"], ent["qt"]
     nbytes = 28 * N * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
-    tail = (1 if ent["fmt"] == "fp4" else 0, L.ptr(q), q.shape[1] if q is not None else 0,
-            L.ptr(qt), qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
+    tail = (1 if ent["fmt"] == "fp4" else 0, q, q.shape[1] if q is not None else 0,
+            qt, qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
     with _timed("sign_pack_tile_k<adam>", 0, nbytes):
         if sched is not None:
-            L.call("bnn_adam_clamp_pack_sched", L.ptr(p), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), N, K,
-                   float(beta1), float(beta2), float(eps), L.ptr(sched), L.ptr(ctr), float(grad_scale),
-                   int(bool(clamp)), *tail)
+            L.call("bnn_adam_clamp_pack_sched", p, grad, exp_avg, exp_avg_sq, N, K, float(beta1), float(beta2),
+                   float(eps), sched, ctr, float(grad_scale), int(bool(clamp)), *tail)
         else:
-            L.call("bnn_adam_clamp_pack", L.ptr(p), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), N, K,
-                   float(lr), float(beta1), float(beta2), float(eps), int(step), float(grad_scale),
-                   int(bool(clamp)), *tail)
+            L.call("bnn_adam_clamp_pack", p, grad, exp_avg, exp_avg_sq, N, K, float(lr), float(beta1), float(beta2),
+                   float(eps), int(step), float(grad_scale), int(bool(clamp)), *tail)
     _bump(p)
     ent["key"] = _pack_key(p)           # the operands just written match the bumped version
     return True
@@ -454,10 +450,10 @@ def sgd_clamp_pack_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=
     streams = 3 if buf is None else (4 if first else 5)
     nbytes = 4 * streams * N * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
     with _timed("sign_pack_tile_k<sgd>", 0, nbytes):
-        L.call("bnn_sgd_clamp_pack", L.ptr(p), L.ptr(grad), L.ptr(buf), N, K, float(lr), float(momentum),
-               _sgd_omd(dampening), float(weight_decay), int(bool(nesterov)), int(bool(first)), float(grad_scale),
-               int(bool(clamp)), 1 if ent["fmt"] == "fp4" else 0, L.ptr(q), q.shape[1] if q is not None else 0,
-               L.ptr(qt), qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
+        L.call("bnn_sgd_clamp_pack", p, grad, buf, N, K, float(lr), float(momentum), _sgd_omd(dampening),
+               float(weight_decay), int(bool(nesterov)), int(bool(first)), float(grad_scale), int(bool(clamp)),
+               1 if ent["fmt"] == "fp4" else 0, q, q.shape[1] if q is not None else 0, qt,
+               qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
     _bump(p)
     ent["key"] = _pack_key(p)           # the operands just written match the bumped version
     return True
@@ -487,8 +483,8 @@ def gemm_i8(A, a_digits, B, b_digits, M, N, a_scale=None, b_scale=None, bias=Non
     ops = 2.0 * M * N * k_true          # algorithmic work; digit passes are not work
     name = gemm_kernel_name(a_digits, b_digits, M, N, K) if _TIMER is not None else ""
     with _timed(name, ops, a_digits * M * K + b_digits * N * K + 4 * M * N):
-        L.call("bnn_gemm_i8", L.ptr(A), lda, a_plane, a_digits, L.ptr(B), ldb, b_plane, b_digits,
-               L.ptr(a_scale), L.ptr(b_scale), L.ptr(bias), L.ptr(C), C.stride(0), M, N, K, L.stream())
+        L.call("bnn_gemm_i8", A, lda, a_plane, a_digits, B, ldb, b_plane, b_digits, a_scale, b_scale, bias, C,
+               C.stride(0), M, N, K, L.stream())
     return C
 
 
@@ -511,9 +507,8 @@ def gemm_i8_affine(A, a_digits, B, b_digits, M, N, a_scale=None, b_scale=None, b
     if label and name:
         name = f"{name} [{label}]"
     with _timed(name, 2.0 * M * N * k_true, a_digits * M * K + b_digits * N * K + 4 * M * N):
-        L.call("bnn_gemm_i8_affine", L.ptr(A), lda, a_plane, a_digits, L.ptr(B), ldb, b_plane, b_digits,
-               L.ptr(a_scale), L.ptr(b_scale), L.ptr(bias), L.ptr(row_off), L.ptr(col_off), float(off_mul),
-               L.ptr(C), C.stride(0), M, N, K, L.stream())
+        L.call("bnn_gemm_i8_affine", A, lda, a_plane, a_digits, B, ldb, b_plane, b_digits, a_scale, b_scale, bias,
+               row_off, col_off, float(off_mul), C, C.stride(0), M, N, K, L.stream())
     return C
 
 
@@ -527,7 +522,7 @@ def gemm_fp4(A4, B4, M, N, bias=None, k_true=None):
     k_true = 2 * Kb if k_true is None else k_true
     name = gemm_kernel_name(0, 0, M, N, Kb) if _TIMER is not None else ""
     with _timed(name, 2.0 * M * N * k_true, (M + N) * Kb + 4 * M * N):
-        L.call("bnn_gemm_fp4", L.ptr(A4), Kb, L.ptr(B4), Kb, L.ptr(bias), L.ptr(C), N, M, N, Kb, L.stream())
+        L.call("bnn_gemm_fp4", A4, Kb, B4, Kb, bias, C, N, M, N, Kb, L.stream())
     return C
 
 
@@ -541,7 +536,7 @@ def gemm_fp4_i16(A4, B4, M, N, k_true=None):
     k_true = 2 * Kb if k_true is None else k_true
     name = (gemm_kernel_name(0, 0, M, N, Kb) + " [i16]") if _TIMER is not None else ""
     with _timed(name, 2.0 * M * N * k_true, (M + N) * Kb + 2 * M * N):
-        L.call("bnn_gemm_fp4_i16", L.ptr(A4), Kb, L.ptr(B4), Kb, L.ptr(C), N, M, N, Kb, L.stream())
+        L.call("bnn_gemm_fp4_i16", A4, Kb, B4, Kb, C, N, M, N, Kb, L.stream())
     return C
 
 
@@ -634,8 +629,7 @@ def gemm_xnor(a_bits, b_bits, M, N, bias=None):
     if M == 0 or N == 0:
         return C
     with _timed("gemm_xnor_k", 2.0 * M * N * kw * 32, 8 * (M + N) * kw + 4 * M * N):
-        L.call("bnn_gemm_xnor", L.ptr(As), L.ptr(An), kw, L.ptr(Bs), L.ptr(Bn), Bs.shape[1], L.ptr(bias),
-               L.ptr(C), N, M, N, kw, L.stream())
+        L.call("bnn_gemm_xnor", As, An, kw, Bs, Bn, Bs.shape[1], bias, C, N, M, N, kw, L.stream())
     return C
 
 
@@ -701,7 +695,7 @@ def quant6_rows(x):
     lo, hi, sc = _fp6_buffers(M, Kp, x.device)
     res = _res_buffer(M, Kp, x.device)
     with _timed("quant6_rows_k", 0, 4 * M * K + (3.5 if res is not None else 3) * M * Kp + M * Kp // 32):
-        L.call("bnn_quant6_rows", L.ptr(x), M, K, K, Kp, L.ptr(lo), L.ptr(hi), L.ptr(sc), L.ptr(res), L.stream())
+        L.call("bnn_quant6_rows", x, M, K, K, Kp, lo, hi, sc, res, L.stream())
     return Fp6Operand(lo, hi, sc, M, Kp, res)
 
 
@@ -717,8 +711,7 @@ def quant6_cols_t(x, want_colsum=False):
         cs = torch.empty((N,), dtype=torch.float32, device=x.device)
         ws = torch.empty((L.lib().bnn_quant6_cols_workspace(M, N),), dtype=torch.uint8, device=x.device)
     with _timed("quant6_cols_t_k", 0, 4 * M * N + 3 * N * Mp + N * Mp // 32):
-        L.call("bnn_quant6_cols_t", L.ptr(x), M, N, N, Mp, L.ptr(lo), L.ptr(hi), L.ptr(sc), L.ptr(cs), L.ptr(ws),
-               L.stream())
+        L.call("bnn_quant6_cols_t", x, M, N, N, Mp, lo, hi, sc, cs, ws, L.stream())
     return Fp6Operand(lo, hi, sc, N, Mp), cs
 
 
@@ -731,7 +724,7 @@ def fp4_panels(B4, N, Kp):
     """FP4 rows [N, >= Kp/2 bytes] -> the panel layout [ceil(N/512), Kp/64, 512, 32 B] (flat uint8)."""
     P = torch.empty((L.lib().bnn_fp4_panel_bytes(N, Kp),), dtype=torch.uint8, device=B4.device)
     with _timed("fp4_panelize_k", 0, 2 * N * Kp // 2):
-        L.call("bnn_fp4_panelize", L.ptr(B4), N, B4.shape[1], Kp, L.ptr(P), L.stream())
+        L.call("bnn_fp4_panelize", B4, N, B4.shape[1], Kp, P, L.stream())
     return P
 
 
@@ -759,11 +752,11 @@ def gemm_fp6(A, B4, N, bias=None, k_true=None, out=None, panels=None, panel_ks=N
     ws = torch.empty((wsb,), dtype=torch.uint8, device=dev) if wsb > 0 else None
     with _timed(name, 2.0 * M * N * k_true, (3.5 if A.res is not None else 3) * M * K + N * K // 2 + 4 * M * N):
         if panels is not None:
-            L.call("bnn_gemm_fp6_panel_ws", L.ptr(A.lo), L.ptr(A.hi), L.ptr(A.sc), A.sc.shape[1], L.ptr(A.res),
-                   L.ptr(panels), panel_ks, L.ptr(bias), L.ptr(C), C.stride(0), M, N, K, L.ptr(ws), wsb, L.stream())
+            L.call("bnn_gemm_fp6_panel_ws", A.lo, A.hi, A.sc, A.sc.shape[1], A.res, panels, panel_ks, bias, C,
+                   C.stride(0), M, N, K, ws, wsb, L.stream())
         else:
-            L.call("bnn_gemm_fp6_ws", L.ptr(A.lo), L.ptr(A.hi), L.ptr(A.sc), A.sc.shape[1], L.ptr(A.res), L.ptr(B4),
-                   B4.shape[1], L.ptr(bias), L.ptr(C), C.stride(0), M, N, K, L.ptr(ws), wsb, L.stream())
+            L.call("bnn_gemm_fp6_ws", A.lo, A.hi, A.sc, A.sc.shape[1], A.res, B4, B4.shape[1], bias, C, C.stride(0), M,
+                   N, K, ws, wsb, L.stream())
     return C
 
 
@@ -794,10 +787,8 @@ def gemm_fp6_bnstats(A, panels, panel_ks, N, x, xbias, x_i16, mean, mlo, invstd,
     part = torch.empty(((4 if mode == 2 else 2) * R * N,), dtype=torch.float32, device=dev)
     name = _fp6_name(M, N, K, A) if _TIMER is not None else ""
     with _timed(name, 2.0 * M * N * K, 3 * M * K + N * K // 2 + 4 * M * N + (2 if x_i16 else 4) * M * N):
-        L.call("bnn_gemm_fp6_bnstats", L.ptr(A.lo), L.ptr(A.hi), L.ptr(A.sc), A.sc.shape[1], L.ptr(A.res),
-               L.ptr(panels), panel_ks,
-               L.ptr(C), N, M, N, K, L.ptr(x), L.ptr(xbias), int(bool(x_i16)), L.ptr(mean), L.ptr(mlo), L.ptr(invstd),
-               L.ptr(gamma), L.ptr(beta), 1, int(mode), L.ptr(part), L.stream())
+        L.call("bnn_gemm_fp6_bnstats", A.lo, A.hi, A.sc, A.sc.shape[1], A.res, panels, panel_ks, C, N, M, N, K, x,
+               xbias, int(bool(x_i16)), mean, mlo, invstd, gamma, beta, 1, int(mode), part, L.stream())
     BN_EPI_USES += 1
     return C, part, R
 
@@ -972,7 +963,7 @@ def unit_to_pixels(x, guard=None):
     else:
         bad = torch.zeros((1,), dtype=torch.int32, device=x.device)
     with _timed("unit_to_pixels_k", 0, 5 * x.numel()):
-        L.call("bnn_unit_to_pixels", L.ptr(x), x.numel(), L.ptr(u), L.ptr(bad), L.stream())
+        L.call("bnn_unit_to_pixels", x, x.numel(), u, bad, L.stream())
     if capturing:
         CAPTURE_GUARDS.append(guard)
     elif int(bad.item()) != 0:
@@ -991,8 +982,8 @@ def pixels_pack(u, want_q=True, want_qt=False):
     if (q is None and qt is None) or M == 0:
         return q, qt
     with _timed("pixels_pack_k", 0, M * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)):
-        L.call("bnn_pixels_pack", L.ptr(u), M, K, K, L.ptr(q), q.shape[1] if q is not None else 0,
-               L.ptr(qt), qt.shape[1] if qt is not None else 0, L.stream())
+        L.call("bnn_pixels_pack", u, M, K, K, q, q.shape[1] if q is not None else 0, qt,
+               qt.shape[1] if qt is not None else 0, L.stream())
     return q, qt
 
 
@@ -1000,7 +991,7 @@ def row_sums(q, K):
     """Exact int64 row sums of an int8 matrix's first K columns (bnn_row_sums)."""
     N = q.shape[0]
     out = torch.empty((N,), dtype=torch.int64, device=q.device)
-    L.call("bnn_row_sums", L.ptr(q), N, K, q.shape[1], L.ptr(out), L.stream())
+    L.call("bnn_row_sums", q, N, K, q.shape[1], out, L.stream())
     return out
 
 
@@ -1034,8 +1025,8 @@ def _pixels_fwd_with_stats(q, wq, M, N, K, bscale, bias, R, s0):
     assert wq.shape[1] == Kp and Kp % ALIGN == 0
     name = f"{gemm_kernel_name(1, 1, M, N, Kp)} [pixels]" if _TIMER is not None else ""
     with _timed(name, 2.0 * M * N * K, M * Kp + N * Kp + 4 * M * N):
-        L.call("bnn_gemm_i8_affine_bnstats", L.ptr(q), Kp, L.ptr(wq), Kp, L.ptr(bscale), L.ptr(bias), L.ptr(R),
-               float(s0), L.ptr(y), N, M, N, Kp, L.ptr(part), rows, L.stream())
+        L.call("bnn_gemm_i8_affine_bnstats", q, Kp, wq, Kp, bscale, bias, R, float(s0), y, N, M, N, Kp, part, rows,
+               L.stream())
     setattr(y, _FSTATS_ATTR, (part, rows, chunk, M, N, "pixels", 0.0, 0))
     return y
 
@@ -1098,8 +1089,8 @@ def _pixels_fwd_s20(q, wq, M, N, K, a, bias, R, s0):
     bs = bias
     name = f"{gemm_kernel_name(1, 1, M, N, Kp)} [pixels s20]" if _TIMER is not None else ""
     with _timed(name, 2.0 * M * N * K, M * Kp + N * Kp + 2.5 * M * N):
-        L.call("bnn_gemm_i8_affine_bnstats_s20", L.ptr(q), Kp, L.ptr(wq), Kp, L.ptr(R), float(s0), K, L.ptr(lo),
-               L.ptr(hi), N, M, N, Kp, L.ptr(part), rows, L.ptr(_const_vec(a, N, dev)), L.ptr(bias), L.stream())
+        L.call("bnn_gemm_i8_affine_bnstats_s20", q, Kp, wq, Kp, R, float(s0), K, lo, hi, N, M, N, Kp, part, rows,
+               _const_vec(a, N, dev), bias, L.stream())
     y = _s20_carrier(lo, hi, bs, a)
     setattr(y, _FSTATS_ATTR, (part, rows, chunk, M, N, "pixels", 0.0, 0))
     return y
@@ -1133,9 +1124,8 @@ def _fp4_fwd_with_stats(q, wq, M, N, k_true, bias, zbias, chunk, i16, drop=(0.0,
     C = torch.empty((M, N), dtype=torch.int16 if i16 else torch.float32, device=q.device)
     name = (gemm_kernel_name(0, 0, M, N, Kb) + (" [i16]" if i16 else "")) if _TIMER is not None else ""
     with _timed(name, 2.0 * M * N * k_true, (M + N) * Kb + (2 if i16 else 4) * M * N):
-        L.call("bnn_gemm_fp4_bnstats", L.ptr(q), Kb, L.ptr(wq), Kb, L.ptr(None if i16 else bias),
-               None if i16 else L.ptr(C), L.ptr(C) if i16 else None, N, L.ptr(zbias), M, N, Kb, float(drop[0]),
-               int(drop[1]), L.ptr(part), rows, L.stream())
+        L.call("bnn_gemm_fp4_bnstats", q, Kb, wq, Kb, None if i16 else bias, None if i16 else C, C if i16 else None, N,
+               zbias, M, N, Kb, float(drop[0]), int(drop[1]), part, rows, L.stream())
     return C, (part, rows, chunk, M, N, "fp4", float(drop[0]), int(drop[1]))
 
 
@@ -1237,8 +1227,7 @@ class LinearNSmallFunction(torch.autograd.Function):
         N = w.shape[0]
         y = torch.empty((M, N), dtype=torch.float32, device=x.device)
         with _timed("linear_nsmall_fwd", 2.0 * M * N * K, 4 * M * K):
-            L.call("bnn_linear_nsmall_fwd", L.ptr(x), M, K, L.ptr(w), L.ptr(bias.detach() if bias is not None else None),
-                   N, L.ptr(y), L.stream())
+            L.call("bnn_linear_nsmall_fwd", x, M, K, w, bias.detach() if bias is not None else None, N, y, L.stream())
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
         return y
@@ -1255,8 +1244,7 @@ class LinearNSmallFunction(torch.autograd.Function):
         nb = int(L.lib().bnn_linear_nsmall_workspace(M, N, K)) if dw is not None or db is not None else 0
         work = torch.empty((nb,), dtype=torch.uint8, device=x.device) if nb else None
         with _timed("linear_nsmall_bwd", 4.0 * M * N * K, 8 * M * K):
-            L.call("bnn_linear_nsmall_bwd", L.ptr(x), L.ptr(w), L.ptr(dy), M, K, N, L.ptr(dx), L.ptr(dw), L.ptr(db),
-                   L.ptr(work), nb, L.stream())
+            L.call("bnn_linear_nsmall_bwd", x, w, dy, M, K, N, dx, dw, db, work, nb, L.stream())
         return dx, dw, db
 
 
@@ -1286,8 +1274,7 @@ class CrossEntropyFunction(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=p.device)
         work = torch.empty((int(L.lib().bnn_cross_entropy_workspace(M)),), dtype=torch.uint8, device=p.device)
         with _timed("cross_entropy_fwd", 0, 4 * M * C + 8 * M):
-            L.call("bnn_cross_entropy_fwd", L.ptr(p), L.ptr(target), M, C, int(ignore_index), L.ptr(loss),
-                   L.ptr(work), work.numel(), L.stream())
+            L.call("bnn_cross_entropy_fwd", p, target, M, C, int(ignore_index), loss, work, work.numel(), L.stream())
         ctx.save_for_backward(p, target, work)
         ctx.ignore_index = int(ignore_index)
         return loss
@@ -1299,8 +1286,7 @@ class CrossEntropyFunction(torch.autograd.Function):
         dp = torch.empty_like(p)
         go = go.to(torch.float32).contiguous()
         with _timed("cross_entropy_bwd", 0, 8 * M * C + 8 * M):
-            L.call("bnn_cross_entropy_bwd", L.ptr(p), L.ptr(target), M, C, ctx.ignore_index, L.ptr(go),
-                   L.ptr(work), L.ptr(dp), L.stream())
+            L.call("bnn_cross_entropy_bwd", p, target, M, C, ctx.ignore_index, go, work, dp, L.stream())
         return dp, None, None
 
 
@@ -1337,8 +1323,8 @@ class HingeLossFunction(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         work = torch.empty((int(L.lib().bnn_hinge_workspace(M, C)),), dtype=torch.uint8, device=x.device)
         with _timed("hinge_fwd", 0, (8 if dense else 4) * M * C + (0 if dense else 8 * M)):
-            L.call("bnn_hinge_fwd", L.ptr(x), L.ptr(y), L.ptr(t), M, C, float(margin), int(bool(squared)),
-                   L.ptr(loss), L.ptr(work), work.numel(), L.stream())
+            L.call("bnn_hinge_fwd", x, y, t, M, C, float(margin), int(bool(squared)), loss, work, work.numel(),
+                   L.stream())
         ctx.save_for_backward(x, target)
         ctx.args = (float(margin), bool(squared))
         return loss
@@ -1363,8 +1349,7 @@ def hinge_loss_backward(input, target, go, margin=1.0, squared=False):
     dx = torch.empty_like(x)
     go = go.to(torch.float32).contiguous()
     with _timed("hinge_bwd", 0, (12 if dense else 8) * M * C + (0 if dense else 8 * M)):
-        L.call("bnn_hinge_bwd", L.ptr(x), L.ptr(y), L.ptr(t), M, C, float(margin), int(bool(squared)), L.ptr(go),
-               L.ptr(dx), L.stream())
+        L.call("bnn_hinge_bwd", x, y, t, M, C, float(margin), int(bool(squared)), go, dx, L.stream())
     return dx
 
 
@@ -1511,8 +1496,8 @@ class BinaryConv2dFunction(torch.autograd.Function):
             yq = torch.empty((N, Co, OH, OW), dtype=torch.int8 if zf == 1 else torch.int16, device=x.device)
             macs = N * Co * OH * OW * C * KH * KW
             with _timed("conv2d_fwd", 2 * macs, 4 * x.numel() + yq.numel() * yq.element_size() + 4 * w.numel()):
-                L.call("bnn_conv2d_fwd_q", L.ptr(x), L.ptr(w), L.ptr(yq), zf, N, C, H, W, Co, KH, KW, stride,
-                       padding, dilation, groups, L.stream())
+                L.call("bnn_conv2d_fwd_q", x, w, yq, zf, N, C, H, W, Co, KH, KW, stride, padding, dilation, groups,
+                       L.stream())
             ctx.save_for_backward(x, w)
             ctx.conf = (binarize_input, stride, padding, dilation, groups)
             ctx.has_bias = bias is not None
@@ -1534,8 +1519,8 @@ class BinaryConv2dFunction(torch.autograd.Function):
             return y
         macs = N * Co * OH * OW * (C // groups) * KH * KW
         with _timed("conv2d_fwd", 2 * macs, 4 * (x.numel() + y.numel() + w.numel())):
-            L.call("bnn_conv2d_fwd", L.ptr(x), int(binarize_input), L.ptr(w), L.ptr(b), L.ptr(y),
-                   N, C, H, W, Co, KH, KW, stride, padding, dilation, groups, L.stream())
+            L.call("bnn_conv2d_fwd", x, int(binarize_input), w, b, y, N, C, H, W, Co, KH, KW, stride, padding, dilation,
+                   groups, L.stream())
         ctx.save_for_backward(x, w)
         ctx.conf = (binarize_input, stride, padding, dilation, groups)
         ctx.has_bias = bias is not None
@@ -1574,17 +1559,16 @@ class BinaryConv2dFunction(torch.autograd.Function):
                              dtype=torch.uint8, device=x.device)
             zq, zb, zf, dyp, mean, invstd, gw, gb, sg, sgx, inv_n, ht = bn
             with _timed("conv2d_bwd_filter_bn", 2 * macs, zq.numel() * zq.element_size() + 4 * dyp.numel()):
-                L.call("bnn_conv2d_bwd_filter_bn", L.ptr(zq), L.ptr(zb), zf, L.ptr(dyp), L.ptr(mean), L.ptr(invstd),
-                       L.ptr(gw), L.ptr(gb), L.ptr(sg), L.ptr(sgx), float(inv_n), int(ht), L.ptr(x),
-                       int(binarize_input), L.ptr(dw), L.ptr(db), L.ptr(ws), N, C, H, W, Co, KH, KW, stride,
-                       padding, dilation, groups, L.stream())
+                L.call("bnn_conv2d_bwd_filter_bn", zq, zb, zf, dyp, mean, invstd, gw, gb, sg, sgx, float(inv_n),
+                       int(ht), x, int(binarize_input), dw, db, ws, N, C, H, W, Co, KH, KW, stride, padding, dilation,
+                       groups, L.stream())
             C1BN_HANDOFFS += 1
             return (None, dw if ctx.needs_input_grad[1] else None, db, None, None, None, None, None, None, None)
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             with _timed("conv2d_bwd_data", 2 * macs, 4 * (dy.numel() + dx.numel() + w.numel())):
-                L.call("bnn_conv2d_bwd_data", L.ptr(dy), L.ptr(w), L.ptr(dx), N, C, H, W, Co, KH, KW,
-                       stride, padding, dilation, groups, L.stream())
+                L.call("bnn_conv2d_bwd_data", dy, w, dx, N, C, H, W, Co, KH, KW, stride, padding, dilation, groups,
+                       L.stream())
         need_db = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or need_db:
             dw = torch.empty_like(w)
@@ -1592,9 +1576,8 @@ class BinaryConv2dFunction(torch.autograd.Function):
             ws = torch.empty((L.lib().bnn_conv2d_bwd_filter_workspace(N, C, Co, KH, KW, groups),),
                              dtype=torch.uint8, device=x.device)
             with _timed("conv2d_bwd_filter", 2 * macs, 4 * (dy.numel() + x.numel() + w.numel())):
-                L.call("bnn_conv2d_bwd_filter", L.ptr(dy), L.ptr(x), int(binarize_input), L.ptr(dw),
-                       L.ptr(db), L.ptr(ws), N, C, H, W, Co, KH, KW, stride, padding, dilation, groups,
-                       L.stream())
+                L.call("bnn_conv2d_bwd_filter", dy, x, int(binarize_input), dw, db, ws, N, C, H, W, Co, KH, KW, stride,
+                       padding, dilation, groups, L.stream())
             if not ctx.needs_input_grad[1]:
                 dw = None
         return dx, dw, db, None, None, None, None, None, None, None
@@ -1610,8 +1593,8 @@ def _bn2d_dy_of_handoff(bn, shape):
     dz = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
     scratch = torch.empty((2, C), dtype=torch.float32, device=dev)
     ws = torch.empty((L.lib().bnn_bn2d_workspace(N, C),), dtype=torch.uint8, device=dev)
-    L.call("bnn_bn2d_bwd_q", L.ptr(zq), L.ptr(zb), zf, L.ptr(dyp), N, C, H, W, L.ptr(gw), L.ptr(gb), L.ptr(mean),
-           L.ptr(invstd), int(ht), 2, L.ptr(dz), L.ptr(scratch[0]), L.ptr(scratch[1]), L.ptr(ws), L.stream())
+    L.call("bnn_bn2d_bwd_q", zq, zb, zf, dyp, N, C, H, W, gw, gb, mean, invstd, int(ht), 2, dz, scratch[0], scratch[1],
+           ws, L.stream())
     return dz
 
 
@@ -1630,7 +1613,7 @@ def hardtanh_backward(x, g):
     _check(x, g)
     x, g = _c2d(x), _c2d(g)
     out = torch.empty_like(g)
-    L.call("bnn_hardtanh_bwd", L.ptr(x), L.ptr(g), L.ptr(out), g.numel(), L.stream())
+    L.call("bnn_hardtanh_bwd", x, g, out, g.numel(), L.stream())
     return out
 
 
@@ -1651,22 +1634,30 @@ def adam_clamp_(p, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, 
             raise ValueError("adam_clamp_: tensors must be contiguous")
     _bump(p)
     if sched is not None:
-        L.call("bnn_adam_clamp_sched", L.ptr(p), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), p.numel(),
-               float(beta1), float(beta2), float(eps), L.ptr(sched), L.ptr(ctr), float(grad_scale),
-               int(bool(clamp)), L.stream())
+        L.call("bnn_adam_clamp_sched", p, grad, exp_avg, exp_avg_sq, p.numel(), float(beta1), float(beta2), float(eps),
+               sched, ctr, float(grad_scale), int(bool(clamp)), L.stream())
         return
-    L.call("bnn_adam_clamp", L.ptr(p), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), p.numel(),
-           float(lr), float(beta1), float(beta2), float(eps), int(step), float(grad_scale),
-           int(bool(clamp)), L.stream())
+    L.call("bnn_adam_clamp", p, grad, exp_avg, exp_avg_sq, p.numel(), float(lr), float(beta1), float(beta2), float(eps),
+           int(step), float(grad_scale), int(bool(clamp)), L.stream())
 
 
 ADAM_MULTI_MAX = 16     # tensors per bnn_adam_clamp_multi launch
 
 
+def _multi_arrays(chunk, ntensors, *ints):
+    """The host arrays of one multi-tensor launch over ``chunk``'s items: the device pointers of each of
+    the first ``ntensors`` fields (None = NULL), the element counts of field 0, then one array per
+    (ctype, values) in ``ints``."""
+    k = len(chunk)
+    arr = [(ctypes.c_void_p * k)(*[None if it[j] is None else it[j].data_ptr() for it in chunk])
+           for j in range(ntensors)]
+    arr.append((ctypes.c_int64 * k)(*[it[0].numel() for it in chunk]))
+    return arr + [(ct * k)(*vals) for ct, vals in ints]
+
+
 def adam_clamp_multi_(items, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, sched=None, ctr=None):
     """adam_clamp_ on several tensors in one launch per ADAM_MULTI_MAX: items = [(p, grad, exp_avg,
     exp_avg_sq, step, clamp)], bit-identical per tensor to adam_clamp_ (bnn_adam_clamp_multi)."""
-    import ctypes
     for i in range(0, len(items), ADAM_MULTI_MAX):
         chunk = items[i:i + ADAM_MULTI_MAX]
         for p, g, m, v, _, _ in chunk:
@@ -1676,14 +1667,10 @@ def adam_clamp_multi_(items, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.
                 if not t.is_contiguous():
                     raise ValueError("adam_clamp_multi_: tensors must be contiguous")
             _bump(p)
-        k = len(chunk)
-        arr = [(ctypes.c_void_p * k)(*[it[j].data_ptr() for it in chunk]) for j in range(4)]
-        nn_ = (ctypes.c_int64 * k)(*[it[0].numel() for it in chunk])
-        st = (ctypes.c_int64 * k)(*[int(it[4]) for it in chunk])
-        cl = (ctypes.c_int32 * k)(*[int(bool(it[5])) for it in chunk])
-        vp = [ctypes.cast(a, ctypes.c_void_p) for a in arr + [nn_, st, cl]]
-        L.call("bnn_adam_clamp_multi", k, *vp, float(lr), float(beta1), float(beta2), float(eps), L.ptr(sched),
-               L.ptr(ctr), float(grad_scale), L.stream())
+        vp = _multi_arrays(chunk, 4, (ctypes.c_int64, [int(it[4]) for it in chunk]),
+                           (ctypes.c_int32, [int(bool(it[5])) for it in chunk]))
+        L.call("bnn_adam_clamp_multi", len(chunk), *vp, float(lr), float(beta1), float(beta2), float(eps), sched, ctr,
+               float(grad_scale), L.stream())
 
 
 def sgd_clamp_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
@@ -1698,15 +1685,14 @@ def sgd_clamp_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, 
             raise ValueError("sgd_clamp_: tensors must be contiguous")
     _bump(p)
     with _timed("sgd_clamp_k", 0, 4 * p.numel() * (3 if buf is None else (4 if first else 5))):
-        L.call("bnn_sgd_clamp", L.ptr(p), L.ptr(grad), L.ptr(buf), p.numel(), float(lr), float(momentum),
-               _sgd_omd(dampening), float(weight_decay), int(bool(nesterov)), int(bool(first)), float(grad_scale),
-               int(bool(clamp)), L.stream())
+        L.call("bnn_sgd_clamp", p, grad, buf, p.numel(), float(lr), float(momentum), _sgd_omd(dampening),
+               float(weight_decay), int(bool(nesterov)), int(bool(first)), float(grad_scale), int(bool(clamp)),
+               L.stream())
 
 
 def sgd_clamp_multi_(items, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0):
     """sgd_clamp_ on several tensors in one launch per ADAM_MULTI_MAX: items = [(p, grad, buf, first,
     clamp)] (buf None when momentum is 0), bit-identical per tensor to sgd_clamp_ (bnn_sgd_clamp_multi)."""
-    import ctypes
     for i in range(0, len(items), ADAM_MULTI_MAX):
         chunk = items[i:i + ADAM_MULTI_MAX]
         nbytes = 0
@@ -1718,14 +1704,10 @@ def sgd_clamp_multi_(items, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, n
                     raise ValueError("sgd_clamp_multi_: tensors must be contiguous")
             _bump(p)
             nbytes += 4 * p.numel() * (3 if b is None else (4 if first else 5))
-        k = len(chunk)
-        arr = [(ctypes.c_void_p * k)(*[None if it[j] is None else it[j].data_ptr() for it in chunk]) for j in range(3)]
-        nn_ = (ctypes.c_int64 * k)(*[it[0].numel() for it in chunk])
-        fi = (ctypes.c_int32 * k)(*[int(bool(it[3])) for it in chunk])
-        cl = (ctypes.c_int32 * k)(*[int(bool(it[4])) for it in chunk])
-        vp = [ctypes.cast(a, ctypes.c_void_p) for a in arr + [nn_, fi, cl]]
+        vp = _multi_arrays(chunk, 3, (ctypes.c_int32, [int(bool(it[3])) for it in chunk]),
+                           (ctypes.c_int32, [int(bool(it[4])) for it in chunk]))
         with _timed("sgd_clamp_multi_k", 0, nbytes):
-            L.call("bnn_sgd_clamp_multi", k, *vp, float(lr), float(momentum), _sgd_omd(dampening),
+            L.call("bnn_sgd_clamp_multi", len(chunk), *vp, float(lr), float(momentum), _sgd_omd(dampening),
                    float(weight_decay), int(bool(nesterov)), float(grad_scale), L.stream())
 
 
@@ -1749,11 +1731,9 @@ def _bn_stat_buffers(C, device):
 def _bn_bwd_call(training, x, dy, M, C, w, b, mean, invstd, mlo, hardtanh, dx, dw, db, ws):
     # eval mode: the running statistics are constants (dx = gamma*invstd*g)
     if training:
-        L.call("bnn_bn_bwd", L.ptr(x), L.ptr(dy), M, C, L.ptr(w), L.ptr(b), L.ptr(mean), L.ptr(invstd), L.ptr(mlo),
-               int(hardtanh), L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(ws), L.stream())
+        L.call("bnn_bn_bwd", x, dy, M, C, w, b, mean, invstd, mlo, int(hardtanh), dx, dw, db, ws, L.stream())
     else:
-        L.call("bnn_bn_bwd_eval", L.ptr(x), L.ptr(dy), M, C, L.ptr(w), L.ptr(b), L.ptr(mean), L.ptr(invstd),
-               int(hardtanh), L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(ws), L.stream())
+        L.call("bnn_bn_bwd_eval", x, dy, M, C, w, b, mean, invstd, int(hardtanh), dx, dw, db, ws, L.stream())
 
 
 # FP6 digits of a gradient, handed from the BatchNorm backward that produces it to the
@@ -1814,7 +1794,6 @@ def _bn_bwd_q6(x, dy, M, C, w, b, mean, invstd, mlo, hardtanh, p, seed, dw, db, 
     the statistics from the dX GEMM's epilogue (gemm_fp6_bnstats mode 1; p = 0)."""
     dev = dy.device
     dx = torch.empty((M, C), dtype=torch.float32, device=dev) if z16 is None else _dz_placeholder(M, C, dev)
-    dx_ptr = L.ptr(dx) if z16 is None else None
     rows = Fp6Operand(*_fp6_buffers(M, C, dev), M, C, _res_buffer(M, C, dev))
     Mp = round_up(M)
     cols = Fp6Operand(*_fp6_buffers(C, Mp, dev), C, Mp)
@@ -1822,22 +1801,15 @@ def _bn_bwd_q6(x, dy, M, C, w, b, mean, invstd, mlo, hardtanh, p, seed, dw, db, 
     xb, dzb = (8, 4) if z16 is None else (4, 0)   # bytes per element: two passes over x, the dz write
     if pre is not None:
         xb //= 2                                    # one pass over x and dy: the statistics came with dy
-        L.call("bnn_bn_bwd_stats_pre", L.ptr(pre[0]), pre[1], M, C, 1, L.ptr(w), L.ptr(invstd), L.ptr(dw), L.ptr(db),
-               None, None, L.ptr(ws), L.stream())
-    sfx = "_pre" if pre is not None else ""
+        L.call("bnn_bn_bwd_stats_pre", pre[0], pre[1], M, C, 1, w, invstd, dw, db, None, None, ws, L.stream())
+    sfx, xin = ("", (x,)) if z16 is None else ("_i16", z16)
+    sfx += "_pre" if pre is not None else ""
     rb = 0.5 if rows.res is not None else 0.0
     with _timed(name, 0, xb * M * C + (4 if pre is not None else 8) * M * C + dzb * M * C + (3 + rb) * M * C + 3 * C * Mp
                 + M * C // 16):
-        if z16 is None:
-            L.call("bnn_bn_bwd_q6" + sfx, L.ptr(x), L.ptr(dy), M, C, L.ptr(w), L.ptr(b), L.ptr(mean), L.ptr(invstd),
-                   L.ptr(mlo), int(hardtanh), float(p), int(seed), dx_ptr, L.ptr(dw), L.ptr(db), L.ptr(rows.lo),
-                   L.ptr(rows.hi), L.ptr(rows.sc), L.ptr(rows.res), L.ptr(cols.lo), L.ptr(cols.hi), L.ptr(cols.sc),
-                   L.ptr(cs), L.ptr(ws), L.stream())
-        else:
-            L.call("bnn_bn_bwd_q6_i16" + sfx, L.ptr(z16[0]), L.ptr(z16[1]), L.ptr(dy), M, C, L.ptr(w), L.ptr(b),
-                   L.ptr(mean), L.ptr(invstd), L.ptr(mlo), int(hardtanh), float(p), int(seed), dx_ptr, L.ptr(dw),
-                   L.ptr(db), L.ptr(rows.lo), L.ptr(rows.hi), L.ptr(rows.sc), L.ptr(rows.res), L.ptr(cols.lo),
-                   L.ptr(cols.hi), L.ptr(cols.sc), L.ptr(cs), L.ptr(ws), L.stream())
+        L.call("bnn_bn_bwd_q6" + sfx, *xin, dy, M, C, w, b, mean, invstd, mlo, int(hardtanh), float(p), int(seed),
+               dx if z16 is None else None, dw, db, rows.lo, rows.hi, rows.sc, rows.res, cols.lo, cols.hi, cols.sc, cs,
+               ws, L.stream())
     setattr(dx, _Q6_ATTR, (_q6_key(dx), rows, cols, cs))
     return dx
 
@@ -1863,19 +1835,13 @@ def _bn_bwd_i8c(x, dy, M, C, w, b, mean, invstd, mlo, dw, db, pre=None, s20=None
     ds = torch.empty((C,), dtype=torch.int64, device=dev)
     ws = torch.empty((L.lib().bnn_bn_bwd_i8cols_workspace(M, C),), dtype=torch.uint8, device=dev)
     if pre is not None:
-        L.call("bnn_bn_bwd_stats_pre", L.ptr(pre[0]), pre[1], M, C, 2, L.ptr(w), L.ptr(invstd), L.ptr(dw), L.ptr(db),
-               L.ptr(sc), L.ptr(ds), L.ptr(ws), L.stream())
+        L.call("bnn_bn_bwd_stats_pre", pre[0], pre[1], M, C, 2, w, invstd, dw, db, sc, ds, ws, L.stream())
     xb = 2.5 if s20 is not None else 4
     with _timed("bn_bwd_i8cols", 0, (xb + 4) * (1 if pre is not None else 2) * M * C + dg.numel()):
-        sfx = "_pre" if pre is not None else ""
-        if s20 is not None:
-            L.call("bnn_bn_bwd_i8cols_s20" + sfx, L.ptr(s20[0]), L.ptr(s20[1]), L.ptr(s20[2]), s20[3], L.ptr(dy), M, C,
-                   L.ptr(w), L.ptr(b), L.ptr(mean), L.ptr(invstd), L.ptr(mlo), 1, L.ptr(dw), L.ptr(db), L.ptr(dg), ldqt,
-                   C * ldqt, L.ptr(sc), L.ptr(cs), L.ptr(ds), L.ptr(ws), L.stream())
-        else:
-            L.call("bnn_bn_bwd_i8cols" + sfx, L.ptr(x), L.ptr(dy), M, C, L.ptr(w), L.ptr(b), L.ptr(mean), L.ptr(invstd),
-                   L.ptr(mlo), 1, L.ptr(dw), L.ptr(db), L.ptr(dg), ldqt, C * ldqt, L.ptr(sc), L.ptr(cs), L.ptr(ds),
-                   L.ptr(ws), L.stream())
+        sfx, xin = ("", (x,)) if s20 is None else ("_s20", s20)
+        sfx += "_pre" if pre is not None else ""
+        L.call("bnn_bn_bwd_i8cols" + sfx, *xin, dy, M, C, w, b, mean, invstd, mlo, 1, dw, db, dg, ldqt, C * ldqt, sc,
+               cs, ds, ws, L.stream())
     dz = _dz_placeholder(M, C, dev)
     setattr(dz, _I8C_ATTR, (_q6_key(dz), dg, sc, cs, ds))
     global I8C_HANDOFFS
@@ -1914,15 +1880,15 @@ class BatchNormHardtanhFunction(torch.autograd.Function):
         if training:
             mean, invstd, mlo = _bn_stat_buffers(C, x.device)
             with _timed("bn_fwd_train", 0, 12 * M * C):
-                L.call("bnn_bn_fwd_train", L.ptr(x), M, C, L.ptr(w), L.ptr(b), L.ptr(running_mean),
-                       L.ptr(running_var), float(momentum if momentum is not None else -1.0), float(eps),
-                       L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.ptr(y), int(hardtanh), L.ptr(ws), L.stream())
+                L.call("bnn_bn_fwd_train", x, M, C, w, b, running_mean, running_var,
+                       float(momentum if momentum is not None else -1.0), float(eps), mean, invstd, mlo, y,
+                       int(hardtanh), ws, L.stream())
         else:
             mean, mlo = running_mean, None
             invstd = (running_var + eps).rsqrt()
             with _timed("bn_fwd_eval", 0, 8 * M * C):
-                L.call("bnn_bn_fwd_eval", L.ptr(x), M, C, L.ptr(w), L.ptr(b), L.ptr(running_mean),
-                       L.ptr(running_var), float(eps), L.ptr(y), int(hardtanh), L.ptr(ws), L.stream())
+                L.call("bnn_bn_fwd_eval", x, M, C, w, b, running_mean, running_var, float(eps), y, int(hardtanh), ws,
+                       L.stream())
         ctx.save_for_backward(x, w, b, mean, invstd, mlo)
         ctx.hardtanh = hardtanh
         ctx.training = training
@@ -1963,10 +1929,9 @@ class DropoutBatchNormHardtanhFunction(torch.autograd.Function):
         ws = _bn_ws(M, C, x.device)
         mean, invstd, mlo = _bn_stat_buffers(C, x.device)
         with _timed("bn_dropout_fwd_train", 0, 12 * M * C):
-            L.call("bnn_bn_dropout_fwd_train", L.ptr(x), M, C, L.ptr(w), L.ptr(b), L.ptr(running_mean),
-                   L.ptr(running_var), float(momentum if momentum is not None else -1.0), float(eps),
-                   L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.ptr(y), 1, float(p), int(seed), None, L.ptr(ws),
-                   L.stream())
+            L.call("bnn_bn_dropout_fwd_train", x, M, C, w, b, running_mean, running_var,
+                   float(momentum if momentum is not None else -1.0), float(eps), mean, invstd, mlo, y, 1, float(p),
+                   int(seed), None, ws, L.stream())
         ctx.save_for_backward(x, w, b, mean, invstd, mlo)
         ctx.p, ctx.seed = p, seed
         return y
@@ -1986,9 +1951,8 @@ class DropoutBatchNormHardtanhFunction(torch.autograd.Function):
             return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None,
                     None, None, None, None, None, None)
         with _timed("bn_dropout_bwd", 0, 16 * M * C):
-            L.call("bnn_bn_dropout_bwd", L.ptr(x), L.ptr(dy), M, C, L.ptr(w), L.ptr(b), L.ptr(mean), L.ptr(invstd),
-                   L.ptr(mlo), 1, float(ctx.p), int(ctx.seed), L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(ws),
-                   L.stream())
+            L.call("bnn_bn_dropout_bwd", x, dy, M, C, w, b, mean, invstd, mlo, 1, float(ctx.p), int(ctx.seed), dx, dw,
+                   db, ws, L.stream())
         return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None, None)
 
@@ -2027,33 +1991,26 @@ class DropoutBNHardtanhLinearFunction(torch.autograd.Function):
         if fs is not None and float(p) > 0:
             global FP4_STATS_USES
             FP4_STATS_USES += 1
-            L.call("bnn_bn_fwd_final_parts", L.ptr(fs[0]), fs[1], fs[2], M, C, L.ptr(running_mean),
-                   L.ptr(running_var), mom, float(eps), L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.stream())
+            L.call("bnn_bn_fwd_final_parts", fs[0], fs[1], fs[2], M, C, running_mean, running_var, mom, float(eps),
+                   mean, invstd, mlo, L.stream())
         else:
             if float(p) > 0 and _KEEP_BITS[0]:
                 kb = torch.empty((int(L.lib().bnn_dropout_keep_bits_bytes(M, C)) // 4,), dtype=torch.int32,
                                  device=z.device)
             with _timed("bn_dropout_fwd_stats", 0, (4 if zz is None else 2) * M * C):
                 if zz is None:
-                    L.call("bnn_bn_dropout_fwd_train", L.ptr(z), M, C, L.ptr(gw), L.ptr(gb), L.ptr(running_mean),
-                           L.ptr(running_var), mom, float(eps), L.ptr(mean), L.ptr(invstd), L.ptr(mlo), None, 1,
-                           float(p), int(seed), L.ptr(kb), L.ptr(ws), L.stream())
+                    L.call("bnn_bn_dropout_fwd_train", z, M, C, gw, gb, running_mean, running_var, mom, float(eps),
+                           mean, invstd, mlo, None, 1, float(p), int(seed), kb, ws, L.stream())
                 else:
-                    L.call("bnn_bn_fwd_train_i16", L.ptr(zz[0]), L.ptr(zz[1]), M, C, L.ptr(gw), L.ptr(gb),
-                           L.ptr(running_mean), L.ptr(running_var), mom, float(eps), L.ptr(mean), L.ptr(invstd),
-                           L.ptr(mlo), float(p), int(seed), L.ptr(kb), L.ptr(ws), L.stream())
+                    L.call("bnn_bn_fwd_train_i16", zz[0], zz[1], M, C, gw, gb, running_mean, running_var, mom,
+                           float(eps), mean, invstd, mlo, float(p), int(seed), kb, ws, L.stream())
         w4c = w4.detach().contiguous()
         y4 = torch.empty((M, HEAD_NOUT), dtype=torch.float32, device=z.device)
         b4d = b4.detach() if b4 is not None else None
+        sfx, xin = ("", (z,)) if zz is None else ("_i16", zz)
         with _timed("bn_head_fwd", 0, (4 if zz is None else 2) * M * C + 4 * M * HEAD_NOUT):
-            if zz is None:
-                L.call("bnn_bn_head_fwd", L.ptr(z), M, C, L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.ptr(gw),
-                       L.ptr(gb), float(p), int(seed), L.ptr(kb), L.ptr(w4c), HEAD_NOUT, L.ptr(b4d), L.ptr(y4),
-                       L.stream())
-            else:
-                L.call("bnn_bn_head_fwd_i16", L.ptr(zz[0]), L.ptr(zz[1]), M, C, L.ptr(mean), L.ptr(invstd),
-                       L.ptr(mlo), L.ptr(gw), L.ptr(gb), float(p), int(seed), L.ptr(kb), L.ptr(w4c), HEAD_NOUT,
-                       L.ptr(b4d), L.ptr(y4), L.stream())
+            L.call("bnn_bn_head_fwd" + sfx, *xin, M, C, mean, invstd, mlo, gw, gb, float(p), int(seed), kb, w4c,
+                   HEAD_NOUT, b4d, y4, L.stream())
         if zz is None:
             ctx.save_for_backward(z, gw, gb, mean, invstd, mlo, w4c, None)
         else:
@@ -2081,26 +2038,18 @@ class DropoutBNHardtanhLinearFunction(torch.autograd.Function):
         cols = Fp6Operand(*_fp6_buffers(C, Mp, dev), C, Mp)
         cs = torch.empty((C,), dtype=torch.float32, device=dev)
         ws = torch.empty((L.lib().bnn_bn_head_workspace(M, C, HEAD_NOUT),), dtype=torch.uint8, device=dev)
+        sfx, xin = ("_i16", (z, zb)) if ctx.z16 else ("", (z,))
         with _timed("bn_head_bwd_q6", 0, (8 if ctx.z16 else 16) * M * C + (0 if ctx.z16 else 4) * M * C + 6 * M * C):
-            if not ctx.z16:
-                L.call("bnn_bn_head_bwd_q6", L.ptr(z), L.ptr(dy4), L.ptr(w4c), HEAD_NOUT, M, C, L.ptr(gw),
-                       L.ptr(gb), L.ptr(mean), L.ptr(invstd), L.ptr(mlo), float(ctx.p), int(ctx.seed),
-                       L.ptr(ctx.kb), L.ptr(dx),
-                       L.ptr(dgw), L.ptr(dgb), L.ptr(dw4), L.ptr(rows.lo), L.ptr(rows.hi), L.ptr(rows.sc),
-                       L.ptr(rows.res), L.ptr(cols.lo), L.ptr(cols.hi), L.ptr(cols.sc), L.ptr(cs), L.ptr(ws), L.stream())
-            else:
-                L.call("bnn_bn_head_bwd_q6_i16", L.ptr(z), L.ptr(zb), L.ptr(dy4), L.ptr(w4c), HEAD_NOUT, M, C,
-                       L.ptr(gw), L.ptr(gb), L.ptr(mean), L.ptr(invstd), L.ptr(mlo), float(ctx.p), int(ctx.seed),
-                       L.ptr(ctx.kb), None, L.ptr(dgw), L.ptr(dgb), L.ptr(dw4), L.ptr(rows.lo), L.ptr(rows.hi),
-                       L.ptr(rows.sc), L.ptr(rows.res), L.ptr(cols.lo), L.ptr(cols.hi), L.ptr(cols.sc), L.ptr(cs),
-                       L.ptr(ws), L.stream())
+            L.call("bnn_bn_head_bwd_q6" + sfx, *xin, dy4, w4c, HEAD_NOUT, M, C, gw, gb, mean, invstd, mlo, float(ctx.p),
+                   int(ctx.seed), ctx.kb, None if ctx.z16 else dx, dgw, dgb, dw4, rows.lo, rows.hi, rows.sc, rows.res,
+                   cols.lo, cols.hi, cols.sc, cs, ws, L.stream())
         if ctx.q6 or ctx.z16:
             setattr(dx, _Q6_ATTR, (_q6_key(dx), rows, cols, cs))
         db4 = None
         if ctx.has_b4 and ctx.needs_input_grad[10]:
             if COL_SUMS and M <= 32768 and dy4.is_contiguous():   # one libbnn launch (fixed order)
                 db4 = torch.empty((HEAD_NOUT,), dtype=torch.float32, device=dev)
-                L.call("bnn_col_sums_narrow", L.ptr(dy4), M, HEAD_NOUT, HEAD_NOUT, L.ptr(db4), L.stream())
+                L.call("bnn_col_sums_narrow", dy4, M, HEAD_NOUT, HEAD_NOUT, db4, L.stream())
             else:
                 db4 = dy4.sum(0)
         return (dx, dgw if ctx.needs_input_grad[1] else None, dgb if ctx.needs_input_grad[2] else None,
@@ -2148,7 +2097,7 @@ def dropout_bn_hardtanh_linear(x, p, bn, fc, seed=None):
 def dropout_mask(n, p, seed, device="cuda"):
     """The keep mask (scaled: 1/(1-p) or 0) the fused dropout passes use for elements 0..n-1."""
     out = torch.empty((n,), dtype=torch.float32, device=device)
-    L.call("bnn_dropout_mask", n, float(p), int(seed), L.ptr(out), L.stream())
+    L.call("bnn_dropout_mask", n, float(p), int(seed), out, L.stream())
     return out
 
 
@@ -2241,20 +2190,19 @@ class BatchNorm2dHardtanhPoolFunction(torch.autograd.Function):
             xb = 4 if zq is None else zq[0].element_size()
             with _timed("bn2d_fwd_train", 0, 2 * xb * nel + 4 * y.numel()):
                 if zq is None:
-                    L.call("bnn_bn2d_fwd_train", L.ptr(x), N, C, H, W, L.ptr(w), L.ptr(b), L.ptr(running_mean),
-                           L.ptr(running_var), float(momentum if momentum is not None else -1.0), float(eps),
-                           L.ptr(mean), L.ptr(invstd), L.ptr(y), int(hardtanh), int(pool), L.ptr(ws), L.stream())
+                    L.call("bnn_bn2d_fwd_train", x, N, C, H, W, w, b, running_mean, running_var,
+                           float(momentum if momentum is not None else -1.0), float(eps), mean, invstd, y,
+                           int(hardtanh), int(pool), ws, L.stream())
                 else:
-                    L.call("bnn_bn2d_fwd_train_q", L.ptr(zq[0]), L.ptr(zq[1]), zq[2], N, C, H, W, L.ptr(w), L.ptr(b),
-                           L.ptr(running_mean), L.ptr(running_var), float(momentum if momentum is not None else -1.0),
-                           float(eps), L.ptr(mean), L.ptr(invstd), L.ptr(y), int(hardtanh), int(pool), L.ptr(ws),
-                           L.stream())
+                    L.call("bnn_bn2d_fwd_train_q", zq[0], zq[1], zq[2], N, C, H, W, w, b, running_mean, running_var,
+                           float(momentum if momentum is not None else -1.0), float(eps), mean, invstd, y,
+                           int(hardtanh), int(pool), ws, L.stream())
         else:
             mean = running_mean
             invstd = (running_var + eps).rsqrt()
             with _timed("bn2d_fwd_eval", 0, 4 * nel + 4 * y.numel()):
-                L.call("bnn_bn2d_fwd_eval", L.ptr(x), N, C, H, W, L.ptr(w), L.ptr(b), L.ptr(running_mean),
-                       L.ptr(running_var), float(eps), L.ptr(y), int(hardtanh), int(pool), L.ptr(ws), L.stream())
+                L.call("bnn_bn2d_fwd_eval", x, N, C, H, W, w, b, running_mean, running_var, float(eps), y,
+                       int(hardtanh), int(pool), ws, L.stream())
         if zq is None:
             ctx.save_for_backward(x, w, b, mean, invstd, None, None)
         else:
@@ -2282,9 +2230,8 @@ class BatchNorm2dHardtanhPoolFunction(torch.autograd.Function):
             sg = torch.empty((C,), dtype=torch.float32, device=dy.device)
             sgx = torch.empty_like(sg)
             with _timed("bn2d_bwd_stats", 0, xb * nel + 4 * dy.numel()):
-                L.call("bnn_bn2d_bwd_stats_q", L.ptr(x), L.ptr(xbias), ctx.zq_fmt, L.ptr(dy), N, C, H, W, L.ptr(w),
-                       L.ptr(b), L.ptr(mean), L.ptr(invstd), int(ctx.hardtanh), int(ctx.pool), L.ptr(dw), L.ptr(db),
-                       L.ptr(sg), L.ptr(sgx), L.ptr(ws), L.stream())
+                L.call("bnn_bn2d_bwd_stats_q", x, xbias, ctx.zq_fmt, dy, N, C, H, W, w, b, mean, invstd,
+                       int(ctx.hardtanh), int(ctx.pool), dw, db, sg, sgx, ws, L.stream())
             dx = _placeholder((N, C, H, W), dy.device)
             setattr(dx, _C1BN_ATTR, (_q6_key(dx), x, xbias, ctx.zq_fmt, dy, mean, invstd, w, b, sg, sgx,
                                      1.0 / (N * H * W), int(ctx.hardtanh)))
@@ -2292,13 +2239,11 @@ class BatchNorm2dHardtanhPoolFunction(torch.autograd.Function):
                     None, None, None, None, None, None, None)
         with _timed("bn2d_bwd", 0, (2 * xb + 4) * nel + 8 * dy.numel()):
             if ctx.zq_fmt:
-                L.call("bnn_bn2d_bwd_q", L.ptr(x), L.ptr(xbias), ctx.zq_fmt, L.ptr(dy), N, C, H, W, L.ptr(w), L.ptr(b),
-                       L.ptr(mean), L.ptr(invstd), int(ctx.hardtanh), int(ctx.pool), L.ptr(dx), L.ptr(dw), L.ptr(db),
-                       L.ptr(ws), L.stream())
+                L.call("bnn_bn2d_bwd_q", x, xbias, ctx.zq_fmt, dy, N, C, H, W, w, b, mean, invstd, int(ctx.hardtanh),
+                       int(ctx.pool), dx, dw, db, ws, L.stream())
             else:
-                L.call("bnn_bn2d_bwd" if ctx.training else "bnn_bn2d_bwd_eval", L.ptr(x), L.ptr(dy), N, C, H, W,
-                       L.ptr(w), L.ptr(b), L.ptr(mean), L.ptr(invstd), int(ctx.hardtanh), int(ctx.pool), L.ptr(dx),
-                       L.ptr(dw), L.ptr(db), L.ptr(ws), L.stream())
+                L.call("bnn_bn2d_bwd" if ctx.training else "bnn_bn2d_bwd_eval", x, dy, N, C, H, W, w, b, mean, invstd,
+                       int(ctx.hardtanh), int(ctx.pool), dx, dw, db, ws, L.stream())
         return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None, None, None)
 
@@ -2363,16 +2308,15 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
                         PIX_STATS_USES += 1
                     else:
                         FP4_STATS_USES += 1
-                    L.call("bnn_bn_fwd_final_parts", L.ptr(fs[0]), fs[1], fs[2], M, C, L.ptr(rm), L.ptr(rv), mom,
-                           float(eps), L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.stream())
+                    L.call("bnn_bn_fwd_final_parts", fs[0], fs[1], fs[2], M, C, rm, rv, mom, float(eps), mean, invstd,
+                           mlo, L.stream())
                 elif zz is None:
                     assert zs is None
-                    L.call("bnn_bn_fwd_train", L.ptr(z), M, C, L.ptr(gw), L.ptr(gb), L.ptr(rm), L.ptr(rv), mom,
-                           float(eps), L.ptr(mean), L.ptr(invstd), L.ptr(mlo), None, 1, L.ptr(ws), L.stream())
+                    L.call("bnn_bn_fwd_train", z, M, C, gw, gb, rm, rv, mom, float(eps), mean, invstd, mlo, None, 1, ws,
+                           L.stream())
                 else:
-                    L.call("bnn_bn_fwd_train_i16", L.ptr(zz[0]), L.ptr(zz[1]), M, C, L.ptr(gw), L.ptr(gb), L.ptr(rm),
-                           L.ptr(rv), mom, float(eps), L.ptr(mean), L.ptr(invstd), L.ptr(mlo), 0.0, 0, None,
-                           L.ptr(ws), L.stream())
+                    L.call("bnn_bn_fwd_train_i16", zz[0], zz[1], M, C, gw, gb, rm, rv, mom, float(eps), mean, invstd,
+                           mlo, 0.0, 0, None, ws, L.stream())
         else:
             mean, mlo = rm.contiguous(), None
             invstd = (rv + eps).rsqrt()
@@ -2388,30 +2332,17 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
         nx = 2.5 if zs is not None else (4 if zz is None else 2)
         with _timed("bn_apply_pack" if stochastic is None else "bn_apply_pack_stoch", 0,
                     nx * M * C + q.numel() + (qt.numel() if qt is not None else 0)):
-            if stochastic is not None and zs is not None:
-                L.call("bnn_bn_apply_pack_stoch_s20", L.ptr(zs[0]), L.ptr(zs[1]), L.ptr(zs[2]), zs[3], M, C,
-                       L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.ptr(gw), L.ptr(gb), L.ptr(q), q.shape[1], L.ptr(qt),
-                       qt.shape[1], 1 if ctx.qt_panel else 0, _u64(stochastic), L.stream())
-            elif stochastic is not None and zz is None:
-                L.call("bnn_bn_apply_pack_stoch", L.ptr(z), M, C, L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.ptr(gw),
-                       L.ptr(gb), 1 if fp4 else 0, L.ptr(q), q.shape[1], L.ptr(qt), qt.shape[1] if qt is not None else 0,
-                       _QT_CODE[qf], _u64(stochastic), 0, L.stream())
+            if zs is not None or zz is not None:      # the compact forms: FP4 rows, qt in panels or absent
+                sfx, xin = ("_s20", zs) if zs is not None else ("_i16", zz)
+                stoch, seed = ("", ()) if stochastic is None else ("_stoch", (_u64(stochastic),))
+                L.call("bnn_bn_apply_pack" + stoch + sfx, *xin, M, C, mean, invstd, mlo, gw, gb, q, q.shape[1], qt,
+                       qt.shape[1], 1 if ctx.qt_panel else 0, *seed, L.stream())
             elif stochastic is not None:
-                L.call("bnn_bn_apply_pack_stoch_i16", L.ptr(zz[0]), L.ptr(zz[1]), M, C, L.ptr(mean), L.ptr(invstd),
-                       L.ptr(mlo), L.ptr(gw), L.ptr(gb), L.ptr(q), q.shape[1], L.ptr(qt), qt.shape[1],
-                       1 if ctx.qt_panel else 0, _u64(stochastic), L.stream())
-            elif zs is not None:
-                L.call("bnn_bn_apply_pack_s20", L.ptr(zs[0]), L.ptr(zs[1]), L.ptr(zs[2]), zs[3], M, C, L.ptr(mean),
-                       L.ptr(invstd), L.ptr(mlo), L.ptr(gw), L.ptr(gb), L.ptr(q), q.shape[1], L.ptr(qt), qt.shape[1],
-                       1 if ctx.qt_panel else 0, L.stream())
-            elif zz is None:
-                L.call("bnn_bn_apply_pack", L.ptr(z), M, C, L.ptr(mean), L.ptr(invstd), L.ptr(mlo), L.ptr(gw),
-                       L.ptr(gb), 1 if fp4 else 0, L.ptr(q), q.shape[1], L.ptr(qt), qt.shape[1] if qt is not None else 0,
-                       _QT_CODE[qf], L.stream())
+                L.call("bnn_bn_apply_pack_stoch", z, M, C, mean, invstd, mlo, gw, gb, 1 if fp4 else 0, q, q.shape[1],
+                       qt, qt.shape[1] if qt is not None else 0, _QT_CODE[qf], _u64(stochastic), 0, L.stream())
             else:
-                L.call("bnn_bn_apply_pack_i16", L.ptr(zz[0]), L.ptr(zz[1]), M, C, L.ptr(mean), L.ptr(invstd),
-                       L.ptr(mlo), L.ptr(gw), L.ptr(gb), L.ptr(q), q.shape[1], L.ptr(qt), qt.shape[1],
-                       1 if ctx.qt_panel else 0, L.stream())
+                L.call("bnn_bn_apply_pack", z, M, C, mean, invstd, mlo, gw, gb, 1 if fp4 else 0, q, q.shape[1], qt,
+                       qt.shape[1] if qt is not None else 0, _QT_CODE[qf], L.stream())
         b = bias.detach() if bias is not None else None
         wq, wqt = packed_weight(weight, "fp4" if fp4 else "i8", True, need_dh, cache=True, qt_fmt=qf)
         chunk = (int(L.lib().bnn_gemm_fp4_bnstats_chunk(M, N, q.shape[1]))
@@ -2554,8 +2485,8 @@ def gemm_fp4_bnsign(A4, B4, M, N, bias, mean, invstd, gamma=None, beta=None, k_t
         return q4
     k_true = 2 * Kb if k_true is None else k_true
     with _timed("gemm_fp4_bnsign_k", 2.0 * M * N * k_true, (M + N) * Kb + q4.numel()):
-        L.call("bnn_gemm_fp4_bnsign", L.ptr(A4), Kb, L.ptr(B4), Kb, L.ptr(bias), L.ptr(mean), L.ptr(invstd),
-               L.ptr(gamma), L.ptr(beta), L.ptr(q4), q4.shape[1], M, N, Kb, L.stream())
+        L.call("bnn_gemm_fp4_bnsign", A4, Kb, B4, Kb, bias, mean, invstd, gamma, beta, q4, q4.shape[1], M, N, Kb,
+               L.stream())
     return q4
 
 
@@ -2571,9 +2502,8 @@ def gemm_i8_affine_bnsign(A, B, M, N, b_scale, bias, col_off, off_mul, mean, inv
         return q4
     k_true = K if k_true is None else k_true
     with _timed("gemm_i8_bnsign_k [pixels]", 2.0 * M * N * k_true, (M + N) * K + q4.numel()):
-        L.call("bnn_gemm_i8_affine_bnsign", L.ptr(A), K, L.ptr(B), K, L.ptr(b_scale), L.ptr(bias), L.ptr(col_off),
-               float(off_mul), L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), L.ptr(q4), q4.shape[1],
-               M, N, K, L.stream())
+        L.call("bnn_gemm_i8_affine_bnsign", A, K, B, K, b_scale, bias, col_off, float(off_mul), mean, invstd, gamma,
+               beta, q4, q4.shape[1], M, N, K, L.stream())
     return q4
 
 
@@ -2605,9 +2535,8 @@ def bn_head_eval(z, mean, invstd, gamma, beta, w4, b4, out=None):
     if M == 0:
         return y4
     with _timed("bn_head_fwd [eval]", 0, (2 if z16 else 4) * M * C + 4 * M * HEAD_NOUT):
-        L.call("bnn_bn_head_eval", None if z16 else L.ptr(x), L.ptr(x) if z16 else None,
-               L.ptr(z[1]) if z16 else None, M, C, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), L.ptr(w4),
-               HEAD_NOUT, L.ptr(b4), L.ptr(y4), L.stream())
+        L.call("bnn_bn_head_eval", None if z16 else x, x if z16 else None, z[1] if z16 else None, M, C, mean, invstd,
+               gamma, beta, w4, HEAD_NOUT, b4, y4, L.stream())
     return y4
 
 
@@ -2625,8 +2554,7 @@ def bn_linear_eval(z, mean, var, eps, gamma, beta, w4, b4):
         return torch.empty((0, w4.shape[0]), dtype=torch.float32, device=x.device)
     h = torch.empty_like(x)
     with _timed("bn_fwd_eval", 0, 8 * M * C):
-        L.call("bnn_bn_fwd_eval", L.ptr(x), M, C, L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(var),
-               float(eps), L.ptr(h), 1, L.ptr(_bn_ws(M, C, x.device)), L.stream())
+        L.call("bnn_bn_fwd_eval", x, M, C, gamma, beta, mean, var, float(eps), h, 1, _bn_ws(M, C, x.device), L.stream())
     return torch.nn.functional.linear(h, w4 if w4.is_contiguous() else w4.contiguous(), b4)
 
 

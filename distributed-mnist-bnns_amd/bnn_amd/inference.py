@@ -305,8 +305,8 @@ class FrozenMLP(_Frozen):
         """The two-pass form's second pass: z fp32 -> FP4 rows of sign(BN_i(z)) (bnn_bn_apply_pack)."""
         mean, invstd, gamma, beta = self._bn(i)
         M, C = z.shape
-        L.call("bnn_bn_apply_pack", L.ptr(z), M, C, L.ptr(mean), L.ptr(invstd), None, L.ptr(gamma), L.ptr(beta), 1,
-               L.ptr(out), out.shape[1], None, 0, 0, L.stream())
+        L.call("bnn_bn_apply_pack", z, M, C, mean, invstd, None, gamma, beta, 1, out, out.shape[1], None, 0, 0,
+               L.stream())
         return out
 
     def _forward_gpu(self, x, b):
@@ -323,7 +323,7 @@ class FrozenMLP(_Frozen):
             x = u if u is not None else x
         if x.dtype == torch.uint8:
             x = x if x.is_contiguous() else x.contiguous()
-            L.call("bnn_pixels_pack", L.ptr(x), M, _K1, _K1, L.ptr(b["q"]), b["q"].shape[1], None, 0, L.stream())
+            L.call("bnn_pixels_pack", x, M, _K1, _K1, b["q"], b["q"].shape[1], None, 0, L.stream())
             a, s0 = BF.pixel_affine(self.normalize)
             bscale = BF._const_vec(a, h1, x.device)
             if BF.bnsign_ok(h1) and not self.two_pass:
@@ -503,8 +503,8 @@ class FrozenCNN(_Frozen):
         y = torch.empty((N, Co, PH, PW), dtype=torch.float32, device=x.device)
         ws = torch.empty((L.lib().bnn_bn2d_workspace(N, Co),), dtype=torch.uint8, device=x.device)
         mean, _, gamma, beta = self._bn(i)
-        L.call("bnn_bn2d_fwd_eval", L.ptr(z), N, Co, z.shape[2], z.shape[3], L.ptr(gamma), L.ptr(beta), L.ptr(mean),
-               L.ptr(self.t[f"bn{i}.var"]), float(self.eps[i - 1]), L.ptr(y), 1, 2, L.ptr(ws), L.stream())
+        L.call("bnn_bn2d_fwd_eval", z, N, Co, z.shape[2], z.shape[3], gamma, beta, mean, self.t[f"bn{i}.var"],
+               float(self.eps[i - 1]), y, 1, 2, ws, L.stream())
         return y
 
     def _as_form(self, cur, form, want, C):
@@ -549,13 +549,12 @@ class FrozenCNN(_Frozen):
             want = "f32" if not fused else "s8" if last else form
             cur, form = self._as_form(cur, form, want, C), want
             if fused and last:
-                L.call("bnn_conv2d_fwd_bn_pool_linear", L.ptr(cur), L.ptr(wq), L.ptr(bias), L.ptr(mean), L.ptr(invstd),
-                       L.ptr(gamma), L.ptr(beta), L.ptr(t["fc.weight"]), L.ptr(t.get("fc.bias")), n_out, L.ptr(b["y"]),
-                       *geo, L.stream())
+                L.call("bnn_conv2d_fwd_bn_pool_linear", cur, wq, bias, mean, invstd, gamma, beta, t["fc.weight"],
+                       t.get("fc.bias"), n_out, b["y"], *geo, L.stream())
                 logits = b["y"]
             elif fused:
-                L.call("bnn_conv2d_fwd_bnsign_pool", L.ptr(cur), xfmt, L.ptr(t["pixel.table"]), L.ptr(wq), L.ptr(bias),
-                       L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), L.ptr(b[f"a{i}"]), *geo, L.stream())
+                L.call("bnn_conv2d_fwd_bnsign_pool", cur, xfmt, t["pixel.table"], wq, bias, mean, invstd, gamma, beta,
+                       b[f"a{i}"], *geo, L.stream())
                 cur, form = b[f"a{i}"], "s8"
             else:
                 cur = self._two_pass_layer(i, cur, shp)
