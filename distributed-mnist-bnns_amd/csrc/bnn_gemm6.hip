@@ -232,6 +232,28 @@ __device__ __forceinline__ void glds16_6s(const void* sbase, uint32_t voff, void
                : "memory", "m0");
 }
 
+// Four B fragments (FP4 panels, BREG instances of gemm_fp6_k) straight into registers: fragment u =
+// the contiguous KiB at sbase + 1024 u, 16 B per lane at voff (saddr form: wave-uniform base in SGPRs
+// + per-lane 32-bit offset).  The compiler neither counts these loads nor knows when they land: the
+// destinations may be read only behind a counted wait and pin_b6 (the caller's issue sequence).
+__device__ __forceinline__ void gload_b6(const void* sbase, uint32_t voff, v4i& f0, v4i& f1, v4i& f2, v4i& f3) {
+  asm volatile("s_nop 4\n\t"
+               "global_load_dwordx4 %0, %4, %5\n\t"
+               "global_load_dwordx4 %1, %4, %5 offset:1024\n\t"
+               "global_load_dwordx4 %2, %4, %5 offset:2048\n\t"
+               "global_load_dwordx4 %3, %4, %5 offset:3072"
+               : "=&v"(f0), "=&v"(f1), "=&v"(f2), "=&v"(f3)
+               : "v"(voff), "s"(sbase)
+               : "memory");
+}
+
+// Behind the wait for gload_b6's loads: every later use of the fragments depends on this statement,
+// so neither the compiler's scheduler nor its register allocator moves one ahead of the wait.
+__device__ __forceinline__ void pin_b6(v4i& f0, v4i& f1, v4i& f2, v4i& f3) {
+  asm volatile("" : "+v"(f0), "+v"(f1), "+v"(f2), "+v"(f3) : : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt6() {
   static_assert(N >= 0 && N < 64, "vmcnt range");
@@ -265,7 +287,17 @@ __device__ __forceinline__ void tile6_of(int bid, int gm, int gn, int G, int& tm
 //          chunk c ^ ((row >> 1) & 7)
 //   A hi : BM rows x  64 B  (block 0: planes 01, 23; block 1: ...), chunk c at c ^ ((row >> 2) & 3)
 //   A sc : BM x 2 B        (row-major, plane-0 bytes of blocks 0, 1)
-//   B    : BN rows x  32 B  (the 64 FP4 codes), chunk c at c ^ ((row >> 3) & 1)
+//   B    : BN rows x  32 B  (the 64 FP4 codes), chunk c at c ^ ((row >> 3) & 1); absent with BREG
+//   A res: BM rows x  32 B  (RES only; block c of row i at chunk c ^ ((i >> 3) & 1))
+// Bytes per stage: 128 x 512 tile 42,496 (+ 4,096 with RES); 64 x 512 half tile 29,696 (+ 2,048),
+// and with BREG 13,312 (+ 2,048): a three-stage ring of 46,080 B where two stages with B took 63,488.
+// BREG = 1 (WAVES_M = 1, B in FP4 panels: the half-tile dX launches): B never enters LDS.  With one
+// wave row, wave wn is the only reader of B rows wn*128 .. wn*128+127, and its fragment for column
+// group u is one contiguous KiB of the panel: 4 global_load_dwordx4 per wave and k-step replace 16
+// LDS-DMA pieces per workgroup and the 4 ds_read_b128 per wave that fetched the same bytes back.  The
+// fragments are double-buffered in registers (2 x 16 VGPRs), one k-step ahead; the A ring may then
+// be three stages deep, RES included (FP6_BREG_STAGES; two measured faster and is the default,
+// DESIGN.md §5).  Same register image as read_b's, same MFMAs in the same order.
 // DIAG (timing-only builds, wrong results): 1 = no global->LDS staging, 2 = no LDS fragment reads,
 // 3 / 4 = the MFMA stream alone (fragments read once) with / without the per-step barrier, 5 = B
 // staged from contiguous per-k-step panels (as if B were stored [N/BN][K/64][BN][32 B]), 6 = 5 +
@@ -279,10 +311,13 @@ __device__ __forceinline__ void tile6_of(int bid, int gm, int gn, int G, int& tm
 // ring slots are in flight: stage kt+1 is waited for at step kt with stage kt+2 still landing
 // (two steps of cover), and stage kt+3 refills the slot stage kt has just left.
 // RES = 1: A carries the residual FP4 plane (header): BM x 32 B more per stage (block c of row i at
-// chunk c ^ ((i >> 3) & 1), as B's), a fifth MFMA per A fragment; the plain two-stage loop only.
+// chunk c ^ ((i >> 3) & 1), as B's), a fifth MFMA per A fragment; the plain two-stage loop, or the
+// BREG loop at two or three stages.
 template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int DIAG = 0, int OCC = 2, int PP = 0,
-          int BNS = 0, int RES = 0>
+          int BNS = 0, int RES = 0, int BREG = 0>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6Params p) {
+  static_assert(!BREG || (WAVES_M == 1 && WN == 4 && PP == 0 && DIAG == 0 && BNS == 0 && (STAGES == 2 || STAGES == 3)),
+                "B in registers: one wave row, 4 column groups per wave, the plain loop at 2 or 3 stages");
   static_assert(PP != 1 || (WM == 2 && STAGES == 3 && DIAG == 0), "pipelined form 1: 2 tile rows, 3 stages");
   static_assert(PP != 2 || (WM == 1 && WN % 2 == 0 && STAGES == 3 && DIAG == 0),
                 "pipelined form 2: 1 tile row, an even number of tile columns, 3 stages");
@@ -290,11 +325,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
                 "ping-pong form: 2 wave rows (the two groups), 2 tile rows, 3 stages");
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
-  constexpr int LO_ST = BM * 128, HI_ST = BM * 64, SC_ST = BM * 2, B_ST = BN * 32;
+  constexpr int LO_ST = BM * 128, HI_ST = BM * 64, SC_ST = BM * 2, B_ST = BREG ? 0 : BN * 32;
   constexpr int SC_PAD = (SC_ST + 1023) / 1024 * 1024;
   constexpr int R_ST = RES ? BM * 32 : 0;
   constexpr int ST = LO_ST + HI_ST + SC_PAD + B_ST + R_ST;
-  static_assert(!RES || (PP == 0 && DIAG == 0 && STAGES == 2), "the residual plane: the plain two-stage loop");
+  static_assert(!RES || (PP == 0 && DIAG == 0 && (STAGES == 2 || BREG)),
+                "the residual plane: the plain two-stage loop, or the BREG loop");
+  static_assert(STAGES * ST >= NW * 4096, "the epilogue's per-wave patches lie in the ring");
   constexpr int I_LO = LO_ST / 1024, I_HI = HI_ST / 1024, I_SC = SC_PAD / 1024, I_B = B_ST / 1024;
   constexpr int PER_WAVE = (I_LO + I_HI + I_B) / NW + 1;   // wave 0 also issues the scale piece
   __shared__ __attribute__((aligned(16))) char smem[STAGES * ST];
@@ -325,7 +362,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
   // k-invariant and computed once, so a stage is a wave-uniform base advance + the saddr-form DMA.
   static_assert(I_LO % NW == 0 && I_HI % NW == 0 && I_B % NW == 0 && I_SC == 1, "piece split");
   constexpr int P_LO = I_LO / NW, P_HI = I_HI / NW, P_B = I_B / NW;
-  uint32_t off_lo[P_LO], off_hi[P_HI], off_b[P_B];
+  uint32_t off_lo[P_LO], off_hi[P_HI], off_b[P_B > 0 ? P_B : 1];
 #pragma unroll
   for (int ii = 0; ii < P_LO; ++ii) {
     const int i = wave + ii * NW;
@@ -358,11 +395,15 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
   const int64_t b_step = (DIAG >= 5) ? BN * 32 : (p.bks > 0 ? FP4_PANEL * 32 : 32);
   // the residual plane: I_R pieces of 32 rows x 32 B, one per wave (waves >= I_R issue none; the
   // two-stage loop waits for every piece, so the per-wave counts need not match)
+  // BREG: residual piece i is wave i + 1's, so that no wave issues more than one piece beyond its
+  // lo / hi share (wave 0 has the scale piece) and the counted waits know two counts, not three
   constexpr int I_R = R_ST / 1024, P_R = (I_R + NW - 1) / NW;
+  static_assert(!BREG || I_R < NW, "BREG: one residual piece per wave 1 .. I_R");
+  const int rwave = BREG ? wave - 1 : wave;
   uint32_t off_r[P_R > 0 ? P_R : 1];
 #pragma unroll
   for (int ii = 0; ii < P_R; ++ii) {
-    const int lrow = (wave + ii * NW) * 32 + (lane >> 1), c = lane & 1;
+    const int lrow = (rwave + ii * NW) * 32 + (lane >> 1), c = lane & 1;
     off_r[ii] = (uint32_t)min(lrow, p.M - 1 - m0) * (uint32_t)(nblk * 16) + 16u * (uint32_t)(c ^ ((lrow >> 3) & 1));
   }
   const uint8_t* r_base = RES ? p.ares + (int64_t)m0 * nblk * 16 + (int64_t)ks0 * 32 : nullptr;
@@ -378,13 +419,17 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
 #pragma unroll
     for (int ii = 0; ii < P_B; ++ii)
       glds16_6s(b_base + (int64_t)kt * b_step, off_b[ii], base + LO_ST + HI_ST + SC_PAD + (wave + ii * NW) * 1024);
-    if (wave == 0)   // a whole 1-KiB piece (512 rows): the scale array has 512 rows of tail padding
-      glds16_6(sc_base + (int64_t)kt * p.asc_rows * 2 + lane * 16, base + LO_ST + HI_ST);
+    if (wave == 0) {   // a whole 1-KiB piece (512 rows): the scale array has 512 rows of tail padding
+      if constexpr (BREG)   // asm form (as stage_piece): the compiler counts none of the ring's pieces
+        glds16_6s(sc_base + (int64_t)kt * p.asc_rows * 2, (uint32_t)lane * 16u, base + LO_ST + HI_ST);
+      else
+        glds16_6(sc_base + (int64_t)kt * p.asc_rows * 2 + lane * 16, base + LO_ST + HI_ST);
+    }
     if constexpr (RES) {
 #pragma unroll
       for (int ii = 0; ii < P_R; ++ii)
-        if (wave + ii * NW < I_R)
-          glds16_6s(r_base + (int64_t)kt * 32, off_r[ii], base + LO_ST + HI_ST + SC_PAD + B_ST + (wave + ii * NW) * 1024);
+        if (rwave + ii * NW >= 0 && rwave + ii * NW < I_R)
+          glds16_6s(r_base + (int64_t)kt * 32, off_r[ii], base + LO_ST + HI_ST + SC_PAD + B_ST + (rwave + ii * NW) * 1024);
     }
   };
   // piece i (compile-time after unrolling) of stage(kt, buf): lo, hi, B, then wave 0's scale piece
@@ -721,6 +766,54 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
         if (g < NPIECE - 1) stage_piece(kn, nb, g);
       }
       __builtin_amdgcn_sched_barrier(0);
+    }
+  } else if constexpr (BREG) {
+    // B fragments from the panels into registers, one k-step ahead; the A ring STAGES deep.  Lane l
+    // of fragment u: panel row wn*128 + u*32 + (l & 31), k-block l >> 5 -- what read_b returns.
+    // Loads and LDS-DMA pieces retire through one in-order counter.  Issue sequence of a wave, with
+    // A(k) = its pieces of stage k (NA, or NA + 1 for wave 0's scale piece and waves 1 .. I_R's
+    // residual piece) and B(k) = its 4 fragment loads of k-step k:
+    //   prologue            A(0) B(0) [A(1)]                      ([..]: STAGES = 3 only)
+    //   step kt, on top     wait until only A(kt+1) may be out    -> A(kt), B(kt) have landed
+    //            barrier    (every wave's A(kt) pieces landed; slot (kt-1) % STAGES is read out)
+    //            then       B(kt+1) A(kt+STAGES-1)
+    // so on top of step kt the counter holds, oldest first, A(kt) B(kt) [A(kt+1)]: vmcnt(own A
+    // count) with three stages while a step kt+1 exists, vmcnt(0) with two stages and on the last
+    // step.  No B load is issued past the last k-step, so none is in flight when the registers
+    // are reused; the epilogue's vmcnt(0) finds nothing of B's.
+    constexpr int NA = P_LO + P_HI;
+    const bool extra = wave < 1 + I_R;
+    const uint32_t off_bf = (uint32_t)((wn * WN * 32 + r) * 32 + h * 16);
+    v4i b0[WN], b1[WN];
+    auto load_b = [&](int kt, v4i (&bf)[WN]) __attribute__((always_inline)) {
+      gload_b6(b_base + (int64_t)kt * b_step, off_bf, bf[0], bf[1], bf[2], bf[3]);
+    };
+    auto step = [&](int kt, v4i (&bc)[WN], v4i (&bn)[WN]) __attribute__((always_inline)) {
+      if (STAGES >= 3 && kt + 1 < nk) {
+        if (extra) wait_vmcnt6<NA + 1>(); else wait_vmcnt6<NA>();
+      } else {
+        wait_vmcnt6<0>();
+      }
+      pin_b6(bc[0], bc[1], bc[2], bc[3]);
+      barrier6();
+      if (kt + 1 < nk) load_b(kt + 1, bn);
+      if (kt + STAGES - 1 < nk) stage(kt + STAGES - 1, (kt + STAGES - 1) % STAGES);
+      const char* base = smem + (kt % STAGES) * ST;
+#pragma unroll
+      for (int t = 0; t < WM; ++t) {
+        AFrag f;
+        read_a(base, t, f);
+        mma_tile(f, bc, acc[t]);
+      }
+    };
+    if (nk > 0) {
+      stage(0, 0);
+      load_b(0, b0);
+      if (STAGES >= 3 && nk > 1) stage(1, 1);
+    }
+    for (int kt = 0; kt < nk; kt += 2) {   // written out twice: each register set keeps its name
+      step(kt, b0, b1);
+      if (kt + 1 < nk) step(kt + 1, b1, b0);
     }
   } else if constexpr (DIAG == 3 || DIAG == 4) {
     // timing-only: fragments read once from stage 0 and reused by every k-step -- the MFMA
@@ -1157,7 +1250,7 @@ __global__ __launch_bounds__(256) void gemm6_splitk_sum_k(const float* __restric
 }
 
 template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int DIAG = 0, int OCC = 2, int PP = 0,
-          int BNS = 0, int RES = 0>
+          int BNS = 0, int RES = 0, int BREG = 0>
 int launch6(Gemm6Params p, hipStream_t s) {
   constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
   p.gm = (p.M + BM - 1) / BM;
@@ -1166,7 +1259,7 @@ int launch6(Gemm6Params p, hipStream_t s) {
   const int nk = p.K / 64;
   p.kps = (nk + p.ksplit - 1) / p.ksplit;
   p.ksplit = (nk + p.kps - 1) / p.kps;          // no empty split
-  hipLaunchKernelGGL((gemm_fp6_k<WAVES_M, WAVES_N, WM, WN, STAGES, DIAG, OCC, PP, BNS, RES>),
+  hipLaunchKernelGGL((gemm_fp6_k<WAVES_M, WAVES_N, WM, WN, STAGES, DIAG, OCC, PP, BNS, RES, BREG>),
                      dim3((unsigned)((int64_t)p.gm * p.gn * p.ksplit)), dim3(64 * WAVES_M * WAVES_N), 0, s, p);
   if (p.ksplit > 1)
     hipLaunchKernelGGL(gemm6_splitk_sum_k, dim3((unsigned)(((int64_t)p.M * p.N / 4 + 255) / 256)), dim3(256), 0, s,
@@ -1243,7 +1336,9 @@ const Variant6 kVariants6[] = {
 int g_variant6 = -1;
 // bnn_gemm_fp6_set_half: 0 = the 128 x 512 tile, one workgroup per CU; 1 (default) = the dX
 // launches (residual plane) on 64 x 512 tiles, two 4-wave workgroups per CU; 2 = the dW launches
-// (4 planes) too.  g_half_ticks: the first-round stagger of the second workgroup on each CU.
+// (4 planes) too; 3 / 4 = 1 / 2 with the FP4 operand staged through LDS (in modes 1 and 2 a half
+// tile whose B arrives in panels loads its B fragments straight into registers: gemm_fp6_k's BREG).
+// g_half_ticks: the first-round stagger of the second workgroup on each CU.
 // Measured on the wide step's shapes (profiles/r06_b_fp6_half.log, one box, interleaved): dX + res
 // 8.83 -> 8.31 ms with no stagger (40-200 us: 8.32-8.35), dW 7.12 -> 7.30-7.37 (kept on the 128 x
 // 512 tile).  The two residents of a CU (blocks b and b + 256 in the first round,
@@ -1362,18 +1457,22 @@ static int gemm_fp6_impl(const uint8_t* alo, const uint8_t* ahi, const uint8_t* 
 // Whether a launch takes the persistent form of the default tile (gemm_fp6_pers_k, selected by
 // bnn_gemm_fp6_set_persistent): no bias, B in panels, whole K per tile, a 128 x 512-tiled shape of at
 // least two rounds of tiles.  One predicate for gemm_fp6_impl and the name bnn_gemm_fp6_kernel_k reports.
-// Whether a launch takes the half-tile form (bnn_gemm_fp6_set_half): mode 1 the residual-plane (dX)
-// launches, mode 2 every launch; no bias, whole K per tile, 64 x 512-tiled shapes of >= 2 rounds of
+// Whether a launch takes the half-tile form (bnn_gemm_fp6_set_half): mode 1 / 3 the residual-plane (dX)
+// launches, mode 2 / 4 every launch; no bias, whole K per tile, 64 x 512-tiled shapes of >= 2 rounds of
 // two workgroups per CU.
 // FP6_HALF_SMALL: also an unsplit grid of under one round of 128 x 512 tiles (config 3's dX), where the
 // half tiles double the workgroups that share the chip.
 #ifndef FP6_HALF_SMALL
 #define FP6_HALF_SMALL 0
 #endif
+// A-ring depth of the half tile with its B fragments in registers (2 or 3; measured in DESIGN.md §5)
+#ifndef FP6_BREG_STAGES
+#define FP6_BREG_STAGES 2
+#endif
 static bool fp6_half_applies(int64_t M, int64_t N, int ksplit, bool has_bias, bool res) {
   if (g_fp6_half <= 0 || has_bias || ksplit > 1 || g_variant6 >= 0 || M % 64 != 0 || N % 512 != 0) return false;
   const int64_t tiles = (M / 64) * (N / 512);
-  if (res || g_fp6_half > 1) return tiles >= 4 * device_cus();
+  if (res || g_fp6_half == 2 || g_fp6_half == 4) return tiles >= 4 * device_cus();
   return FP6_HALF_SMALL && tiles < 2 * device_cus();
 }
 
@@ -1427,12 +1526,17 @@ static int gemm_fp6_impl(const uint8_t* alo, const uint8_t* ahi, const uint8_t* 
     p.stg_ticks = g_half_ticks;
     if (g_half_group > 0) p.group = g_half_group;
   }
+  // B fragments in registers: the half tile in modes 1 / 2 with B in panels (modes 3 / 4 and a
+  // row-major B keep the LDS path)
+  const bool breg = half && panel && g_fp6_half <= 2;
   if (ares) {   // the residual plane runs on the default tile (variant 7) with its own instance
     p.ares = ares;
     if (pers) return launch6_pers<1>(p, device_cus(), S6(stream));
+    if (breg) return launch6<1, 4, 2, 4, FP6_BREG_STAGES, 0, 2, 0, 0, 1, 1>(p, S6(stream));
     if (half) return launch6<1, 4, 2, 4, 2, 0, 2, 0, 0, 1>(p, S6(stream));
     return launch6<2, 4, 2, 4, 2, 0, 2, 0, 0, 1>(p, S6(stream));
   }
+  if (breg) return launch6<1, 4, 2, 4, FP6_BREG_STAGES, 0, 2, 0, 0, 0, 1>(p, S6(stream));
   if (half) return launch6<1, 4, 2, 4, 2>(p, S6(stream));
   if (pers && pl.v->id == 7) return launch6_pers<0>(p, device_cus(), S6(stream));
   return pl.v->fn(p, S6(stream));
@@ -1447,10 +1551,14 @@ BNN_API int bnn_gemm_fp6_set_persistent(int32_t on) {
   return 0;
 }
 
-// The FP6 GEMM's half-tile form (g_fp6_half above): mode 0 / 1 / 2, stagger in microseconds (the
+// The FP6 GEMM's half-tile form (g_fp6_half above): mode 0 .. 4, stagger in microseconds (the
 // first-round wait of the second workgroup on each CU); mode < 0 queries the mode.
 BNN_API int bnn_gemm_fp6_set_half(int32_t mode, double stagger_us) {
   if (mode < 0) return g_fp6_half;
+  if (mode > 4) {
+    set_error("bnn_gemm_fp6_set_half: mode %d (0 .. 4)", (int)mode);
+    return kErrInval;
+  }
   g_fp6_half = mode;
   g_half_ticks = (int64_t)(stagger_us * 100.0);
   return 0;

@@ -334,8 +334,11 @@ int bnn_gemm_fp6_set_persistent(int32_t on);
  * tiles, two 4-wave workgroups per CU, the second resident of each CU held back stagger_us in the
  * first round so one workgroup's fp32 epilogue drains while the other's MFMAs run; mode 2 also the
  * dW launches; 0 = the 128 x 512 tile.  Default 1 (dX + res 8.83 -> 8.31 ms; dW slower on half
- * tiles, profiles/r06_b_fp6_half.log).  Same fragments and accumulation order per output element:
- * bit-identical C.  mode < 0 queries. */
+ * tiles, profiles/r06_b_fp6_half.log).  In modes 1 and 2 a half tile whose B arrives in FP4 panels
+ * loads its B fragments straight into registers (dX + res 8.58 -> 7.99 ms,
+ * profiles/r07_fp6_half_breg_ab.txt); modes 3 and 4 are 1 and 2 with B staged through LDS (A/B and
+ * the tests).  Same fragments and accumulation order per output element in every mode:
+ * bit-identical C.  mode < 0 queries; mode > 4 is an error. */
 int bnn_gemm_fp6_set_half(int32_t mode, double stagger_us);
 int bnn_gemm_fp6_set_half_group(int32_t group);   /* tuning hook: raster group rows of the half-tile form (0 = default) */
 

@@ -4,7 +4,10 @@ tiles, two workgroups per CU, bnn_gemm_fp6_set_half) at several first-round stag
 the residual plane (as the wide step's dX launches), dW the four planes.  Every form's C is checked
 bit-identical to the default's.
 
-    python tools/fp6_half_ab.py "0:0 1:0 1:65 1:130" [rounds] [reps]     (mode:stagger_us[:group]; dW uses mode 2)
+    python tools/fp6_half_ab.py "0:0 3:0 1:0 1:65" [rounds] [reps]     (mode:stagger_us[:group])
+
+Mode 1 = the half tile with its B fragments loaded straight into registers, 3 = with B staged through
+LDS; the dW launches carry no residual plane and run mode 2 for 1 and 4 for 3.
 """
 import os
 import statistics
@@ -38,7 +41,7 @@ def main():
 
         def run(c):
             mode, st, grp = c
-            L.call("bnn_gemm_fp6_set_half", (mode if res or mode == 0 else 2), st)
+            L.call("bnn_gemm_fp6_set_half", (mode if res or mode in (0, 2, 4) else mode + 1), st)
             L.call("bnn_gemm_fp6_set_half_group", grp)
             BF.gemm_fp6(op, None, N, out=C, panels=panels, panel_ks=K // 64)
 
