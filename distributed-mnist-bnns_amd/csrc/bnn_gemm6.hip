@@ -298,6 +298,10 @@ __device__ __forceinline__ void tile6_of(int bid, int gm, int gn, int G, int& tm
 // fragments are double-buffered in registers (2 x 16 VGPRs), one k-step ahead; the A ring may then
 // be three stages deep, RES included (FP6_BREG_STAGES; two measured faster and is the default,
 // DESIGN.md §5).  Same register image as read_b's, same MFMAs in the same order.
+// The 64 x 1024 tile (<1, 8, 2, 4, 2, ..., BREG>: the dW launches, bnn_gemm_fp6_set_wide) is the same
+// loop on 8 waves: 13,312 B per stage, 13 LDS-DMA pieces per k-step (lo 8, hi 4, scales 1) where the
+// 128 x 512 tile issues 41, each wave's 128 columns in panel (n0 + wn*128) / 512, and a two-stage
+// ring (26,624 B) smaller than the epilogue's 8 patches, which size the buffer (32,768 B).
 // DIAG (timing-only builds, wrong results): 1 = no global->LDS staging, 2 = no LDS fragment reads,
 // 3 / 4 = the MFMA stream alone (fragments read once) with / without the per-step barrier, 5 = B
 // staged from contiguous per-k-step panels (as if B were stored [N/BN][K/64][BN][32 B]), 6 = 5 +
@@ -331,10 +335,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
   constexpr int ST = LO_ST + HI_ST + SC_PAD + B_ST + R_ST;
   static_assert(!RES || (PP == 0 && DIAG == 0 && (STAGES == 2 || BREG)),
                 "the residual plane: the plain two-stage loop, or the BREG loop");
-  static_assert(STAGES * ST >= NW * 4096, "the epilogue's per-wave patches lie in the ring");
+  // the epilogue's per-wave patches lie in the ring; a ring smaller than them (the 64 x 1024 BREG tile
+  // at two stages: 26,624 B against 8 x 4,096) is sized to the patches
+  static_assert(BREG || STAGES * ST >= NW * 4096, "the epilogue's per-wave patches lie in the ring");
   constexpr int I_LO = LO_ST / 1024, I_HI = HI_ST / 1024, I_SC = SC_PAD / 1024, I_B = B_ST / 1024;
   constexpr int PER_WAVE = (I_LO + I_HI + I_B) / NW + 1;   // wave 0 also issues the scale piece
-  __shared__ __attribute__((aligned(16))) char smem[STAGES * ST];
+  __shared__ __attribute__((aligned(16))) char smem[STAGES * ST > NW * 4096 ? STAGES * ST : NW * 4096];
 
   const int lane = threadIdx.x & 63, wave = wave_id();
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
@@ -360,8 +366,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
   // scale piece); each piece's per-lane source offset (row clamped to the last valid row -- its
   // results are never stored -- and the XOR-swizzled 16-B chunk: the LDS image stays linear) is
   // k-invariant and computed once, so a stage is a wave-uniform base advance + the saddr-form DMA.
-  static_assert(I_LO % NW == 0 && I_HI % NW == 0 && I_B % NW == 0 && I_SC == 1, "piece split");
-  constexpr int P_LO = I_LO / NW, P_HI = I_HI / NW, P_B = I_B / NW;
+  // BREG with fewer hi pieces than waves (the 64 x 1024 tile: 8 lo, 4 hi, 8 waves): hi piece i is wave
+  // HI_OFF + i's, the LAST I_HI waves, so that wave 0 (the scale piece) issues none and the per-wave
+  // counts are two, P_LO and P_LO + 1, as the counted waits of the BREG loop assume.
+  constexpr bool HI_EVEN = I_HI % NW == 0;
+  static_assert(I_LO % NW == 0 && I_B % NW == 0 && I_SC == 1 && (HI_EVEN || (BREG && !RES && I_HI < NW)), "piece split");
+  constexpr int P_LO = I_LO / NW, P_HI = (I_HI + NW - 1) / NW, P_B = I_B / NW;
+  constexpr int HI_OFF = HI_EVEN ? 0 : NW - I_HI;
+  const int hwave = wave - HI_OFF;          // this wave's first hi piece (< 0: none)
   uint32_t off_lo[P_LO], off_hi[P_HI], off_b[P_B > 0 ? P_B : 1];
 #pragma unroll
   for (int ii = 0; ii < P_LO; ++ii) {
@@ -371,7 +383,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
   }
 #pragma unroll
   for (int ii = 0; ii < P_HI; ++ii) {
-    const int i = wave + ii * NW;
+    const int i = (HI_EVEN ? wave : max(hwave, 0)) + ii * NW;
     const int lrow = i * 16 + (lane >> 2), c = lane & 3;
     off_hi[ii] = DIAG == 6 ? (uint32_t)lrow * 64u + 16u * (uint32_t)(c ^ ((lrow >> 2) & 3))
                            : (uint32_t)min(lrow, p.M - 1 - m0) * (uint32_t)(nblk * 32) + 16u * (uint32_t)(c ^ ((lrow >> 2) & 3));
@@ -390,7 +402,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
   // beyond N are the panel's padding, staged unclamped: zero in every producer's buffer
   // (bnn_fp4_panelize writes them, functional._qt_buffer zeroes them for the packing kernels) and
   // in any case only ever multiplied into output columns >= N, which are neither stored nor reduced
-  const uint8_t* b_base = p.bks > 0 ? p.b + ((int64_t)(n0 / FP4_PANEL) * p.bks + ks0) * (FP4_PANEL * 32) + (n0 % FP4_PANEL) * 32
+  // a tile wider than a panel (BREG, BN = 1024): the base is the wave's own, its 128 columns
+  // n0 + wn*128 .. lie in panel (n0 + wn*128) / 512 -- still wave-uniform, in SGPRs
+  static_assert(BN <= FP4_PANEL || (BREG && BN % FP4_PANEL == 0 && FP4_PANEL % (WN * 32) == 0), "tile columns and panels");
+  const int nb0 = BN > FP4_PANEL ? n0 + wn * WN * 32 : n0;
+  const uint8_t* b_base = p.bks > 0 ? p.b + ((int64_t)(nb0 / FP4_PANEL) * p.bks + ks0) * (FP4_PANEL * 32) + (nb0 % FP4_PANEL) * 32
                                     : p.b + (int64_t)n0 * p.ldb + (int64_t)ks0 * 32;
   const int64_t b_step = (DIAG >= 5) ? BN * 32 : (p.bks > 0 ? FP4_PANEL * 32 : 32);
   // the residual plane: I_R pieces of 32 rows x 32 B, one per wave (waves >= I_R issue none; the
@@ -414,8 +430,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
     for (int ii = 0; ii < P_LO; ++ii)
       glds16_6s(lo_base + (int64_t)kt * 128, off_lo[ii], base + (wave + ii * NW) * 1024);
 #pragma unroll
-    for (int ii = 0; ii < P_HI; ++ii)
-      glds16_6s(hi_base + (int64_t)kt * (DIAG == 6 ? BM * 64 : 64), off_hi[ii], base + LO_ST + (wave + ii * NW) * 1024);
+    for (int ii = 0; ii < P_HI; ++ii) {
+      if constexpr (HI_EVEN)
+        glds16_6s(hi_base + (int64_t)kt * (DIAG == 6 ? BM * 64 : 64), off_hi[ii], base + LO_ST + (wave + ii * NW) * 1024);
+      else if (hwave >= 0)
+        glds16_6s(hi_base + (int64_t)kt * 64, off_hi[ii], base + LO_ST + hwave * 1024);
+    }
 #pragma unroll
     for (int ii = 0; ii < P_B; ++ii)
       glds16_6s(b_base + (int64_t)kt * b_step, off_b[ii], base + LO_ST + HI_ST + SC_PAD + (wave + ii * NW) * 1024);
@@ -781,9 +801,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void gemm_fp6_k(Gemm6P
     // count) with three stages while a step kt+1 exists, vmcnt(0) with two stages and on the last
     // step.  No B load is issued past the last k-step, so none is in flight when the registers
     // are reused; the epilogue's vmcnt(0) finds nothing of B's.
-    constexpr int NA = P_LO + P_HI;
-    const bool extra = wave < 1 + I_R;
-    const uint32_t off_bf = (uint32_t)((wn * WN * 32 + r) * 32 + h * 16);
+    // Uneven hi split (the 64 x 1024 tile: P_LO = 1, 4 hi pieces on waves 4 .. 7): NA = P_LO and the
+    // waves with one piece more are wave 0 (scales) and waves HI_OFF .. NW-1 (hi):
+    //   wave 0      A(k) = lo sc     waves 1 .. 3  A(k) = lo     waves 4 .. 7  A(k) = lo hi
+    // so vmcnt(2) / vmcnt(1) / vmcnt(2) retire A(kt) B(kt) ahead of A(kt+1) at three stages.
+    constexpr int NA = P_LO + (HI_EVEN ? P_HI : 0);
+    const bool extra = HI_EVEN ? wave < 1 + I_R : (wave == 0 || hwave >= 0);
+    const uint32_t off_bf = (uint32_t)(((BN > FP4_PANEL ? 0 : wn * WN * 32) + r) * 32 + h * 16);
     v4i b0[WN], b1[WN];
     auto load_b = [&](int kt, v4i (&bf)[WN]) __attribute__((always_inline)) {
       gload_b6(b_base + (int64_t)kt * b_step, off_bf, bf[0], bf[1], bf[2], bf[3]);
@@ -1348,6 +1372,15 @@ int g_fp6_half = 1;
 int64_t g_half_ticks = 0;
 int g_half_group = 0;   // raster group rows of the half-tile form (0: as the 128 x 512 tile's, 4 / 8)
 
+// bnn_gemm_fp6_set_wide: the 4-plane (dW) launches with B in panels run on 64 x 1024 tiles -- one
+// wave row of 8 waves, so every B row has one reader and the B fragments go straight into registers
+// (gemm_fp6_k's BREG) on a tile as large as the default's.  0 = off; 1 (default) = on grids of at
+// least two rounds of tiles; 2 = on every shape the tile divides (the tests).  Measured on the wide
+// step's dW shape (profiles/r08_fp6_wide_ab.log, one box, interleaved): 6.95 -> 6.50 ms.
+// g_wide_group: raster group rows of that form (0: as the 128 x 512 tile's, 4 / 8 by K).
+int g_fp6_wide = 1;
+int g_wide_group = 0;
+
 const Variant6* find6(int id) {
   for (const Variant6& v : kVariants6)
     if (v.id == id) return &v;
@@ -1436,9 +1469,13 @@ static int device_cus() {
 #ifndef FP6_SPLIT_CAP
 #define FP6_SPLIT_CAP 8
 #endif
+static bool fp6_wide_shape(int64_t M, int64_t N) { return M > 0 && N > 0 && M % 64 == 0 && N % 1024 == 0; }
+
 static Fp6Plan plan6(int64_t M, int64_t N, int64_t K) {
   if (g_variant6 >= 0) return Fp6Plan{find6(g_variant6), 1};
   const Variant6* v = find6(7);
+  // the forced B-in-registers form (tests) takes a shape whatever its grid: never split
+  if (g_fp6_wide == 2 && g_fp6_half == 1 && fp6_wide_shape(M, N)) return Fp6Plan{v, 1};
   const int64_t tiles = ((M + v->bm - 1) / v->bm) * ((N + v->bn - 1) / v->bn), ncu = device_cus();
   const int64_t s = std::min<int64_t>(std::min<int64_t>(ncu / std::max<int64_t>(tiles, 1), (K / 64) / 4), FP6_SPLIT_CAP);
   return Fp6Plan{v, (int)std::max<int64_t>(1, s)};
@@ -1474,6 +1511,19 @@ static bool fp6_half_applies(int64_t M, int64_t N, int ksplit, bool has_bias, bo
   const int64_t tiles = (M / 64) * (N / 512);
   if (res || g_fp6_half == 2 || g_fp6_half == 4) return tiles >= 4 * device_cus();
   return FP6_HALF_SMALL && tiles < 2 * device_cus();
+}
+
+// Whether a launch takes the 64 x 1024 tile with B in registers (bnn_gemm_fp6_set_wide): the 4-plane
+// launches only (no residual plane, no bias), whole K per tile, B in panels, the default plan,
+// bnn_gemm_fp6_set_half at its default 1, not persistent, M % 64 == 0, N % 1024 == 0 and (mode 1)
+// at least two rounds of tiles.  The B loads are unclamped: N % 1024 == 0 keeps every row inside
+// the N / 512 panels, and bnn_gemm_fp6_panel_ws has checked bks >= K / 64.
+static const char* const kWideName = "gemm_fp6_k<1, 8, 2, 4, 2, 0, 2, 0, 0, 0, 1>";
+static bool fp6_wide_applies(int64_t M, int64_t N, int ksplit, bool has_bias, bool res, bool panel) {
+  if (g_fp6_wide <= 0 || g_fp6_half != 1 || g_fp6_pers || g_variant6 >= 0 || res || has_bias || !panel || ksplit > 1 ||
+      !fp6_wide_shape(M, N))
+    return false;
+  return g_fp6_wide == 2 || (M / 64) * (N / 1024) >= 2 * device_cus();
 }
 
 static bool fp6_pers_applies(int64_t M, int64_t N, int ksplit, bool has_bias, bool panel) {
@@ -1538,6 +1588,10 @@ static int gemm_fp6_impl(const uint8_t* alo, const uint8_t* ahi, const uint8_t* 
   }
   if (breg) return launch6<1, 4, 2, 4, FP6_BREG_STAGES, 0, 2, 0, 0, 0, 1>(p, S6(stream));
   if (half) return launch6<1, 4, 2, 4, 2>(p, S6(stream));
+  if (fp6_wide_applies(M, N, p.ksplit, bias != nullptr, false, panel)) {
+    if (g_wide_group > 0) p.group = g_wide_group;
+    return launch6<1, 8, 2, 4, 2, 0, 2, 0, 0, 0, 1>(p, S6(stream));
+  }
   if (pers && pl.v->id == 7) return launch6_pers<0>(p, device_cus(), S6(stream));
   return pl.v->fn(p, S6(stream));
 }
@@ -1561,6 +1615,23 @@ BNN_API int bnn_gemm_fp6_set_half(int32_t mode, double stagger_us) {
   }
   g_fp6_half = mode;
   g_half_ticks = (int64_t)(stagger_us * 100.0);
+  return 0;
+}
+
+// The B-in-registers form of the 4-plane launches (g_fp6_wide above): mode 0 .. 2; mode < 0 queries.
+BNN_API int bnn_gemm_fp6_set_wide(int32_t mode) {
+  if (mode < 0) return g_fp6_wide;
+  if (mode > 2) {
+    set_error("bnn_gemm_fp6_set_wide: mode %d (0 .. 2)", (int)mode);
+    return kErrInval;
+  }
+  g_fp6_wide = mode;
+  return 0;
+}
+
+// Tuning hook: raster group (tile rows per group, tile6_of) of that form; 0 = default.
+BNN_API int bnn_gemm_fp6_set_wide_group(int32_t g) {
+  g_wide_group = g < 0 ? 0 : g;
   return 0;
 }
 
@@ -1655,6 +1726,7 @@ BNN_API const char* bnn_gemm_fp6_kernel_kr(int64_t M, int64_t N, int64_t K, int3
   const Fp6Plan pl = plan6(M, N, K);
   if (!fp6_pers_applies(M, N, pl.ksplit, false, true) && fp6_half_applies(M, N, pl.ksplit, false, res != 0))
     return "gemm_fp6_k<1, 4, 2, 4, 2>";
+  if (fp6_wide_applies(M, N, pl.ksplit, false, res != 0, true)) return kWideName;
   return bnn_gemm_fp6_kernel_k(M, N, K);
 }
 

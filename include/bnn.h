@@ -341,6 +341,15 @@ int bnn_gemm_fp6_set_persistent(int32_t on);
  * bit-identical C.  mode < 0 queries; mode > 4 is an error. */
 int bnn_gemm_fp6_set_half(int32_t mode, double stagger_us);
 int bnn_gemm_fp6_set_half_group(int32_t group);   /* tuning hook: raster group rows of the half-tile form (0 = default) */
+/* 64 x 1024 tile of the 4-plane (dW) launches, the FP4 operand's fragments loaded straight into
+ * registers instead of through LDS (one wave row of 8 waves: every B row has one reader): taken
+ * with no residual plane, no bias, whole K per tile, B in panels, the default plan,
+ * bnn_gemm_fp6_set_half at its default 1, M % 64 == 0 and N % 1024 == 0.  0 = off; 1 (default) = on
+ * grids of at least two rounds of tiles (dW 6.95 -> 6.50 ms, profiles/r08_fp6_wide_ab.log); 2 = on
+ * every such shape, whatever the grid (the tests).  Same fragments and accumulation order per
+ * output element: bit-identical C.  mode < 0 queries; mode > 2 is an error. */
+int bnn_gemm_fp6_set_wide(int32_t mode);
+int bnn_gemm_fp6_set_wide_group(int32_t group);   /* tuning hook: raster group rows of that form (0 = default) */
 
 /* XNOR/AND-popcount VALU GEMM on bit-planes (same contract as the (1,1) form):
  * C[m][n] = sum_w popc(nzA&nzB) - 2*popc(nzA&nzB&(sA^sB)) + bias[n]; kw = words per row
