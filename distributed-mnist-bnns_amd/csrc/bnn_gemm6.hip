@@ -1273,9 +1273,21 @@ __global__ __launch_bounds__(256) void gemm6_splitk_sum_k(const float* __restric
   }
 }
 
+int device_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    cus = n;
+  }
+  return cus;
+}
+
 template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int DIAG = 0, int OCC = 2, int PP = 0,
           int BNS = 0, int RES = 0, int BREG = 0>
-int launch6(Gemm6Params p, hipStream_t s) {
+int launch_gemm_fp6_k(Gemm6Params p, hipStream_t s) {
   constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
   p.gm = (p.M + BM - 1) / BM;
   p.gn = (p.N + BN - 1) / BN;
@@ -1291,108 +1303,275 @@ int launch6(Gemm6Params p, hipStream_t s) {
   return check_launch("bnn_gemm_fp6");
 }
 
-// The persistent form (gemm_fp6_pers_k) for grids of at least two rounds, no bias / split-K: measured
-// slower than one workgroup per tile on both backward shapes (dX 8.52 vs 8.60 ms with the row-0
-// waves staging every stage, dW 7.2-7.3 vs 6.85-6.89; sharing the staging again after the first 16
-// k-steps: dX 9.27, dW 7.80 -- profiles/r05_fp6_persistent_ab.log), so off by default (A/B switch).
-int g_fp6_pers = 0;
-
+// The persistent form: one workgroup per CU (the launchers of every instance share one signature)
 template <int RES>
-int launch6_pers(Gemm6Params p, int ncu, hipStream_t s) {
+int launch_gemm_fp6_pers_k(Gemm6Params p, hipStream_t s) {
   p.gm = (p.M + 127) / 128;
   p.gn = (p.N + 511) / 512;
   const int ntiles = p.gm * p.gn;
-  hipLaunchKernelGGL((gemm_fp6_pers_k<RES>), dim3((unsigned)std::min(ntiles, ncu)), dim3(512), 0, s, p);
+  hipLaunchKernelGGL((gemm_fp6_pers_k<RES>), dim3((unsigned)std::min(ntiles, device_cus())), dim3(512), 0, s, p);
   return check_launch("bnn_gemm_fp6 (persistent)");
 }
 
-struct Variant6 {
+#ifndef FP6_SPLIT_CAP
+#define FP6_SPLIT_CAP 8
+#endif
+// FP6_HALF_SMALL: the half tile also on an unsplit grid of under one round of 128 x 512 tiles (config
+// 3's dX), where the half tiles double the workgroups that share the chip.
+#ifndef FP6_HALF_SMALL
+#define FP6_HALF_SMALL 0
+#endif
+// A-ring depth of the half tile with its B fragments in registers (2 or 3; measured in DESIGN.md §5)
+#ifndef FP6_BREG_STAGES
+#define FP6_BREG_STAGES 2
+#endif
+
+// ------------------------------------------------------------------------------------------------
+// Dispatch.  One table of the gemm_fp6_k / gemm_fp6_pers_k instances the library can launch -- (row
+// id, label, tile rows and columns, the kernel and its template arguments) -- and one decision
+// function, select6, that maps a launch (shape, residual plane, bias, B layout, workspace) and the
+// process-global switches to a row plus the run-time launch choices.  The launching entries call the
+// row's launcher and the name queries read the row's strings, so the query cannot disagree with the
+// launch and a new table row is launched, named and listed at once.  The exact instance string is
+// generated from the row's template arguments; the label is what bnn_gemm_fp6_kernel / _kernel_k /
+// _kernel_kr report (the timer keys of bench.py and the committed profiles): the row's own string, the
+// string of the row whose tile it runs on, or free text.
+// Ids below 100 are the variants of bnn_gemm_fp6_set_variant (A/B and the tuning sweeps); from 100 on,
+// the forms that only select6 chooses: the default tile with the residual plane (Res), the half tile
+// (through LDS without the plane: variant 14), Breg = B fragments in registers, the 64 x 1024 tile, Bns =
+// the BatchNorm-backward statistics epilogue, the persistent form.
+enum { kRowRes = 100, kRowHalfRes, kRowHalfBreg, kRowHalfBregRes, kRowWide, kRowBns, kRowBnsRes, kRowPers, kRowPersRes };
+#define FP6_SELF nullptr, -1         // label: the row's own instance string
+#define FP6_AS(ID) nullptr, ID       // label: as row ID's
+#define FP6_TEXT(S) S, -1            // label: free text
+#define BNN_FP6_INSTANCES(X) \
+  X(0, FP6_SELF, 256, 256, gemm_fp6_k, 2, 4, 4, 2, 2) \
+  X(1, FP6_SELF, 128, 256, gemm_fp6_k, 2, 4, 2, 2, 3) \
+  X(2, FP6_SELF, 128, 128, gemm_fp6_k, 2, 2, 2, 2, 3) \
+  X(3, FP6_SELF, 256, 256, gemm_fp6_k, 4, 2, 2, 4, 2) \
+  X(4, FP6_SELF, 128, 256, gemm_fp6_k, 2, 4, 2, 2, 4) \
+  /* tall-N tiles: the FP6 operand costs 3 B/element against 0.5 for FP4, so BM x BN = 128 x 512 */ \
+  /* moves 29% fewer bytes per MAC than 256 x 256 and leaves room for a third stage */ \
+  X(5, FP6_SELF, 128, 512, gemm_fp6_k, 2, 4, 2, 4, 3) \
+  X(6, FP6_SELF, 128, 512, gemm_fp6_k, 1, 8, 4, 2, 3) \
+  /* the default: the FP6 operand is 6x the bytes of the FP4 one per row, so tall-N tiles move the */ \
+  /* fewest bytes per MAC, for every shape */ \
+  X(7, FP6_SELF, 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2) \
+  /* two workgroups per CU (OCC 4: <= 128 registers per lane) */ \
+  X(8, FP6_SELF, 128, 256, gemm_fp6_k, 2, 4, 2, 2, 2, 0, 4) \
+  /* software-pipelined k loop (PP): 128 x 512 and 128 x 256 tiles */ \
+  X(10, FP6_SELF, 128, 512, gemm_fp6_k, 2, 4, 2, 4, 3, 0, 2, 1) \
+  X(11, FP6_SELF, 128, 256, gemm_fp6_k, 2, 4, 2, 2, 3, 0, 2, 1) \
+  /* pipelined form 2: 128 x 512 tile, every wave 32 rows x 256 columns (4 x 2 waves) */ \
+  X(12, FP6_SELF, 128, 512, gemm_fp6_k, 4, 2, 1, 8, 3, 0, 2, 2) \
+  X(13, FP6_SELF, 128, 256, gemm_fp6_k, 4, 1, 1, 8, 3, 0, 2, 2) \
+  /* 4-wave workgroups small enough in LDS for two per CU: one workgroup's barrier wait or */ \
+  /* epilogue overlaps the other's MFMAs (14 is also the half tile through LDS, select6) */ \
+  X(14, FP6_SELF, 64, 512, gemm_fp6_k, 1, 4, 2, 4, 2) \
+  X(15, FP6_SELF, 128, 256, gemm_fp6_k, 2, 2, 2, 4, 2) \
+  /* ping-pong: the two wave rows run a phase apart, one group's MFMAs beside the other's reads */ \
+  /* (equal to variant 7 within 1% on the wide shapes: the MFMA-busy fraction stays ~0.6 -- */ \
+  /* profiles/r02_fp6_pingpong.txt) */ \
+  X(16, FP6_SELF, 128, 512, gemm_fp6_k, 2, 4, 2, 4, 3, 0, 2, 3) \
+  /* interleaved form: all fragment reads right after the barrier, the next stage's DMA pieces */ \
+  /* spread between the MFMA column groups */ \
+  X(17, FP6_SELF, 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 0, 2, 4) \
+  X(18, FP6_SELF, 128, 512, gemm_fp6_k, 2, 4, 2, 4, 3, 0, 2, 4) \
+  /* timing-only diagnostics of variant 5 (wrong results; never picked by default) */ \
+  X(91, FP6_TEXT("diag: v5 without global->LDS staging"), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 3, 1) \
+  X(92, FP6_TEXT("diag: v5 without LDS fragment reads"), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 3, 2) \
+  /* timing-only diagnostics of variant 7 (the wide default) */ \
+  X(93, FP6_TEXT("diag: v7 MFMA stream + barrier"), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 3) \
+  X(94, FP6_TEXT("diag: v7 MFMA stream only"), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 4) \
+  X(95, FP6_TEXT("diag: v7 without global->LDS staging"), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 1) \
+  X(96, FP6_TEXT("diag: v7 without LDS fragment reads"), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 2) \
+  X(97, FP6_TEXT("diag: v7 with B staged from contiguous panels"), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 5) \
+  X(98, FP6_TEXT("diag: v7 with B and A hi staged from contiguous panels"), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 6) \
+  X(kRowRes, FP6_AS(7), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 0, 2, 0, 0, 1) \
+  X(kRowHalfRes, FP6_AS(14), 64, 512, gemm_fp6_k, 1, 4, 2, 4, 2, 0, 2, 0, 0, 1) \
+  X(kRowHalfBreg, FP6_AS(14), 64, 512, gemm_fp6_k, 1, 4, 2, 4, FP6_BREG_STAGES, 0, 2, 0, 0, 0, 1) \
+  X(kRowHalfBregRes, FP6_AS(14), 64, 512, gemm_fp6_k, 1, 4, 2, 4, FP6_BREG_STAGES, 0, 2, 0, 0, 1, 1) \
+  X(kRowWide, FP6_SELF, 64, 1024, gemm_fp6_k, 1, 8, 2, 4, 2, 0, 2, 0, 0, 0, 1) \
+  X(kRowBns, FP6_AS(7), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 0, 2, 0, 1) \
+  X(kRowBnsRes, FP6_AS(7), 128, 512, gemm_fp6_k, 2, 4, 2, 4, 2, 0, 2, 0, 1, 1) \
+  X(kRowPers, FP6_TEXT("gemm_fp6_pers_k<2, 4, 2, 4, 2>"), 128, 512, gemm_fp6_pers_k, 0) \
+  X(kRowPersRes, FP6_AS(kRowPers), 128, 512, gemm_fp6_pers_k, 1)
+
+struct Inst6 {
   int id;
-  const char* name;
-  int (*fn)(Gemm6Params, hipStream_t);
-  int bm;   // rows per tile (the scale array must hold round_up(M, bm) rows... see bnn_gemm_fp6)
-  int bn;   // columns per tile
+  const char* text;   // the label as free text, or
+  int as;             // the row whose label this one shares (-1 with no text: its own instance string)
+  int bm, bn;         // rows and columns per tile
+  const char* name;   // the exact instance, "kernel<template arguments>"
+  int (*launch)(Gemm6Params, hipStream_t);
 };
+#define BNN_STR_(...) #__VA_ARGS__
+#define BNN_STR(...) BNN_STR_(__VA_ARGS__)   // two levels: FP6_BREG_STAGES expands before it is stringized
+#define BNN_X(ID, LABEL, BM, BN, KERNEL, ...) \
+  {ID, LABEL, BM, BN, #KERNEL "<" BNN_STR(__VA_ARGS__) ">", launch_##KERNEL<__VA_ARGS__>},
+const Inst6 kInst6[] = {BNN_FP6_INSTANCES(BNN_X)};
+#undef BNN_X
 
-const Variant6 kVariants6[] = {
-    {0, "gemm_fp6_k<2, 4, 4, 2, 2>", launch6<2, 4, 4, 2, 2>, 256, 256},
-    {1, "gemm_fp6_k<2, 4, 2, 2, 3>", launch6<2, 4, 2, 2, 3>, 128, 256},
-    {2, "gemm_fp6_k<2, 2, 2, 2, 3>", launch6<2, 2, 2, 2, 3>, 128, 128},
-    {3, "gemm_fp6_k<4, 2, 2, 4, 2>", launch6<4, 2, 2, 4, 2>, 256, 256},
-    {4, "gemm_fp6_k<2, 4, 2, 2, 4>", launch6<2, 4, 2, 2, 4>, 128, 256},
-    // tall-N tiles: the FP6 operand costs 3 B/element against 0.5 for FP4, so BM x BN = 128 x 512
-    // moves 29% fewer bytes per MAC than 256 x 256 and leaves room for a third stage
-    {5, "gemm_fp6_k<2, 4, 2, 4, 3>", launch6<2, 4, 2, 4, 3>, 128, 512},
-    {6, "gemm_fp6_k<1, 8, 4, 2, 3>", launch6<1, 8, 4, 2, 3>, 128, 512},
-    {7, "gemm_fp6_k<2, 4, 2, 4, 2>", launch6<2, 4, 2, 4, 2>, 128, 512},
-    // two workgroups per CU (OCC 4: <= 128 registers per lane)
-    {8, "gemm_fp6_k<2, 4, 2, 2, 2, 0, 4>", launch6<2, 4, 2, 2, 2, 0, 4>, 128, 256},
-    // software-pipelined k loop (PP): 128 x 512 and 128 x 256 tiles
-    {10, "gemm_fp6_k<2, 4, 2, 4, 3, 0, 2, 1>", launch6<2, 4, 2, 4, 3, 0, 2, 1>, 128, 512},
-    {11, "gemm_fp6_k<2, 4, 2, 2, 3, 0, 2, 1>", launch6<2, 4, 2, 2, 3, 0, 2, 1>, 128, 256},
-    // pipelined form 2: 128 x 512 tile, every wave 32 rows x 256 columns (4 x 2 waves)
-    {12, "gemm_fp6_k<4, 2, 1, 8, 3, 0, 2, 2>", launch6<4, 2, 1, 8, 3, 0, 2, 2>, 128, 512},
-    {13, "gemm_fp6_k<4, 1, 1, 8, 3, 0, 2, 2>", launch6<4, 1, 1, 8, 3, 0, 2, 2>, 128, 256},
-    // 4-wave workgroups small enough in LDS for two per CU: one workgroup's barrier wait or
-    // epilogue overlaps the other's MFMAs
-    {14, "gemm_fp6_k<1, 4, 2, 4, 2>", launch6<1, 4, 2, 4, 2>, 64, 512},
-    {15, "gemm_fp6_k<2, 2, 2, 4, 2>", launch6<2, 2, 2, 4, 2>, 128, 256},
-    // ping-pong: the two wave rows run a phase apart, one group's MFMAs beside the other's reads
-    // (equal to variant 7 within 1% on the wide shapes: the MFMA-busy fraction stays ~0.6 --
-    // profiles/r02_fp6_pingpong.txt)
-    {16, "gemm_fp6_k<2, 4, 2, 4, 3, 0, 2, 3>", launch6<2, 4, 2, 4, 3, 0, 2, 3>, 128, 512},
-    // interleaved form: all fragment reads right after the barrier, the next stage's DMA pieces
-    // spread between the MFMA column groups
-    {17, "gemm_fp6_k<2, 4, 2, 4, 2, 0, 2, 4>", launch6<2, 4, 2, 4, 2, 0, 2, 4>, 128, 512},
-    {18, "gemm_fp6_k<2, 4, 2, 4, 3, 0, 2, 4>", launch6<2, 4, 2, 4, 3, 0, 2, 4>, 128, 512},
-    // timing-only diagnostics of variant 5 (wrong results; never picked by default)
-    {91, "diag: v5 without global->LDS staging", launch6<2, 4, 2, 4, 3, 1>, 128, 512},
-    {92, "diag: v5 without LDS fragment reads", launch6<2, 4, 2, 4, 3, 2>, 128, 512},
-    // timing-only diagnostics of variant 7 (the wide default)
-    {93, "diag: v7 MFMA stream + barrier", launch6<2, 4, 2, 4, 2, 3>, 128, 512},
-    {94, "diag: v7 MFMA stream only", launch6<2, 4, 2, 4, 2, 4>, 128, 512},
-    {95, "diag: v7 without global->LDS staging", launch6<2, 4, 2, 4, 2, 1>, 128, 512},
-    {96, "diag: v7 without LDS fragment reads", launch6<2, 4, 2, 4, 2, 2>, 128, 512},
-    {97, "diag: v7 with B staged from contiguous panels", launch6<2, 4, 2, 4, 2, 5>, 128, 512},
-    {98, "diag: v7 with B and A hi staged from contiguous panels", launch6<2, 4, 2, 4, 2, 6>, 128, 512},
-};
-
-int g_variant6 = -1;
-// bnn_gemm_fp6_set_half: 0 = the 128 x 512 tile, one workgroup per CU; 1 (default) = the dX
-// launches (residual plane) on 64 x 512 tiles, two 4-wave workgroups per CU; 2 = the dW launches
-// (4 planes) too; 3 / 4 = 1 / 2 with the FP4 operand staged through LDS (in modes 1 and 2 a half
-// tile whose B arrives in panels loads its B fragments straight into registers: gemm_fp6_k's BREG).
-// g_half_ticks: the first-round stagger of the second workgroup on each CU.
-// Measured on the wide step's shapes (profiles/r06_b_fp6_half.log, one box, interleaved): dX + res
-// 8.83 -> 8.31 ms with no stagger (40-200 us: 8.32-8.35), dW 7.12 -> 7.30-7.37 (kept on the 128 x
-// 512 tile).  The two residents of a CU (blocks b and b + 256 in the first round,
-// tools/probes/probe_wg_placement.hip) drift apart by themselves once their tiles' epilogues and
-// barrier waits differ, so one's fp32 stores drain beside the other's MFMAs.
-int g_fp6_half = 1;
-int64_t g_half_ticks = 0;
-int g_half_group = 0;   // raster group rows of the half-tile form (0: as the 128 x 512 tile's, 4 / 8)
-
-// bnn_gemm_fp6_set_wide: the 4-plane (dW) launches with B in panels run on 64 x 1024 tiles -- one
-// wave row of 8 waves, so every B row has one reader and the B fragments go straight into registers
-// (gemm_fp6_k's BREG) on a tile as large as the default's.  0 = off; 1 (default) = on grids of at
-// least two rounds of tiles; 2 = on every shape the tile divides (the tests).  Measured on the wide
-// step's dW shape (profiles/r08_fp6_wide_ab.log, one box, interleaved): 6.95 -> 6.50 ms.
-// g_wide_group: raster group rows of that form (0: as the 128 x 512 tile's, 4 / 8 by K).
-int g_fp6_wide = 1;
-int g_wide_group = 0;
-
-const Variant6* find6(int id) {
-  for (const Variant6& v : kVariants6)
-    if (v.id == id) return &v;
-  return &kVariants6[0];      // unknown id: the first entry (the sweep skips repeated names)
+const Inst6* row6(int id) {
+  for (const Inst6& r : kInst6)
+    if (r.id == id) return &r;
+  return nullptr;
 }
 
-// Default per shape: the 128 x 512 tile (the FP6 operand is 6x the bytes of the FP4 one per row,
-// so tall-N tiles move the fewest bytes per MAC) for every shape; grids below one round of the
-// chip are split along K (plan6).
-const Variant6* pick6(int64_t M, int64_t N) {
-  (void)M, (void)N;
-  return g_variant6 >= 0 ? find6(g_variant6) : find6(7);
+const char* label6(const Inst6& r) { return r.text ? r.text : r.as >= 0 ? label6(*row6(r.as)) : r.name; }
+
+// The process-global switches select6 reads, each with its setter's semantics.
+struct Fp6Switches {
+  // bnn_gemm_fp6_set_variant: >= 0 forces that row of the table (an unknown id: the first row; the
+  // sweeps skip repeated names); a forced variant never splits and takes none of the forms below.
+  int variant = -1;
+  // bnn_gemm_fp6_set_persistent: the persistent form (gemm_fp6_pers_k) for grids of at least two rounds,
+  // no bias / split-K: measured slower than one workgroup per tile on both backward shapes (dX 8.52 vs
+  // 8.60 ms with the row-0 waves staging every stage, dW 7.2-7.3 vs 6.85-6.89; sharing the staging
+  // again after the first 16 k-steps: dX 9.27, dW 7.80 -- profiles/r05_fp6_persistent_ab.log), so off
+  // by default (A/B switch).
+  int pers = 0;
+  // bnn_gemm_fp6_set_half: 0 = the 128 x 512 tile, one workgroup per CU; 1 (default) = the dX
+  // launches (residual plane) on 64 x 512 tiles, two 4-wave workgroups per CU; 2 = the dW launches
+  // (4 planes) too; 3 / 4 = 1 / 2 with the FP4 operand staged through LDS (in modes 1 and 2 a half
+  // tile whose B arrives in panels loads its B fragments straight into registers: gemm_fp6_k's BREG).
+  // half_ticks: the first-round stagger of the second workgroup on each CU.
+  // Measured on the wide step's shapes (profiles/r06_b_fp6_half.log, one box, interleaved): dX + res
+  // 8.83 -> 8.31 ms with no stagger (40-200 us: 8.32-8.35), dW 7.12 -> 7.30-7.37 (kept on the 128 x
+  // 512 tile).  The two residents of a CU (blocks b and b + 256 in the first round,
+  // tools/probes/probe_wg_placement.hip) drift apart by themselves once their tiles' epilogues and
+  // barrier waits differ, so one's fp32 stores drain beside the other's MFMAs.
+  int half = 1;
+  int64_t half_ticks = 0;
+  int half_group = 0;   // raster group rows of the half-tile form (0: as the 128 x 512 tile's, 4 / 8)
+  // bnn_gemm_fp6_set_wide: the 4-plane (dW) launches with B in panels run on 64 x 1024 tiles -- one
+  // wave row of 8 waves, so every B row has one reader and the B fragments go straight into registers
+  // (gemm_fp6_k's BREG) on a tile as large as the default's.  0 = off; 1 (default) = on grids of at
+  // least two rounds of tiles; 2 = on every shape the tile divides (the tests).  Measured on the wide
+  // step's dW shape (profiles/r08_fp6_wide_ab.log, one box, interleaved): 6.95 -> 6.50 ms.
+  int wide = 1;
+  int wide_group = 0;   // raster group rows of that form (0: as the 128 x 512 tile's, 4 / 8 by K)
+} g_fp6;
+
+struct Query6 {
+  int64_t M, N, K;
+  bool res;     // A carries the residual plane
+  bool bias;
+  bool panel;   // B in FP4 panels
+  bool work;    // a usable split-K workspace was passed (the name queries assume one)
+  bool bns;     // the BatchNorm-backward statistics epilogue (bnn_gemm_fp6_bnstats)
+};
+
+struct Choice6 {
+  const Inst6* row = nullptr;    // what the launch runs; nullptr: the launch is refused
+  const Inst6* plan = nullptr;   // the plan's tile: the forced variant or the default (bnn_gemm_fp6_kernel_k's label)
+  int ksplit = 1;
+  int group = 4;                 // raster group rows (tile6_of)
+  bool stagger = false;          // the first-round stagger fields are filled (the half tile only)
+};
+
+// The one decision.  No HIP call but the cached device_cus().
+Choice6 select6(const Query6& q) {
+  const Fp6Switches& sw = g_fp6;
+  const int64_t M = q.M, N = q.N, ncu = device_cus();
+  const bool forced = sw.variant >= 0;
+  Choice6 c;
+  c.group = q.K >= 32768 ? 8 : 4;
+  c.plan = forced && sw.variant < kRowRes && row6(sw.variant) ? row6(sw.variant) : row6(forced ? 0 : 7);
+  // refused: the residual plane has its own instance of the default tile only, and a tile of a
+  // panel launch must lie inside one 512-row panel
+  if (forced && ((q.res && sw.variant != 7) || (q.panel && 512 % c.plan->bn != 0))) return c;
+  // Launch plan of the default kernel for a shape: the 128 x 512 tile, and a grid below one round of
+  // the chip (the MLP's backward GEMMs at batch 4096: 18-192 tiles) split along K into
+  // floor(CUs / tiles) parts of >= 4 k-steps each (the whole-round efficiency of the big tile beats a
+  // smaller tile's finer grid: stream-K on 128 x 256 tiles measured 27-55 us per GEMM against 44 for
+  // the unsplit 192-tile 128 x 512 grid, tools/gpu_r03_sk.sh).  Forced variants never split, and
+  // neither does a shape the forced 64 x 1024 tile (wide mode 2, the tests) may take whatever its grid.
+  // Split-K only with a workspace (else the whole K per tile); the result depends on the shape only --
+  // never on C's alignment or pitch: a gradient written straight into a bucket view must equal the
+  // one AccumulateGrad would add.
+  const bool wide_shape = M > 0 && N > 0 && M % 64 == 0 && N % 1024 == 0;
+  if (q.work && !forced && !(sw.wide == 2 && sw.half == 1 && wide_shape)) {
+    const int64_t tiles = ((M + c.plan->bm - 1) / c.plan->bm) * ((N + c.plan->bn - 1) / c.plan->bn);
+    const int64_t s = std::min<int64_t>(std::min<int64_t>(ncu / std::max<int64_t>(tiles, 1), (q.K / 64) / 4), FP6_SPLIT_CAP);
+    c.ksplit = (int)std::max<int64_t>(1, s);
+  }
+  // The statistics epilogue exists on the unsplit default tile only, whatever the switches below say.
+  if (q.bns) {
+    if (c.ksplit == 1 && c.plan->id == 7) c.row = row6(q.res ? kRowBnsRes : kRowBns);
+    return c;
+  }
+  // Every form below replaces the default plan's unsplit tile on a launch without bias.
+  const bool whole = !forced && c.ksplit == 1 && !q.bias;
+  // The persistent form of the default tile (bnn_gemm_fp6_set_persistent): B in panels, a
+  // 128 x 512-tiled shape of at least two rounds of tiles.
+  if (sw.pers && whole && q.panel && M % 128 == 0 && N % 512 == 0 && (M / 128) * (N / 512) >= 2 * ncu) {
+    c.row = row6(q.res ? kRowPersRes : kRowPers);
+    return c;
+  }
+  // The half tile (bnn_gemm_fp6_set_half): mode 1 / 3 the residual-plane (dX) launches, mode 2 / 4
+  // every launch, on 64 x 512-tiled shapes of >= 2 rounds of two workgroups per CU (or FP6_HALF_SMALL).
+  // The second resident of each CU in the first round (blocks [CUs, 2 CUs):
+  // tools/probes/probe_wg_placement.hip) is held back half_ticks.  B fragments in registers in modes
+  // 1 / 2 with B in panels; modes 3 / 4 and a row-major B keep the LDS path.
+  if (sw.half > 0 && whole && M % 64 == 0 && N % 512 == 0) {
+    const int64_t tiles = (M / 64) * (N / 512);
+    if (q.res || sw.half == 2 || sw.half == 4 ? tiles >= 4 * ncu : FP6_HALF_SMALL && tiles < 2 * ncu) {
+      const bool breg = q.panel && sw.half <= 2;
+      c.row = row6(breg ? (q.res ? kRowHalfBregRes : kRowHalfBreg) : (q.res ? kRowHalfRes : 14));
+      c.stagger = true;
+      if (sw.half_group > 0) c.group = sw.half_group;
+      return c;
+    }
+  }
+  // The 64 x 1024 tile with B in registers (bnn_gemm_fp6_set_wide): the 4-plane launches only, B in
+  // panels, bnn_gemm_fp6_set_half at its default 1, not persistent, and (mode 1) at least two rounds
+  // of tiles.  The B loads are unclamped: N % 1024 == 0 keeps every row inside the N / 512 panels, and
+  // bnn_gemm_fp6_panel_ws has checked bks >= K / 64.
+  if (sw.wide > 0 && sw.half == 1 && !sw.pers && whole && !q.res && q.panel && wide_shape &&
+      (sw.wide == 2 || (M / 64) * (N / 1024) >= 2 * ncu)) {
+    c.row = row6(kRowWide);
+    if (sw.wide_group > 0) c.group = sw.wide_group;
+    return c;
+  }
+  c.row = q.res ? row6(kRowRes) : c.plan;
+  return c;
+}
+
+// The split-K workspace of a choice: the fp32 partials of every split (gemm6_splitk_sum_k folds float4s)
+int64_t split_bytes6(const Choice6& c, int64_t M, int64_t N) {
+  return c.ksplit > 1 && N % 4 == 0 ? (int64_t)c.ksplit * M * N * (int64_t)sizeof(float) : 0;
+}
+
+// A name of a choice's row, with " split-K S" where split; valid until the thread's next query.
+const char* name6(const char* name, int ksplit) {
+  static thread_local char buf[96];
+  if (ksplit <= 1) return name;
+  snprintf(buf, sizeof buf, "%s split-K %d", name, ksplit);
+  return buf;
+}
+
+// The arguments every GEMM entry checks (ldb < 0: B in panels).
+bool gemm6_args_ok(const uint8_t* alo, const uint8_t* ahi, const uint8_t* asc, int64_t asc_rows, const uint8_t* ares,
+                   const uint8_t* b, int64_t ldb, const float* C, int64_t ldc, int64_t M, int64_t N, int64_t K) {
+  return alo && ahi && asc && b && C && M >= 0 && N >= 0 && K > 0 && K % 64 == 0 &&
+         (ldb < 0 || (ldb >= K / 2 && ldb % 16 == 0)) && ldc >= N && asc_rows >= q6_scale_rows(M) &&
+         asc_rows % 256 == 0 && aligned16(alo) && aligned16(ahi) && aligned16(asc) && aligned16(b) &&
+         (!ares || aligned16(ares)) && M <= 0x7fffffff && N <= 0x7fffffff && K <= 0x7fffffff;
+}
+
+Gemm6Params params6(const uint8_t* alo, const uint8_t* ahi, const uint8_t* asc, int64_t asc_rows, const uint8_t* ares,
+                    const uint8_t* b, int64_t ldb, const float* bias, float* C, int64_t ldc, int64_t M, int64_t N,
+                    int64_t K, const Choice6& c, void* work) {
+  Gemm6Params p{};
+  p.alo = alo, p.ahi = ahi, p.asc = asc, p.asc_rows = asc_rows, p.ares = ares;
+  p.b = b, p.ldb = ldb, p.bks = ldb < 0 ? -ldb : 0;
+  p.bias = bias, p.C = C, p.ldc = ldc;
+  p.M = (int)M, p.N = (int)N, p.K = (int)K;
+  p.group = c.group, p.ksplit = c.ksplit;
+  p.part = c.ksplit > 1 ? reinterpret_cast<float*>(work) : nullptr;
+  if (c.stagger) p.stg_lo = device_cus(), p.stg_hi = 2 * device_cus(), p.stg_ticks = g_fp6.half_ticks;
+  return p;
 }
 
 inline hipStream_t S6(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -1444,91 +1623,34 @@ BNN_API int bnn_quant6_cols_t(const float* x, int64_t M, int64_t N, int64_t ldx,
   return check_launch("bnn_quant6_cols_t");
 }
 
-// Launch plan of the default kernel for a shape: the 128 x 512 tile, and a grid below one round of
-// the chip (the MLP's backward GEMMs at batch 4096: 18-192 tiles) split along K into
-// floor(CUs / tiles) parts of >= 4 k-steps each (the whole-round efficiency of the big tile beats a
-// smaller tile's finer grid: stream-K on 128 x 256 tiles measured 27-55 us per GEMM against 44 for
-// the unsplit 192-tile 128 x 512 grid, tools/gpu_r03_sk.sh).  Forced variants never split.
-struct Fp6Plan {
-  const Variant6* v;
-  int ksplit;
-};
-
-static int device_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    cus = n;
-  }
-  return cus;
-}
-
-#ifndef FP6_SPLIT_CAP
-#define FP6_SPLIT_CAP 8
-#endif
-static bool fp6_wide_shape(int64_t M, int64_t N) { return M > 0 && N > 0 && M % 64 == 0 && N % 1024 == 0; }
-
-static Fp6Plan plan6(int64_t M, int64_t N, int64_t K) {
-  if (g_variant6 >= 0) return Fp6Plan{find6(g_variant6), 1};
-  const Variant6* v = find6(7);
-  // the forced B-in-registers form (tests) takes a shape whatever its grid: never split
-  if (g_fp6_wide == 2 && g_fp6_half == 1 && fp6_wide_shape(M, N)) return Fp6Plan{v, 1};
-  const int64_t tiles = ((M + v->bm - 1) / v->bm) * ((N + v->bn - 1) / v->bn), ncu = device_cus();
-  const int64_t s = std::min<int64_t>(std::min<int64_t>(ncu / std::max<int64_t>(tiles, 1), (K / 64) / 4), FP6_SPLIT_CAP);
-  return Fp6Plan{v, (int)std::max<int64_t>(1, s)};
-}
-
 BNN_API int64_t bnn_gemm_fp6_workspace(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 64 != 0) return 0;
-  const Fp6Plan pl = plan6(M, N, K);
-  return pl.ksplit > 1 && N % 4 == 0 ? (int64_t)pl.ksplit * M * N * (int64_t)sizeof(float) : 0;
+  return split_bytes6(select6(Query6{M, N, K, false, false, true, true, false}), M, N);
 }
 
+// Validate, select, fill the parameters, launch the row.  ldb < 0: B in panels of -ldb k-steps.
 static int gemm_fp6_impl(const uint8_t* alo, const uint8_t* ahi, const uint8_t* asc, int64_t asc_rows,
                          const uint8_t* ares, const uint8_t* b, int64_t ldb, const float* bias, float* C, int64_t ldc,
-                         int64_t M, int64_t N, int64_t K, void* work, int64_t work_bytes, void* stream);
-
-// Whether a launch takes the persistent form of the default tile (gemm_fp6_pers_k, selected by
-// bnn_gemm_fp6_set_persistent): no bias, B in panels, whole K per tile, a 128 x 512-tiled shape of at
-// least two rounds of tiles.  One predicate for gemm_fp6_impl and the name bnn_gemm_fp6_kernel_k reports.
-// Whether a launch takes the half-tile form (bnn_gemm_fp6_set_half): mode 1 / 3 the residual-plane (dX)
-// launches, mode 2 / 4 every launch; no bias, whole K per tile, 64 x 512-tiled shapes of >= 2 rounds of
-// two workgroups per CU.
-// FP6_HALF_SMALL: also an unsplit grid of under one round of 128 x 512 tiles (config 3's dX), where the
-// half tiles double the workgroups that share the chip.
-#ifndef FP6_HALF_SMALL
-#define FP6_HALF_SMALL 0
-#endif
-// A-ring depth of the half tile with its B fragments in registers (2 or 3; measured in DESIGN.md §5)
-#ifndef FP6_BREG_STAGES
-#define FP6_BREG_STAGES 2
-#endif
-static bool fp6_half_applies(int64_t M, int64_t N, int ksplit, bool has_bias, bool res) {
-  if (g_fp6_half <= 0 || has_bias || ksplit > 1 || g_variant6 >= 0 || M % 64 != 0 || N % 512 != 0) return false;
-  const int64_t tiles = (M / 64) * (N / 512);
-  if (res || g_fp6_half == 2 || g_fp6_half == 4) return tiles >= 4 * device_cus();
-  return FP6_HALF_SMALL && tiles < 2 * device_cus();
-}
-
-// Whether a launch takes the 64 x 1024 tile with B in registers (bnn_gemm_fp6_set_wide): the 4-plane
-// launches only (no residual plane, no bias), whole K per tile, B in panels, the default plan,
-// bnn_gemm_fp6_set_half at its default 1, not persistent, M % 64 == 0, N % 1024 == 0 and (mode 1)
-// at least two rounds of tiles.  The B loads are unclamped: N % 1024 == 0 keeps every row inside
-// the N / 512 panels, and bnn_gemm_fp6_panel_ws has checked bks >= K / 64.
-static const char* const kWideName = "gemm_fp6_k<1, 8, 2, 4, 2, 0, 2, 0, 0, 0, 1>";
-static bool fp6_wide_applies(int64_t M, int64_t N, int ksplit, bool has_bias, bool res, bool panel) {
-  if (g_fp6_wide <= 0 || g_fp6_half != 1 || g_fp6_pers || g_variant6 >= 0 || res || has_bias || !panel || ksplit > 1 ||
-      !fp6_wide_shape(M, N))
-    return false;
-  return g_fp6_wide == 2 || (M / 64) * (N / 1024) >= 2 * device_cus();
-}
-
-static bool fp6_pers_applies(int64_t M, int64_t N, int ksplit, bool has_bias, bool panel) {
-  return g_fp6_pers && !has_bias && panel && ksplit <= 1 && g_variant6 < 0 && M % 128 == 0 && N % 512 == 0 &&
-         (M / 128) * (N / 512) >= 2 * device_cus();
+                         int64_t M, int64_t N, int64_t K, void* work, int64_t work_bytes, void* stream) {
+  Query6 q{M, N, K, ares != nullptr, bias != nullptr, ldb < 0, true, false};
+  Choice6 c;
+  if (gemm6_args_ok(alo, ahi, asc, asc_rows, ares, b, ldb, C, ldc, M, N, K)) {
+    c = select6(q);
+    // a workspace that is missing, misaligned or smaller than bnn_gemm_fp6_workspace: the unsplit grid
+    const int64_t need = split_bytes6(c, M, N);
+    if (c.ksplit > 1 && (need == 0 || work == nullptr || !aligned16(work) || work_bytes < need)) {
+      q.work = false;
+      c = select6(q);
+    }
+  }
+  if (!c.row) {
+    set_error("bnn_gemm_fp6: bad arguments (M=%lld N=%lld K=%lld ldb=%lld asc_rows=%lld; K a positive multiple of "
+              "64, asc_rows a multiple of 256 >= bnn_quant6_scale_rows(M))",
+              (long long)M, (long long)N, (long long)K, (long long)ldb, (long long)asc_rows);
+    return kErrInval;
+  }
+  if (M == 0 || N == 0) return 0;
+  return c.row->launch(params6(alo, ahi, asc, asc_rows, ares, b, ldb, bias, C, ldc, M, N, K, c, work), S6(stream));
 }
 
 BNN_API int bnn_gemm_fp6(const uint8_t* alo, const uint8_t* ahi, const uint8_t* asc, int64_t asc_rows,
@@ -1543,101 +1665,53 @@ BNN_API int bnn_gemm_fp6_ws(const uint8_t* alo, const uint8_t* ahi, const uint8_
   return gemm_fp6_impl(alo, ahi, asc, asc_rows, ares, b, ldb, bias, C, ldc, M, N, K, work, work_bytes, stream);
 }
 
-static int gemm_fp6_impl(const uint8_t* alo, const uint8_t* ahi, const uint8_t* asc, int64_t asc_rows,
-                         const uint8_t* ares, const uint8_t* b, int64_t ldb, const float* bias, float* C, int64_t ldc,
-                         int64_t M, int64_t N, int64_t K, void* work, int64_t work_bytes, void* stream) {
-  const bool panel = ldb < 0;   // bnn_gemm_fp6_panel_ws: ldb = -(k-steps per panel)
-  if (!alo || !ahi || !asc || !b || !C || M < 0 || N < 0 || K <= 0 || K % 64 != 0 || (!panel && (ldb < K / 2 || ldb % 16 != 0)) ||
-      ldc < N || asc_rows < bnn_quant6_scale_rows(M) || asc_rows % 256 != 0 || !aligned16(alo) || !aligned16(ahi) ||
-      !aligned16(asc) || !aligned16(b) || (ares && !aligned16(ares)) || (ares && g_variant6 >= 0 && g_variant6 != 7) ||
-      M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff) {
-    set_error("bnn_gemm_fp6: bad arguments (M=%lld N=%lld K=%lld ldb=%lld asc_rows=%lld; K a positive multiple of "
-              "64, asc_rows a multiple of 256 >= bnn_quant6_scale_rows(M))",
-              (long long)M, (long long)N, (long long)K, (long long)ldb, (long long)asc_rows);
-    return kErrInval;
-  }
-  if (M == 0 || N == 0) return 0;
-  // split-K only with a workspace of bnn_gemm_fp6_workspace bytes (else the whole K per tile); the
-  // result depends on the shape only -- never on C's alignment or pitch: a gradient written straight
-  // into a bucket view must equal the one AccumulateGrad would add
-  const Fp6Plan pl = plan6(M, N, K);
-  const int64_t need = bnn_gemm_fp6_workspace(M, N, K);
-  const bool split = need > 0 && work != nullptr && aligned16(work) && work_bytes >= need;
-  Gemm6Params p{alo, ahi, asc, b, ldb, asc_rows, bias, C, ldc, (int)M, (int)N, (int)K, 0, 0, K >= 32768 ? 8 : 4,
-                split ? pl.ksplit : 1, 0, split ? reinterpret_cast<float*>(work) : nullptr, panel ? -ldb : 0, {}};
-
-  const bool pers = fp6_pers_applies(M, N, p.ksplit, bias != nullptr, panel);
-  // the half-tile form: 64 x 512 tiles, two workgroups per CU, the second resident of each CU in the
-  // first round (blocks [CUs, 2 CUs): tools/probes/probe_wg_placement.hip) held back g_half_ticks
-  const bool half = !pers && fp6_half_applies(M, N, p.ksplit, bias != nullptr, ares != nullptr);
-  if (half) {
-    p.stg_lo = device_cus();
-    p.stg_hi = 2 * device_cus();
-    p.stg_ticks = g_half_ticks;
-    if (g_half_group > 0) p.group = g_half_group;
-  }
-  // B fragments in registers: the half tile in modes 1 / 2 with B in panels (modes 3 / 4 and a
-  // row-major B keep the LDS path)
-  const bool breg = half && panel && g_fp6_half <= 2;
-  if (ares) {   // the residual plane runs on the default tile (variant 7) with its own instance
-    p.ares = ares;
-    if (pers) return launch6_pers<1>(p, device_cus(), S6(stream));
-    if (breg) return launch6<1, 4, 2, 4, FP6_BREG_STAGES, 0, 2, 0, 0, 1, 1>(p, S6(stream));
-    if (half) return launch6<1, 4, 2, 4, 2, 0, 2, 0, 0, 1>(p, S6(stream));
-    return launch6<2, 4, 2, 4, 2, 0, 2, 0, 0, 1>(p, S6(stream));
-  }
-  if (breg) return launch6<1, 4, 2, 4, FP6_BREG_STAGES, 0, 2, 0, 0, 0, 1>(p, S6(stream));
-  if (half) return launch6<1, 4, 2, 4, 2>(p, S6(stream));
-  if (fp6_wide_applies(M, N, p.ksplit, bias != nullptr, false, panel)) {
-    if (g_wide_group > 0) p.group = g_wide_group;
-    return launch6<1, 8, 2, 4, 2, 0, 2, 0, 0, 0, 1>(p, S6(stream));
-  }
-  if (pers && pl.v->id == 7) return launch6_pers<0>(p, device_cus(), S6(stream));
-  return pl.v->fn(p, S6(stream));
-}
-
 // 0 (default): one workgroup per tile.  1: the default tile runs persistent with split load / store
 // roles on grids of two or more rounds (gemm_fp6_pers_k; measured slower on both backward shapes,
 // DESIGN.md §5 -- kept for A/B).  on < 0 queries.
 BNN_API int bnn_gemm_fp6_set_persistent(int32_t on) {
-  if (on < 0) return g_fp6_pers;
-  g_fp6_pers = on != 0;
+  if (on < 0) return g_fp6.pers;
+  g_fp6.pers = on != 0;
   return 0;
 }
 
-// The FP6 GEMM's half-tile form (g_fp6_half above): mode 0 .. 4, stagger in microseconds (the
+// The FP6 GEMM's half-tile form (Fp6Switches::half): mode 0 .. 4, stagger in microseconds (the
 // first-round wait of the second workgroup on each CU); mode < 0 queries the mode.
 BNN_API int bnn_gemm_fp6_set_half(int32_t mode, double stagger_us) {
-  if (mode < 0) return g_fp6_half;
+  if (mode < 0) return g_fp6.half;
   if (mode > 4) {
     set_error("bnn_gemm_fp6_set_half: mode %d (0 .. 4)", (int)mode);
     return kErrInval;
   }
-  g_fp6_half = mode;
-  g_half_ticks = (int64_t)(stagger_us * 100.0);
+  g_fp6.half = mode;
+  g_fp6.half_ticks = (int64_t)(stagger_us * 100.0);
   return 0;
 }
 
-// The B-in-registers form of the 4-plane launches (g_fp6_wide above): mode 0 .. 2; mode < 0 queries.
+// The B-in-registers form of the 4-plane launches (Fp6Switches::wide): mode 0 .. 2; mode < 0 queries.
 BNN_API int bnn_gemm_fp6_set_wide(int32_t mode) {
-  if (mode < 0) return g_fp6_wide;
+  if (mode < 0) return g_fp6.wide;
   if (mode > 2) {
     set_error("bnn_gemm_fp6_set_wide: mode %d (0 .. 2)", (int)mode);
     return kErrInval;
   }
-  g_fp6_wide = mode;
+  g_fp6.wide = mode;
   return 0;
 }
 
 // Tuning hook: raster group (tile rows per group, tile6_of) of that form; 0 = default.
 BNN_API int bnn_gemm_fp6_set_wide_group(int32_t g) {
-  g_wide_group = g < 0 ? 0 : g;
+  g_fp6.wide_group = g < 0 ? 0 : g;
   return 0;
 }
 
 // Tuning hook: raster group (tile rows per group, tile6_of) of the half-tile form; 0 = default.
 BNN_API int bnn_gemm_fp6_set_half_group(int32_t g) {
-  g_half_group = g < 0 ? 0 : g;
+  g_fp6.half_group = g < 0 ? 0 : g;
+  return 0;
+}
+
+BNN_API int bnn_gemm_fp6_set_variant(int32_t v) {
+  g_fp6.variant = v;
   return 0;
 }
 
@@ -1662,9 +1736,8 @@ BNN_API int bnn_gemm_fp6_panel_ws(const uint8_t* alo, const uint8_t* ahi, const 
                                   const uint8_t* ares, const uint8_t* bpanels, int64_t bks, const float* bias, float* C,
                                   int64_t ldc, int64_t M, int64_t N, int64_t K, void* work, int64_t work_bytes,
                                   void* stream) {
-  if ((g_variant6 >= 0 && 512 % find6(g_variant6)->bn != 0) || K <= 0 || bks < K / 64) {
-    set_error("bnn_gemm_fp6_panel_ws: bad arguments (K=%lld bks=%lld; bks >= K/64, a tile width dividing 512)",
-              (long long)K, (long long)bks);
+  if (K <= 0 || bks < K / 64) {
+    set_error("bnn_gemm_fp6_panel_ws: bad arguments (K=%lld bks=%lld; bks >= K/64)", (long long)K, (long long)bks);
     return kErrInval;
   }
   return gemm_fp6_impl(alo, ahi, asc, asc_rows, ares, bpanels, -bks, bias, C, ldc, M, N, K, work, work_bytes, stream);
@@ -1681,56 +1754,53 @@ BNN_API int bnn_gemm_fp6_bnstats(const uint8_t* alo, const uint8_t* ahi, const u
                                  int64_t K, const void* x, const float* xbias, int32_t x_i16, const float* mean,
                                  const float* mean_lo, const float* invstd, const float* gamma, const float* beta,
                                  int32_t hardtanh, int32_t mode, float* part, void* stream) {
-  const Fp6Plan pl = plan6(M, N, K);
-  if (!x || !mean || !invstd || !part || (mode != 1 && mode != 2) || N % 4 != 0 || pl.ksplit != 1 ||
-      pl.v->bm != 128 || pl.v->id != 7 || K <= 0 || bks < K / 64 || !aligned16(x) || !aligned16(mean) ||
-      !aligned16(invstd) || (mean_lo && !aligned16(mean_lo)) || (gamma && !aligned16(gamma)) ||
-      (beta && !aligned16(beta)) || (xbias && !aligned16(xbias)) || !aligned16(part)) {
+  const Choice6 c = select6(Query6{M, N, K, ares != nullptr, false, true, true, true});
+  if (!x || !mean || !invstd || !part || (mode != 1 && mode != 2) || N % 4 != 0 || !c.row || K <= 0 ||
+      bks < K / 64 || !aligned16(x) || !aligned16(mean) || !aligned16(invstd) || (mean_lo && !aligned16(mean_lo)) ||
+      (gamma && !aligned16(gamma)) || (beta && !aligned16(beta)) || (xbias && !aligned16(xbias)) || !aligned16(part)) {
     set_error("bnn_gemm_fp6_bnstats: bad arguments (M=%lld N=%lld K=%lld mode=%d; N %% 4 == 0, an unsplit 128x512 "
               "default plan, 16-B aligned vectors)", (long long)M, (long long)N, (long long)K, mode);
     return kErrInval;
   }
-  if (!alo || !ahi || !asc || !bpanels || !C || M <= 0 || N <= 0 || K % 64 != 0 || ldc < N ||
-      asc_rows < bnn_quant6_scale_rows(M) || asc_rows % 256 != 0 || !aligned16(alo) || !aligned16(ahi) ||
-      !aligned16(asc) || !aligned16(bpanels) || (ares && !aligned16(ares)) || M > 0x7fffffff || N > 0x7fffffff ||
-      K > 0x7fffffff) {
+  if (M <= 0 || N <= 0 || !gemm6_args_ok(alo, ahi, asc, asc_rows, ares, bpanels, -bks, C, ldc, M, N, K)) {
     set_error("bnn_gemm_fp6_bnstats: bad GEMM arguments");
     return kErrInval;
   }
-  Gemm6Params p{alo, ahi, asc, bpanels, -bks, asc_rows, nullptr, C, ldc, (int)M, (int)N, (int)K, 0, 0,
-                K >= 32768 ? 8 : 4, 1, 0, nullptr, bks};
+  Gemm6Params p = params6(alo, ahi, asc, asc_rows, ares, bpanels, -bks, nullptr, C, ldc, M, N, K, c, nullptr);
   p.bn = Gemm6Params::Bn{x, xbias, mean, mean_lo, invstd, gamma, beta, part, x_i16 ? 1 : 0, hardtanh ? 1 : 0, mode};
-  if (ares) {
-    p.ares = ares;
-    return launch6<2, 4, 2, 4, 2, 0, 2, 0, 1, 1>(p, S6(stream));
-  }
-  return launch6<2, 4, 2, 4, 2, 0, 2, 0, 1>(p, S6(stream));
+  return c.row->launch(p, S6(stream));
 }
 
-BNN_API const char* bnn_gemm_fp6_kernel(int64_t M, int64_t N) { return pick6(M, N)->name; }
+// The label queries (the timer keys of bench.py and the committed profiles): the tile of the plan.
+BNN_API const char* bnn_gemm_fp6_kernel(int64_t M, int64_t N) {
+  return label6(*select6(Query6{M, N, 64, false, false, true, true, false}).plan);
+}
 
+// What the backward GEMMs (no bias, B in panels, a workspace) launch on this shape, the half and wide
+// forms ignored: the persistent form where select6 takes it, else the plan's tile.
 BNN_API const char* bnn_gemm_fp6_kernel_k(int64_t M, int64_t N, int64_t K) {
-  const Fp6Plan pl = plan6(M, N, K);
-  static thread_local char buf[96];
-  // the name of what the backward GEMMs (no bias, B in panels) launch on this shape: the persistent
-  // form where gemm_fp6_impl's predicate takes it; a residual-plane launch runs the default tile's
-  // RES instance, which is variant 7 = the plan's choice on every unsplit shape of the wide step
-  if (fp6_pers_applies(M, N, pl.ksplit, false, true)) return "gemm_fp6_pers_k<2, 4, 2, 4, 2>";
-  if (pl.ksplit <= 1) return pl.v->name;
-  snprintf(buf, sizeof buf, "%s split-K %d", pl.v->name, pl.ksplit);
-  return buf;
+  const Choice6 c = select6(Query6{M, N, K, false, false, true, true, false});
+  const bool pers = c.row && c.row->id >= kRowPers;
+  return name6(label6(pers ? *c.row : *c.plan), c.ksplit);
 }
 
-// As bnn_gemm_fp6_kernel_k for a launch with (res != 0) or without the residual plane.
+// The label of a launch with (res != 0) or without the residual plane; a residual-plane launch on the
+// default tile runs its RES instance, whose label is variant 7's.
 BNN_API const char* bnn_gemm_fp6_kernel_kr(int64_t M, int64_t N, int64_t K, int32_t res) {
-  const Fp6Plan pl = plan6(M, N, K);
-  if (!fp6_pers_applies(M, N, pl.ksplit, false, true) && fp6_half_applies(M, N, pl.ksplit, false, res != 0))
-    return "gemm_fp6_k<1, 4, 2, 4, 2>";
-  if (fp6_wide_applies(M, N, pl.ksplit, false, res != 0, true)) return kWideName;
-  return bnn_gemm_fp6_kernel_k(M, N, K);
+  const Choice6 c = select6(Query6{M, N, K, res != 0, false, true, true, false});
+  return name6(label6(c.row ? *c.row : *c.plan), c.ksplit);
 }
 
-BNN_API int bnn_gemm_fp6_set_variant(int32_t v) {
-  g_variant6 = v;
-  return 0;
+// Host-only query: the exact instance bnn_gemm_fp6_ws (panel == 0) / bnn_gemm_fp6_panel_ws launches
+// with no bias and a workspace; "" for a launch that is refused.
+BNN_API const char* bnn_gemm_fp6_instance(int64_t M, int64_t N, int64_t K, int32_t res, int32_t panel) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % 64 != 0) return "";
+  const Choice6 c = select6(Query6{M, N, K, res != 0, false, panel != 0, true, false});
+  return c.row ? name6(c.row->name, split_bytes6(c, M, N) > 0 ? c.ksplit : 1) : "";
 }
+
+// The index-th row of the instance table; "" past the end.
+BNN_API const char* bnn_gemm_fp6_instance_at(int32_t index) {
+  return index >= 0 && index < (int)(sizeof(kInst6) / sizeof(kInst6[0])) ? kInst6[index].name : "";
+}
+

@@ -323,6 +323,19 @@ int bnn_gemm_fp6_bnstats(const uint8_t* alo, const uint8_t* ahi, const uint8_t* 
 const char* bnn_gemm_fp6_kernel(int64_t M, int64_t N);
 const char* bnn_gemm_fp6_kernel_k(int64_t M, int64_t N, int64_t K);   /* + " split-K S" */
 const char* bnn_gemm_fp6_kernel_kr(int64_t M, int64_t N, int64_t K, int32_t res);   /* with / without the residual plane */
+/* Host-only dispatch query (needs no GPU, launches nothing): the exact kernel template instance that
+ * bnn_gemm_fp6_ws (panel == 0) or bnn_gemm_fp6_panel_ws (panel != 0) runs for a shape with (res != 0)
+ * or without the residual plane, no bias and a workspace, under the current bnn_gemm_fp6_set_variant /
+ * _persistent / _half / _wide settings, e.g. "gemm_fp6_k<1, 4, 2, 4, 2, 0, 2, 0, 0, 1, 1>" (the half
+ * tile with the residual plane and its B fragments in registers), plus " split-K S" where the launch
+ * splits.  The three label queries above name the tile such an instance runs on (the timer keys);
+ * this one tells the instances of a tile apart.  "" for a shape or a combination the entries refuse.
+ * The entries and the queries share one decision function.  The string is valid until the calling
+ * thread's next query.
+ * bnn_gemm_fp6_instance_at: the index-th instance the FP6 GEMM entries can launch (the table the
+ * launchers are generated from, bnn_gemm_fp6_bnstats' two included); "" past the end. */
+const char* bnn_gemm_fp6_instance(int64_t M, int64_t N, int64_t K, int32_t res, int32_t panel);
+const char* bnn_gemm_fp6_instance_at(int32_t index);
 int bnn_gemm_fp6_set_variant(int32_t variant);   /* tuning hook (-1 = default) */
 /* 1: on grids of >= 2 rounds of 128 x 512 tiles with no bias, M % 128 == 0, N % 512 == 0 and B in
  * panels (the backward GEMMs), the default tile runs persistent -- one workgroup per CU, the waves

@@ -273,9 +273,11 @@ def test_fp6_persistent_gemm_bit_identical(F, M, N, K, res):
     try:
         L.call("bnn_gemm_fp6_set_persistent", 1)
         assert "pers" in L.lib().bnn_gemm_fp6_kernel_k(M, N, op.Kp).decode()
+        assert L.lib().bnn_gemm_fp6_instance(M, N, op.Kp, int(res), 1).decode() == f"gemm_fp6_pers_k<{int(res)}>"
         C1 = F.gemm_fp6(op, None, N, panels=P, panel_ks=ks)
         L.call("bnn_gemm_fp6_set_persistent", 0)
         assert "pers" not in L.lib().bnn_gemm_fp6_kernel_k(M, N, op.Kp).decode()
+        assert "pers" not in L.lib().bnn_gemm_fp6_instance(M, N, op.Kp, int(res), 1).decode()
         C0 = F.gemm_fp6(op, None, N, panels=P, panel_ks=ks)
         torch.cuda.synchronize()
     finally:
@@ -313,6 +315,13 @@ def test_fp6_half_tile_gemm_bit_identical(F, M, N, K, res):
             L.call("bnn_gemm_fp6_set_half", mode, st)
             name = L.lib().bnn_gemm_fp6_kernel_kr(M, N, op.Kp, int(res)).decode()
             assert ("<1, 4, 2, 4, 2>" in name) == (mode > 0), (mode, name)
+            # the exact instance: the 128 x 512 tile, or the half tile with its B fragments in
+            # registers (mode 2 on a panel operand), each with or without RES
+            inst = L.lib().bnn_gemm_fp6_instance(M, N, op.Kp, int(res), 1).decode()
+            want = {(0, False): "gemm_fp6_k<2, 4, 2, 4, 2>", (0, True): "gemm_fp6_k<2, 4, 2, 4, 2, 0, 2, 0, 0, 1>",
+                    (2, False): "gemm_fp6_k<1, 4, 2, 4, 2, 0, 2, 0, 0, 0, 1>",
+                    (2, True): "gemm_fp6_k<1, 4, 2, 4, 2, 0, 2, 0, 0, 1, 1>"}[mode, bool(res)]
+            assert inst == want, (mode, inst)
             outs[(mode, st)] = F.gemm_fp6(op, None, N, panels=P, panel_ks=ks)
         torch.cuda.synchronize()
     finally:

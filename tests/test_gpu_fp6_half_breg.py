@@ -20,6 +20,16 @@ pytestmark = pytest.mark.gpu
 N = 4096
 K_MAX = 320
 PANEL_EXTRA = 128          # columns of the wider panel buffer beyond K_MAX
+# (bnn_gemm_fp6_set_half mode, residual plane) -> the exact instance bnn_gemm_fp6_instance must report:
+# the labels cannot tell the three half-tile forms apart
+INSTANCE = {
+    (0, False): "gemm_fp6_k<2, 4, 2, 4, 2>",                              # the 128 x 512 tile
+    (0, True): "gemm_fp6_k<2, 4, 2, 4, 2, 0, 2, 0, 0, 1>",
+    (4, False): "gemm_fp6_k<1, 4, 2, 4, 2>",                              # the half tile, B through LDS
+    (4, True): "gemm_fp6_k<1, 4, 2, 4, 2, 0, 2, 0, 0, 1>",
+    (2, False): "gemm_fp6_k<1, 4, 2, 4, 2, 0, 2, 0, 0, 0, 1>",            # the half tile, B in registers
+    (2, True): "gemm_fp6_k<1, 4, 2, 4, 2, 0, 2, 0, 0, 1, 1>",
+}
 
 
 @pytest.fixture(scope="module")
@@ -63,6 +73,8 @@ def _three_modes(F, op, P, ks, M, res, stagger=0.0):
             L.call("bnn_gemm_fp6_set_half", mode, stagger if mode else 0.0)
             name = L.lib().bnn_gemm_fp6_kernel_kr(M, N, op.Kp, int(res)).decode()
             assert ("<1, 4, 2, 4, 2>" in name) == (mode > 0), (mode, name)
+            inst = L.lib().bnn_gemm_fp6_instance(M, N, op.Kp, int(res), 1).decode()
+            assert inst == INSTANCE[mode, bool(res)], (mode, inst)
             outs[mode] = F.gemm_fp6(op, None, N, panels=P, panel_ks=ks)
         torch.cuda.synchronize()
     finally:

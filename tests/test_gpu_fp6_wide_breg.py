@@ -71,11 +71,14 @@ def _ref_and_wide(F, op, P, ks, M, N, expect):
         L.call("bnn_gemm_fp6_set_half", 0, 0.0)
         L.call("bnn_gemm_fp6_set_wide", 0)
         assert L.lib().bnn_gemm_fp6_kernel_kr(M, N, op.Kp, 0).decode() == DEFAULT
+        assert L.lib().bnn_gemm_fp6_instance(M, N, op.Kp, 0, 1).decode() == DEFAULT
         ref = F.gemm_fp6(op, None, N, panels=P, panel_ks=ks)
         L.call("bnn_gemm_fp6_set_half", 1, 0.0)
         L.call("bnn_gemm_fp6_set_wide", 2)
         name = L.lib().bnn_gemm_fp6_kernel_kr(M, N, op.Kp, 0).decode()
         assert name == expect, name
+        inst = L.lib().bnn_gemm_fp6_instance(M, N, op.Kp, 0, 1).decode()     # the exact instance: both are their own label
+        assert inst == expect, inst
         C = F.gemm_fp6(op, None, N, panels=P, panel_ks=ks)
         torch.cuda.synchronize()
     finally:

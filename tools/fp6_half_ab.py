@@ -48,6 +48,8 @@ def main():
         for c in cfgs:
             run(c)
             torch.cuda.synchronize()
+            print(f"{tag:7s} mode {c[0]}: {L.lib().bnn_gemm_fp6_kernel_kr(M, N, K, int(res)).decode()} "
+                  f"[{L.lib().bnn_gemm_fp6_instance(M, N, K, int(res), 1).decode()}]", flush=True)
             if ref is None:
                 ref = C.clone()
             else:

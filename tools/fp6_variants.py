@@ -33,7 +33,8 @@ def main():
         names = {}
         for v in variants:
             L.call("bnn_gemm_fp6_set_variant", v)
-            names[v] = L.lib().bnn_gemm_fp6_kernel(M, N).decode()
+            names[v] = (f"{L.lib().bnn_gemm_fp6_kernel(M, N).decode()} "
+                        f"[{L.lib().bnn_gemm_fp6_instance(M, N, op.Kp, int(op.res is not None), 0).decode()}]")
             BF.gemm_fp6(op, w4, N, out=C)
             torch.cuda.synchronize()
             if ref is None:

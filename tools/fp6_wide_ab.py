@@ -52,7 +52,8 @@ def main():
             run(c)
             torch.cuda.synchronize()
             assert torch.equal(C, ref), (c, float((C - ref).abs().max()))
-            print(f"{c:5s} {L.lib().bnn_gemm_fp6_kernel_kr(M, N, K, 0).decode()}: equal to the default", flush=True)
+            print(f"{c:5s} {L.lib().bnn_gemm_fp6_kernel_kr(M, N, K, 0).decode()} "
+                  f"[{L.lib().bnn_gemm_fp6_instance(M, N, K, 0, 1).decode()}]: equal to the default", flush=True)
         times = {c: [] for c in cfgs}
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(rounds):
