@@ -11,6 +11,7 @@ Semantics restated from the reference operator module (models/binarized_modules.
 
 Every op here runs on ROCm tensors through libbnn.so; there is no CPU fallback.
 """
+import collections
 import contextlib
 import ctypes
 import itertools
@@ -111,7 +112,7 @@ def _check(*ts, dtype=torch.float32):
 
 def _c2d(x):
     """Contiguous fp32 2-D view."""
-    if getattr(x, "_bnn_z16", None) is not None or getattr(x, "_bnn_s20", None) is not None:
+    if getattr(x, _PREACT_ATTR, None) is not None:
         raise RuntimeError("a compact pre-activation placeholder reached an op that reads fp32 values")
     return x if x.is_contiguous() else x.contiguous()
 
@@ -545,10 +546,9 @@ def gemm_fp4_i16(A4, B4, M, N, k_true=None):
 # consumer is a libbnn BatchNorm pass it travels as int16 dot products + the bias
 # (bnn_gemm_fp4_i16; the *_i16 BatchNorm entries form fl(I + bias), bit-identical to the fp32 z)
 # at half the bytes of every pass over it.  Autograd sees a stride-0 float placeholder of z's
-# shape carrying (int16, bias) in _Z16_ATTR; only the z16-aware functions below read it, and its
-# gradient is an ordinary fp32 tensor.
+# shape carrying a PreAct descriptor of (int16, bias); only the z16-aware functions below read it,
+# and its gradient is an ordinary fp32 tensor.
 Z16 = True
-_Z16_ATTR = "_bnn_z16"
 
 
 Z16_MIN_TILES = 512      # below this many 256x256 output tiles the fp32 epilogue is as cheap
@@ -598,17 +598,124 @@ def _is_placeholder(t):
     return getattr(t, "_bnn_token", None) is not None or t.data_ptr() in _ZERO_PTRS
 
 
-def _z16_carrier(y16, bias):
-    global Z16_HANDOFFS
-    Z16_HANDOFFS += 1
-    ph = _placeholder(y16.shape, y16.device)
-    setattr(ph, _Z16_ATTR, (y16, bias))
+class PreAct:
+    """A layer's pre-activation in the form it travels in: ``kind`` and ``args``, the leading arguments of
+    the library entries that read it -- its tensors (a bias: fp32 [C] or None), then its scalars:
+        f32   (x,)                     fp32 [M, C] or NCHW
+        z16   (x16, bias)              int16 sums [M, C]: fl(x16 + bias)
+        s20   (lo, hi, bias, scale)    20-bit sums S as int16 low bits [M, C] and uint8 nibbles [M, C / 2]:
+                                       fl(fl(S * scale) + bias)
+        zq    (xq, bias, fmt)          int8 (fmt 1) / int16 (fmt 2) NCHW sums: fl(xq + bias[c])
+    The three compact kinds reach their consumer on a stride-0 placeholder (_preact_carrier)."""
+    __slots__ = ("kind", "args", "compact")
+    _TENSORS = {"f32": 1, "z16": 2, "s20": 3, "zq": 2}          # how many of args are tensors
+    _SUFFIX = {"f32": "", "z16": "_i16", "s20": "_s20", "zq": "_q"}
+    _NBYTES = {"f32": 4, "z16": 2, "s20": 2.5}
+
+    def __init__(self, kind, *args):
+        self.kind, self.args, self.compact = kind, args, kind != "f32"
+
+    x = property(lambda self: self.args[0])                     # the plane of the value's shape
+    shape = property(lambda self: self.args[0].shape)
+    device = property(lambda self: self.args[0].device)
+    suffix = property(lambda self: self._SUFFIX[self.kind])     # of the entries that read this kind
+    # bytes per element one pass over the value reads (the timers' byte counts)
+    nbytes = property(lambda self: self._NBYTES[self.kind] if self.kind != "zq" else self.args[0].element_size())
+
+    def saved(self):
+        """The tensors, as three slots of a save_for_backward; ``meta()`` is the rest, for the ctx."""
+        n = self._TENSORS[self.kind]
+        return self.args[:n] + (None,) * (3 - n)
+
+    def meta(self):
+        return (self.kind,) + self.args[self._TENSORS[self.kind]:]
+
+    @classmethod
+    def restored(cls, meta, saved):
+        return cls(meta[0], *saved[:cls._TENSORS[meta[0]]], *meta[1:])
+
+    def dense(self):
+        """The fp32 tensor this stands for, formed with the same fp32 roundings as the kernels that read
+        it (test and debugging aid -- the training path never materialises it)."""
+        if self.kind == "f32":
+            return self.args[0]
+        if self.kind == "s20":
+            lo, hi, bias, scale = self.args
+            nib = torch.stack(((hi & 15), (hi >> 4) & 15), dim=-1).reshape(lo.shape).to(torch.int32)
+            S = ((lo.to(torch.int32) & 0xFFFF) | (nib << 16))
+            S = torch.where(S >= (1 << 19), S - (1 << 20), S)
+            y = S.to(torch.float32) * torch.tensor(scale, dtype=torch.float32, device=lo.device)
+        else:
+            y, bias = self.args[0].to(torch.float32), self.args[1]
+            if self.kind == "zq" and bias is not None:
+                bias = bias.view(1, -1, 1, 1)
+        return y + bias if bias is not None else y
+
+
+# (pass, kind, modifier) -> the library entry that runs the pass on a pre-activation of that kind.  A
+# pass is named by its fp32 entry; the modifier "_stoch" precedes the format suffix, "_pre" follows it.
+_ENTRIES = {(base, k, m): base + (m + PreAct._SUFFIX[k] if m == "_stoch" else PreAct._SUFFIX[k] + m)
+            for base, kinds, mods in (("bnn_bn_fwd_train", ("f32", "z16"), ("",)),
+                                      ("bnn_bn_apply_pack", ("f32", "z16", "s20"), ("", "_stoch")),
+                                      ("bnn_bn_bwd_q6", ("f32", "z16"), ("", "_pre")),
+                                      ("bnn_bn_bwd_i8cols", ("f32", "s20"), ("", "_pre")),
+                                      ("bnn_bn_head_fwd", ("f32", "z16"), ("",)),
+                                      ("bnn_bn_head_bwd_q6", ("f32", "z16"), ("",)),
+                                      ("bnn_bn2d_fwd_train", ("f32", "zq"), ("",)),
+                                      ("bnn_bn2d_bwd", ("f32", "zq"), ("",)),
+                                      ("bnn_bn2d_bwd_stats", ("zq",), ("",)))
+            for k in kinds for m in mods}
+# the statistics pass of drop(z): an entry of its own on fp32, the (p, seed) of the one z16 entry
+_ENTRIES["bnn_bn_fwd_train", "f32", "_dropout"] = "bnn_bn_dropout_fwd_train"
+_ENTRIES["bnn_bn_fwd_train", "z16", "_dropout"] = "bnn_bn_fwd_train_i16"
+_PREACT_ATTR = "_bnn_preact"
+
+
+def _entry(base, z, mod=""):
+    return _ENTRIES[base, z.kind, mod]
+
+
+def _preact_carrier(z):
+    """A placeholder of z's shape that carries the compact z to its consumer."""
+    global Z16_HANDOFFS, S20_HANDOFFS, ZQ_HANDOFFS
+    if z.kind == "z16":
+        Z16_HANDOFFS += 1
+    elif z.kind == "s20":
+        S20_HANDOFFS += 1
+    else:
+        ZQ_HANDOFFS += 1
+    ph = _placeholder(z.shape, z.device)
+    setattr(ph, _PREACT_ATTR, z)
     return ph
 
 
-def _z16_of(x):
-    """(int16 [M, C], bias [C] or None) carried by a z16 placeholder, or None."""
-    return getattr(x, _Z16_ATTR, None)
+def _preact_of(x, accept=()):
+    """The descriptor of any tensor: the one a placeholder carries, if of a kind the caller's entries
+    read, else f32 over _c2d(x) (which refuses every other placeholder)."""
+    z = getattr(x, _PREACT_ATTR, None)
+    return z if z is not None and z.kind in accept else PreAct("f32", _c2d(x))
+
+
+def _attach(t, attr, *payload):
+    """Gradient hand-off: a backward pass attaches what the next one needs to the gradient it returns
+    (often a placeholder: the dense gradient is then never written), keyed on that tensor."""
+    setattr(t, attr, (_q6_key(t),) + payload)
+
+
+def _take(dy, attr, stale=None, lost=None):
+    """The payload attached to ``dy`` under ``attr``, taken once, or None.  A payload keyed for another
+    tensor raises ``stale`` (None: it is dropped).  ``lost`` is the required mode: a stride-0 placeholder
+    that arrives without a payload has no values to fall back on and raises it."""
+    ent = getattr(dy, attr, None)
+    if ent is not None:
+        delattr(dy, attr)
+        if ent[0] == _q6_key(dy):
+            return ent[1:]
+        if stale is not None:
+            raise RuntimeError(stale)
+    if lost is not None and dy.dim() > 0 and not any(dy.stride()) and _is_placeholder(dy):
+        raise RuntimeError(lost)
+    return None
 
 
 def _grad_sink(w):
@@ -1038,41 +1145,19 @@ def _pixels_fwd_with_stats(q, wq, M, N, K, bscale, bias, R, s0):
 # entries form the same fp32 z1 bit for bit.  The statistics still come from the GEMM epilogue.
 # Autograd sees a stride-0 placeholder (as for z16); dense_preact() rebuilds the fp32 tensor.
 S20 = os.environ.get("BNN_S20", "1") != "0"    # BNN_S20=0: fc1 writes the fp32 z1
-_S20_ATTR = "_bnn_s20"
 S20_HANDOFFS = 0          # s20 placeholders produced (tests check the hand-off ran)
 
 
-def _s20_carrier(lo, hi, bias, scale):
-    global S20_HANDOFFS
-    S20_HANDOFFS += 1
-    ph = _placeholder(lo.shape, lo.device)
-    setattr(ph, _S20_ATTR, (lo, hi, bias, float(scale)))
-    return ph
-
-
 def _s20_of(x):
-    """(int16 low bits [M, C], uint8 nibbles [M, C/2], bias [C] or None, scale) of an s20
-    placeholder, or None."""
-    return getattr(x, _S20_ATTR, None)
+    """(int16 low bits [M, C], uint8 nibbles [M, C/2], bias [C] or None, scale) of an s20 placeholder, or None."""
+    z = getattr(x, _PREACT_ATTR, None)
+    return z.args if z is not None and z.kind == "s20" else None
 
 
 def dense_preact(z):
-    """The fp32 tensor a compact pre-activation placeholder (s20 or z16) stands for, formed with
-    the same fp32 roundings as the kernels that read it; any other tensor is returned as is (test
-    and debugging aid -- the training path never materialises it)."""
-    zs = _s20_of(z)
-    if zs is not None:
-        lo, hi, bias, scale = zs
-        nib = torch.stack(((hi & 15), (hi >> 4) & 15), dim=-1).reshape(lo.shape).to(torch.int32)
-        S = ((lo.to(torch.int32) & 0xFFFF) | (nib << 16))
-        S = torch.where(S >= (1 << 19), S - (1 << 20), S)
-        y = S.to(torch.float32) * torch.tensor(scale, dtype=torch.float32, device=lo.device)
-        return y + bias if bias is not None else y
-    zz = _z16_of(z)
-    if zz is not None:
-        y = zz[0].to(torch.float32)
-        return y + zz[1] if zz[1] is not None else y
-    return z
+    """The fp32 tensor a compact placeholder stands for (PreAct.dense); any other tensor is returned as is."""
+    d = getattr(z, _PREACT_ATTR, None)
+    return z if d is None else d.dense()
 
 
 def _pixels_fwd_s20(q, wq, M, N, K, a, bias, R, s0):
@@ -1086,12 +1171,11 @@ def _pixels_fwd_s20(q, wq, M, N, K, a, bias, R, s0):
     assert wq.shape[1] == Kp and Kp % ALIGN == 0
     # the bias itself (a detached view sharing the Parameter's version counter): the consumer saves it
     # for backward, so torch refuses a backward after an in-place update of it -- no snapshot copy
-    bs = bias
     name = f"{gemm_kernel_name(1, 1, M, N, Kp)} [pixels s20]" if _TIMER is not None else ""
     with _timed(name, 2.0 * M * N * K, M * Kp + N * Kp + 2.5 * M * N):
         L.call("bnn_gemm_i8_affine_bnstats_s20", q, Kp, wq, Kp, R, float(s0), K, lo, hi, N, M, N, Kp, part, rows,
                _const_vec(a, N, dev), bias, L.stream())
-    y = _s20_carrier(lo, hi, bs, a)
+    y = _preact_carrier(PreAct("s20", lo, hi, bias, float(a)))
     setattr(y, _FSTATS_ATTR, (part, rows, chunk, M, N, "pixels", 0.0, 0))
     return y
 
@@ -1396,14 +1480,15 @@ _C1BN_ATTR = "_bnn_c1bn"
 C1BN_HANDOFFS = 0
 
 
+# What the BatchNorm2d backward hands conv1: the conv's own compact output (zq, zb, zf: the args of its
+# PreAct), the pooled gradient dyp, the BatchNorm's vectors, its backward sums, 1 / (N H W), the Hardtanh flag
+_C1bnHandoff = collections.namedtuple("_C1bnHandoff", "zq zb zf dyp mean invstd gw gb sg sgx inv_n ht")
+
+
 def _c1bn_take(dy):
-    ent = getattr(dy, _C1BN_ATTR, None)
-    if ent is None:
-        return None
-    delattr(dy, _C1BN_ATTR)
-    if ent[0] != _q6_key(dy):
-        raise RuntimeError("stale conv1 / BatchNorm2d hand-off")
-    return ent[1:]
+    ent = _take(dy, _C1BN_ATTR, stale="stale conv1 / BatchNorm2d hand-off",
+                lost="a conv gradient placeholder lost its BatchNorm2d hand-off")
+    return None if ent is None else _C1bnHandoff(*ent)
 
 
 # BNN_CONV_C1F=1 / 0: the one-input-channel VALU filter-gradient kernel on / off (A/B timing);
@@ -1438,13 +1523,7 @@ def _conv_env():
 # (bnn_conv2d_fwd_q; bnn_bn2d_*_q read fl(I + bias), bit-identical to the fp32 output) -- a stride-0
 # placeholder of the output shape carries them, as the MLP's z16 does.
 ZQ = True
-_ZQ_ATTR = "_bnn_zq"
 ZQ_HANDOFFS = 0
-
-
-def _zq_of(x):
-    """(int8 / int16 sums [N, C, H, W], bias [C] or None, fmt 1 / 2) carried by a zq placeholder."""
-    return getattr(x, _ZQ_ATTR, None)
 
 
 def _zq_fmt(x, binarize_input, stride, dilation, groups, C, KH, KW, H, W, pad, N, Co):
@@ -1477,7 +1556,6 @@ class BinaryConv2dFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, binarize_input, stride, padding, dilation, groups, emit_compact=False,
                 stochastic=None):
-        global ZQ_HANDOFFS
         _check(x, weight, bias)
         OH, OW = conv_out_hw(x.shape[2], x.shape[3], weight.shape[2], weight.shape[3], stride, padding, dilation)
         _conv_env()
@@ -1491,6 +1569,9 @@ class BinaryConv2dFunction(torch.autograd.Function):
         Co, _, KH, KW = w.shape
         b = bias.detach() if bias is not None else None
         ctx.empty = N == 0
+        ctx.save_for_backward(x, w)
+        ctx.conf = (binarize_input, stride, padding, dilation, groups)
+        ctx.has_bias = bias is not None
         zf = _zq_fmt(x, binarize_input, stride, dilation, groups, C, KH, KW, H, W, padding, N, Co) if emit_compact else 0
         if zf and N > 0 and Co <= 64 and (OH * OW) % 4 == 0 and OH % 2 == 0 and OW % 2 == 0:
             yq = torch.empty((N, Co, OH, OW), dtype=torch.int8 if zf == 1 else torch.int16, device=x.device)
@@ -1498,14 +1579,9 @@ class BinaryConv2dFunction(torch.autograd.Function):
             with _timed("conv2d_fwd", 2 * macs, 4 * x.numel() + yq.numel() * yq.element_size() + 4 * w.numel()):
                 L.call("bnn_conv2d_fwd_q", x, w, yq, zf, N, C, H, W, Co, KH, KW, stride, padding, dilation, groups,
                        L.stream())
-            ctx.save_for_backward(x, w)
-            ctx.conf = (binarize_input, stride, padding, dilation, groups)
-            ctx.has_bias = bias is not None
-            ZQ_HANDOFFS += 1
-            ph = _placeholder((N, Co, OH, OW), x.device)
             # the bias as a detached view (its consumer saves it for backward: an in-place update
             # before this step's backward is refused by torch's saved-tensor check, no copy needed)
-            setattr(ph, _ZQ_ATTR, (yq, b, zf))
+            ph = _preact_carrier(PreAct("zq", yq, b, zf))
             if (C1BN and C == 1 and binarize_input and not ctx.needs_input_grad[0]
                     and L.lib().bnn_conv2d_bwd_filter_bn_ok(N, C, H, W, Co, KH, KW, stride, padding, dilation,
                                                             groups)):
@@ -1513,17 +1589,11 @@ class BinaryConv2dFunction(torch.autograd.Function):
             return ph
         y = torch.empty((N, Co, OH, OW), dtype=torch.float32, device=x.device)
         if ctx.empty:             # empty batch: F.conv2d returns [0, Co, OH, OW]
-            ctx.save_for_backward(x, w)
-            ctx.conf = (binarize_input, stride, padding, dilation, groups)
-            ctx.has_bias = bias is not None
             return y
         macs = N * Co * OH * OW * (C // groups) * KH * KW
         with _timed("conv2d_fwd", 2 * macs, 4 * (x.numel() + y.numel() + w.numel())):
             L.call("bnn_conv2d_fwd", x, int(binarize_input), w, b, y, N, C, H, W, Co, KH, KW, stride, padding, dilation,
                    groups, L.stream())
-        ctx.save_for_backward(x, w)
-        ctx.conf = (binarize_input, stride, padding, dilation, groups)
-        ctx.has_bias = bias is not None
         return y
 
     @staticmethod
@@ -1532,8 +1602,6 @@ class BinaryConv2dFunction(torch.autograd.Function):
         binarize_input, stride, padding, dilation, groups = ctx.conf
         bn = _c1bn_take(dy)      # the BatchNorm2d backward's pooled gradient and statistics, if handed over
         if bn is None:
-            if dy.dim() == 4 and dy.numel() > 1 and dy.stride() == (0, 0, 0, 0) and _is_placeholder(dy):
-                raise RuntimeError("a conv gradient placeholder lost its BatchNorm2d hand-off")
             dy = _c2d(dy)
         N, C, H, W = x.shape
         Co, _, KH, KW = w.shape
@@ -1557,11 +1625,11 @@ class BinaryConv2dFunction(torch.autograd.Function):
             db = torch.empty((Co,), dtype=torch.float32, device=x.device) if need_db else None
             ws = torch.empty((L.lib().bnn_conv2d_bwd_filter_workspace(N, C, Co, KH, KW, groups),),
                              dtype=torch.uint8, device=x.device)
-            zq, zb, zf, dyp, mean, invstd, gw, gb, sg, sgx, inv_n, ht = bn
-            with _timed("conv2d_bwd_filter_bn", 2 * macs, zq.numel() * zq.element_size() + 4 * dyp.numel()):
-                L.call("bnn_conv2d_bwd_filter_bn", zq, zb, zf, dyp, mean, invstd, gw, gb, sg, sgx, float(inv_n),
-                       int(ht), x, int(binarize_input), dw, db, ws, N, C, H, W, Co, KH, KW, stride, padding, dilation,
-                       groups, L.stream())
+            with _timed("conv2d_bwd_filter_bn", 2 * macs,
+                        bn.zq.numel() * bn.zq.element_size() + 4 * bn.dyp.numel()):
+                L.call("bnn_conv2d_bwd_filter_bn", bn.zq, bn.zb, bn.zf, bn.dyp, bn.mean, bn.invstd, bn.gw, bn.gb,
+                       bn.sg, bn.sgx, float(bn.inv_n), int(bn.ht), x, int(binarize_input), dw, db, ws, N, C, H, W,
+                       Co, KH, KW, stride, padding, dilation, groups, L.stream())
             C1BN_HANDOFFS += 1
             return (None, dw if ctx.needs_input_grad[1] else None, db, None, None, None, None, None, None, None)
         if ctx.needs_input_grad[0]:
@@ -1587,14 +1655,13 @@ def _bn2d_dy_of_handoff(bn, shape):
     """The fp32 gradient of the conv output a conv1 / BatchNorm2d hand-off stands for: the pooled
     BatchNorm2d(+Hardtanh) backward written out by bnn_bn2d_bwd_q (its dgamma / dbeta, already
     delivered by the BatchNorm's own backward, go to scratch)."""
-    zq, zb, zf, dyp, mean, invstd, gw, gb, sg, sgx, inv_n, ht = bn
     N, C, H, W = shape
-    dev = dyp.device
+    dev = bn.dyp.device
     dz = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
     scratch = torch.empty((2, C), dtype=torch.float32, device=dev)
     ws = torch.empty((L.lib().bnn_bn2d_workspace(N, C),), dtype=torch.uint8, device=dev)
-    L.call("bnn_bn2d_bwd_q", zq, zb, zf, dyp, N, C, H, W, gw, gb, mean, invstd, int(ht), 2, dz, scratch[0], scratch[1],
-           ws, L.stream())
+    L.call("bnn_bn2d_bwd_q", bn.zq, bn.zb, bn.zf, bn.dyp, N, C, H, W, bn.gw, bn.gb, bn.mean, bn.invstd, int(bn.ht), 2,
+           dz, scratch[0], scratch[1], ws, L.stream())
     return dz
 
 
@@ -1716,6 +1783,30 @@ def _bn_ws(M, C, device):
     return torch.empty((L.lib().bnn_bn_workspace(M, C),), dtype=torch.uint8, device=device)
 
 
+def _detached(*ts):
+    return [t.detach() if t is not None else None for t in ts]
+
+
+def _bn_momentum(momentum):
+    return float(momentum if momentum is not None else -1.0)     # the library's argument; negative: none given
+
+
+def _bn_fwd_stats(z, M, C, w, b, rm, rv, mom, eps, mean, invstd, mlo, ws, drop=None):
+    """The training-mode statistics pass alone (no output written) over the PreAct z, f32 or z16; drop =
+    (p, seed, keep-bit plane or None): the statistics of drop(z).  The fp32 entries take an output and the
+    Hardtanh flag and come with and without dropout; the one z16 entry always takes the dropout's arguments."""
+    out = () if z.compact else (None, 1)
+    tail = drop if drop is not None else (0.0, 0, None) if z.compact else ()
+    L.call(_entry("bnn_bn_fwd_train", z, "" if drop is None else "_dropout"), *z.args, M, C, w, b, rm, rv, mom,
+           float(eps), mean, invstd, mlo, *out, *tail, ws, L.stream())
+
+
+def _bn_param_grads(C, gamma, beta, device):
+    """Uninitialised (dgamma, dbeta) [C] for the affine parameters the BatchNorm has."""
+    return (torch.empty((C,), dtype=torch.float32, device=device) if gamma is not None else None,
+            torch.empty((C,), dtype=torch.float32, device=device) if beta is not None else None)
+
+
 STATS_TAP = None   # tests: a list that receives the [3, C] (save_mean, save_invstd, save_mean_lo) of
                    # every training-mode BatchNorm1d forward, in call order
 
@@ -1760,57 +1851,48 @@ def _q6_wanted(x, C, training=True):
 Q6_HANDOFFS = 0           # FP6 digit hand-offs consumed by a linear backward (tests check they ran)
 
 
-def _q6_take(dy):
-    """(rows Fp6Operand, cols Fp6Operand, colsum) attached to ``dy`` by bnn_bn_bwd_q6, or None."""
+def _q6_take(dy, lost=None):
+    """(rows Fp6Operand, cols Fp6Operand, colsum) attached to ``dy`` by bnn_bn_bwd_q6, or None (a
+    stale payload too: the linear then quantises dy itself)."""
     global Q6_HANDOFFS
-    ent = getattr(dy, _Q6_ATTR, None)
-    if ent is None:
-        return None
-    delattr(dy, _Q6_ATTR)
-    if ent[0] != _q6_key(dy):
-        return None
-    Q6_HANDOFFS += 1
-    return ent[1:]
-
-
-def _dz_placeholder(M, C, device):
-    """The gradient of a z16 pre-activation: its only reader is the producing linear's backward,
-    which takes the FP6 digits handed to it, so dz itself is never written (a stride-0 tensor of
-    the right shape carries the hand-off)."""
-    return _placeholder((M, C), device)
+    pre = _take(dy, _Q6_ATTR, lost=lost)
+    if pre is not None:
+        Q6_HANDOFFS += 1
+    return pre
 
 
 def _q6_take_required(dy):
-    pre = _q6_take(dy)
-    if pre is None and dy.dim() == 2 and dy.stride() == (0, 0) and _is_placeholder(dy):
-        raise RuntimeError("a z16 gradient placeholder lost its FP6 hand-off (was the pre-activation consumed twice?)")
-    return pre
+    return _q6_take(dy, lost="a z16 gradient placeholder lost its FP6 hand-off (was the pre-activation "
+                              "consumed twice?)")
+
+
+def _q6_buffers(M, C, dev):
+    """The operands of an FP6 digit hand-off of an [M, C] gradient: (rows, cols, column sums)."""
+    Mp = round_up(M)
+    return (Fp6Operand(*_fp6_buffers(M, C, dev), M, C, _res_buffer(M, C, dev)),
+            Fp6Operand(*_fp6_buffers(C, Mp, dev), C, Mp), torch.empty((C,), dtype=torch.float32, device=dev))
 
 
 def _bn_bwd_q6(x, dy, M, C, w, b, mean, invstd, mlo, hardtanh, p, seed, dw, db, ws, name, z16=None, pre=None):
     """BatchNorm(+Dropout) backward that also quantises dz (returned, with the digits attached).
-    z16 = (int16, bias): the input in its compact form (x unused); dz is then not written (the
-    returned gradient is a placeholder carrying only the digits, _dz_placeholder).  pre = (part, R):
-    the statistics from the dX GEMM's epilogue (gemm_fp6_bnstats mode 1; p = 0)."""
+    x: the input, an fp32 tensor or a PreAct; or z16 = (int16, bias): the input in its compact form
+    (x unused).  dz of a compact input is not written: its one reader, the producing linear's backward,
+    takes the digits, which the returned placeholder carries.  pre = (part, R): the statistics from the
+    dX GEMM's epilogue (gemm_fp6_bnstats mode 1; p = 0)."""
+    z = PreAct("z16", *z16) if z16 is not None else x if isinstance(x, PreAct) else PreAct("f32", x)
     dev = dy.device
-    dx = torch.empty((M, C), dtype=torch.float32, device=dev) if z16 is None else _dz_placeholder(M, C, dev)
-    rows = Fp6Operand(*_fp6_buffers(M, C, dev), M, C, _res_buffer(M, C, dev))
-    Mp = round_up(M)
-    cols = Fp6Operand(*_fp6_buffers(C, Mp, dev), C, Mp)
-    cs = torch.empty((C,), dtype=torch.float32, device=dev)
-    xb, dzb = (8, 4) if z16 is None else (4, 0)   # bytes per element: two passes over x, the dz write
+    dx = _placeholder((M, C), dev) if z.compact else torch.empty((M, C), dtype=torch.float32, device=dev)
+    rows, cols, cs = _q6_buffers(M, C, dev)
+    passes = 1 if pre is not None else 2            # over x and dy: one when the statistics came with dy
     if pre is not None:
-        xb //= 2                                    # one pass over x and dy: the statistics came with dy
         L.call("bnn_bn_bwd_stats_pre", pre[0], pre[1], M, C, 1, w, invstd, dw, db, None, None, ws, L.stream())
-    sfx, xin = ("", (x,)) if z16 is None else ("_i16", z16)
-    sfx += "_pre" if pre is not None else ""
     rb = 0.5 if rows.res is not None else 0.0
-    with _timed(name, 0, xb * M * C + (4 if pre is not None else 8) * M * C + dzb * M * C + (3 + rb) * M * C + 3 * C * Mp
-                + M * C // 16):
-        L.call("bnn_bn_bwd_q6" + sfx, *xin, dy, M, C, w, b, mean, invstd, mlo, int(hardtanh), float(p), int(seed),
-               dx if z16 is None else None, dw, db, rows.lo, rows.hi, rows.sc, rows.res, cols.lo, cols.hi, cols.sc, cs,
-               ws, L.stream())
-    setattr(dx, _Q6_ATTR, (_q6_key(dx), rows, cols, cs))
+    with _timed(name, 0, passes * (z.nbytes + 4) * M * C + (0 if z.compact else 4) * M * C + (3 + rb) * M * C
+                + 3 * C * cols.Kp + M * C // 16):
+        L.call(_entry("bnn_bn_bwd_q6", z, "_pre" if pre is not None else ""), *z.args, dy, M, C, w, b, mean, invstd,
+               mlo, int(hardtanh), float(p), int(seed), None if z.compact else dx, dw, db, rows.lo, rows.hi, rows.sc,
+               rows.res, cols.lo, cols.hi, cols.sc, cs, ws, L.stream())
+    _attach(dx, _Q6_ATTR, rows, cols, cs)
     return dx
 
 
@@ -1825,9 +1907,10 @@ I8C_HANDOFFS = 0          # hand-offs made (tests check the path actually ran)
 
 def _bn_bwd_i8c(x, dy, M, C, w, b, mean, invstd, mlo, dw, db, pre=None, s20=None):
     """pre = (part, R): the statistics and the digit bound's maxima from the dX GEMM's epilogue
-    (gemm_fp6_bnstats mode 2).  s20 = (low bits, nibbles, bias, scale): x in its compact form
-    (x unused)."""
-    dev = x.device
+    (gemm_fp6_bnstats mode 2).  x: the input, an fp32 tensor or a PreAct; or s20 = (low bits, nibbles,
+    bias, scale): the input in its compact form (x unused)."""
+    z = PreAct("s20", *s20) if s20 is not None else x if isinstance(x, PreAct) else PreAct("f32", x)
+    dev = dy.device
     ldqt = round_up(M)
     dg = torch.empty((3, C, ldqt), dtype=torch.int8, device=dev)
     sc = torch.empty((C,), dtype=torch.float32, device=dev)
@@ -1836,29 +1919,19 @@ def _bn_bwd_i8c(x, dy, M, C, w, b, mean, invstd, mlo, dw, db, pre=None, s20=None
     ws = torch.empty((L.lib().bnn_bn_bwd_i8cols_workspace(M, C),), dtype=torch.uint8, device=dev)
     if pre is not None:
         L.call("bnn_bn_bwd_stats_pre", pre[0], pre[1], M, C, 2, w, invstd, dw, db, sc, ds, ws, L.stream())
-    xb = 2.5 if s20 is not None else 4
-    with _timed("bn_bwd_i8cols", 0, (xb + 4) * (1 if pre is not None else 2) * M * C + dg.numel()):
-        sfx, xin = ("", (x,)) if s20 is None else ("_s20", s20)
-        sfx += "_pre" if pre is not None else ""
-        L.call("bnn_bn_bwd_i8cols" + sfx, *xin, dy, M, C, w, b, mean, invstd, mlo, 1, dw, db, dg, ldqt, C * ldqt, sc,
-               cs, ds, ws, L.stream())
-    dz = _dz_placeholder(M, C, dev)
-    setattr(dz, _I8C_ATTR, (_q6_key(dz), dg, sc, cs, ds))
+    with _timed("bn_bwd_i8cols", 0, (z.nbytes + 4) * (1 if pre is not None else 2) * M * C + dg.numel()):
+        L.call(_entry("bnn_bn_bwd_i8cols", z, "_pre" if pre is not None else ""), *z.args, dy, M, C, w, b, mean, invstd,
+               mlo, 1, dw, db, dg, ldqt, C * ldqt, sc, cs, ds, ws, L.stream())
+    dz = _placeholder((M, C), dev)
+    _attach(dz, _I8C_ATTR, dg, sc, cs, ds)
     global I8C_HANDOFFS
     I8C_HANDOFFS += 1
     return dz
 
 
 def _i8c_take(dy):
-    ent = getattr(dy, _I8C_ATTR, None)
-    if ent is None:
-        if dy.dim() == 2 and dy.stride() == (0, 0) and _is_placeholder(dy):
-            raise RuntimeError("a gradient placeholder lost its int8 column-digit hand-off")
-        return None
-    delattr(dy, _I8C_ATTR)
-    if ent[0] != _q6_key(dy):
-        raise RuntimeError("stale int8 column-digit hand-off")
-    return ent[1:]
+    return _take(dy, _I8C_ATTR, stale="stale int8 column-digit hand-off",
+                 lost="a gradient placeholder lost its int8 column-digit hand-off")
 
 
 class BatchNormHardtanhFunction(torch.autograd.Function):
@@ -1874,15 +1947,13 @@ class BatchNormHardtanhFunction(torch.autograd.Function):
         x = _c2d(x)
         M, C = x.shape
         y = torch.empty_like(x)
-        w = weight.detach() if weight is not None else None
-        b = bias.detach() if bias is not None else None
+        w, b = _detached(weight, bias)
         ws = _bn_ws(M, C, x.device)
         if training:
             mean, invstd, mlo = _bn_stat_buffers(C, x.device)
             with _timed("bn_fwd_train", 0, 12 * M * C):
-                L.call("bnn_bn_fwd_train", x, M, C, w, b, running_mean, running_var,
-                       float(momentum if momentum is not None else -1.0), float(eps), mean, invstd, mlo, y,
-                       int(hardtanh), ws, L.stream())
+                L.call("bnn_bn_fwd_train", x, M, C, w, b, running_mean, running_var, _bn_momentum(momentum),
+                       float(eps), mean, invstd, mlo, y, int(hardtanh), ws, L.stream())
         else:
             mean, mlo = running_mean, None
             invstd = (running_var + eps).rsqrt()
@@ -1890,8 +1961,7 @@ class BatchNormHardtanhFunction(torch.autograd.Function):
                 L.call("bnn_bn_fwd_eval", x, M, C, w, b, running_mean, running_var, float(eps), y, int(hardtanh), ws,
                        L.stream())
         ctx.save_for_backward(x, w, b, mean, invstd, mlo)
-        ctx.hardtanh = hardtanh
-        ctx.training = training
+        ctx.hardtanh, ctx.training = hardtanh, training
         return y
 
     @staticmethod
@@ -1900,8 +1970,7 @@ class BatchNormHardtanhFunction(torch.autograd.Function):
         dy = _c2d(dy)
         M, C = x.shape
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dw = torch.empty((C,), dtype=torch.float32, device=x.device) if w is not None else None
-        db = torch.empty((C,), dtype=torch.float32, device=x.device) if b is not None else None
+        dw, db = _bn_param_grads(C, w, b, x.device)
         ws = _bn_ws(M, C, x.device)
         if ctx.q6 and dx is not None:
             dx = _bn_bwd_q6(x, dy, M, C, w, b, mean, invstd, mlo, ctx.hardtanh, 0.0, 0, dw, db, ws, "bn_bwd_q6")
@@ -1924,14 +1993,12 @@ class DropoutBatchNormHardtanhFunction(torch.autograd.Function):
         x = _c2d(x)
         M, C = x.shape
         y = torch.empty_like(x)
-        w = weight.detach() if weight is not None else None
-        b = bias.detach() if bias is not None else None
+        w, b = _detached(weight, bias)
         ws = _bn_ws(M, C, x.device)
         mean, invstd, mlo = _bn_stat_buffers(C, x.device)
         with _timed("bn_dropout_fwd_train", 0, 12 * M * C):
-            L.call("bnn_bn_dropout_fwd_train", x, M, C, w, b, running_mean, running_var,
-                   float(momentum if momentum is not None else -1.0), float(eps), mean, invstd, mlo, y, 1, float(p),
-                   int(seed), None, ws, L.stream())
+            L.call("bnn_bn_dropout_fwd_train", x, M, C, w, b, running_mean, running_var, _bn_momentum(momentum),
+                   float(eps), mean, invstd, mlo, y, 1, float(p), int(seed), None, ws, L.stream())
         ctx.save_for_backward(x, w, b, mean, invstd, mlo)
         ctx.p, ctx.seed = p, seed
         return y
@@ -1942,17 +2009,15 @@ class DropoutBatchNormHardtanhFunction(torch.autograd.Function):
         dy = _c2d(dy)
         M, C = x.shape
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dw = torch.empty((C,), dtype=torch.float32, device=x.device) if w is not None else None
-        db = torch.empty((C,), dtype=torch.float32, device=x.device) if b is not None else None
+        dw, db = _bn_param_grads(C, w, b, x.device)
         ws = _bn_ws(M, C, x.device)
         if ctx.q6 and dx is not None:
             dx = _bn_bwd_q6(x, dy, M, C, w, b, mean, invstd, mlo, True, ctx.p, ctx.seed, dw, db, ws,
                             "bn_dropout_bwd_q6")
-            return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None,
-                    None, None, None, None, None, None)
-        with _timed("bn_dropout_bwd", 0, 16 * M * C):
-            L.call("bnn_bn_dropout_bwd", x, dy, M, C, w, b, mean, invstd, mlo, 1, float(ctx.p), int(ctx.seed), dx, dw,
-                   db, ws, L.stream())
+        else:
+            with _timed("bn_dropout_bwd", 0, 16 * M * C):
+                L.call("bnn_bn_dropout_bwd", x, dy, M, C, w, b, mean, invstd, mlo, 1, float(ctx.p), int(ctx.seed), dx,
+                       dw, db, ws, L.stream())
         return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None, None)
 
@@ -1977,16 +2042,13 @@ class DropoutBNHardtanhLinearFunction(torch.autograd.Function):
         global HEAD_CALLS
         HEAD_CALLS += 1
         ctx.q6 = _q6_wanted(z, z.shape[-1])
-        zz = _z16_of(z)                       # (int16, bias): the compact pre-activation
-        if zz is None:
-            z = _c2d(z)
+        fs = _fstats_of(z, *z.shape, (float(p), int(seed)))
+        z = _preact_of(z, ("z16",))
         M, C = z.shape
-        gw = weight.detach() if weight is not None else None
-        gb = bias.detach() if bias is not None else None
+        gw, gb = _detached(weight, bias)
         ws = _bn_ws(M, C, z.device)
         mean, invstd, mlo = _bn_stat_buffers(C, z.device)
-        mom = float(momentum if momentum is not None else -1.0)
-        fs = _fstats_of(z, M, C, (float(p), int(seed)))
+        mom = _bn_momentum(momentum)
         kb = None   # the dropout keep-bit plane: written by the statistics pass, read by the head passes
         if fs is not None and float(p) > 0:
             global FP4_STATS_USES
@@ -1997,54 +2059,39 @@ class DropoutBNHardtanhLinearFunction(torch.autograd.Function):
             if float(p) > 0 and _KEEP_BITS[0]:
                 kb = torch.empty((int(L.lib().bnn_dropout_keep_bits_bytes(M, C)) // 4,), dtype=torch.int32,
                                  device=z.device)
-            with _timed("bn_dropout_fwd_stats", 0, (4 if zz is None else 2) * M * C):
-                if zz is None:
-                    L.call("bnn_bn_dropout_fwd_train", z, M, C, gw, gb, running_mean, running_var, mom, float(eps),
-                           mean, invstd, mlo, None, 1, float(p), int(seed), kb, ws, L.stream())
-                else:
-                    L.call("bnn_bn_fwd_train_i16", zz[0], zz[1], M, C, gw, gb, running_mean, running_var, mom,
-                           float(eps), mean, invstd, mlo, float(p), int(seed), kb, ws, L.stream())
+            with _timed("bn_dropout_fwd_stats", 0, z.nbytes * M * C):
+                _bn_fwd_stats(z, M, C, gw, gb, running_mean, running_var, mom, eps, mean, invstd, mlo, ws,
+                              drop=(float(p), int(seed), kb))
         w4c = w4.detach().contiguous()
         y4 = torch.empty((M, HEAD_NOUT), dtype=torch.float32, device=z.device)
         b4d = b4.detach() if b4 is not None else None
-        sfx, xin = ("", (z,)) if zz is None else ("_i16", zz)
-        with _timed("bn_head_fwd", 0, (4 if zz is None else 2) * M * C + 4 * M * HEAD_NOUT):
-            L.call("bnn_bn_head_fwd" + sfx, *xin, M, C, mean, invstd, mlo, gw, gb, float(p), int(seed), kb, w4c,
+        with _timed("bn_head_fwd", 0, z.nbytes * M * C + 4 * M * HEAD_NOUT):
+            L.call(_entry("bnn_bn_head_fwd", z), *z.args, M, C, mean, invstd, mlo, gw, gb, float(p), int(seed), kb, w4c,
                    HEAD_NOUT, b4d, y4, L.stream())
-        if zz is None:
-            ctx.save_for_backward(z, gw, gb, mean, invstd, mlo, w4c, None)
-        else:
-            ctx.save_for_backward(zz[0], gw, gb, mean, invstd, mlo, w4c, zz[1])
-        ctx.z16 = zz is not None
-        ctx.dims = (M, C)
-        ctx.p, ctx.seed = p, seed
-        ctx.kb = kb
+        ctx.save_for_backward(*z.saved(), gw, gb, mean, invstd, mlo, w4c)
+        ctx.z = z.meta()
+        ctx.p, ctx.seed, ctx.kb = p, seed, kb
         ctx.has_b4 = b4 is not None
         return y4
 
     @staticmethod
     def backward(ctx, dy4):
-        z, gw, gb, mean, invstd, mlo, w4c, zb = ctx.saved_tensors
+        *zt, gw, gb, mean, invstd, mlo, w4c = ctx.saved_tensors
+        z = PreAct.restored(ctx.z, zt)
         dy4 = _c2d(dy4)
-        M, C = ctx.dims
-        dev = z.device
-        # z16 input: its producer's backward takes the digits; dz itself is never written
-        dx = _dz_placeholder(M, C, dev) if ctx.z16 else torch.empty((M, C), dtype=torch.float32, device=dev)
-        dgw = torch.empty((C,), dtype=torch.float32, device=dev) if gw is not None else None
-        dgb = torch.empty((C,), dtype=torch.float32, device=dev) if gb is not None else None
+        (M, C), dev = z.shape, z.device
+        # compact input: its producer's backward takes the digits; dz itself is never written
+        dx = _placeholder((M, C), dev) if z.compact else torch.empty((M, C), dtype=torch.float32, device=dev)
+        dgw, dgb = _bn_param_grads(C, gw, gb, dev)
         dw4 = torch.empty((HEAD_NOUT, C), dtype=torch.float32, device=dev)
-        rows = Fp6Operand(*_fp6_buffers(M, C, dev), M, C, _res_buffer(M, C, dev))
-        Mp = round_up(M)
-        cols = Fp6Operand(*_fp6_buffers(C, Mp, dev), C, Mp)
-        cs = torch.empty((C,), dtype=torch.float32, device=dev)
+        rows, cols, cs = _q6_buffers(M, C, dev)
         ws = torch.empty((L.lib().bnn_bn_head_workspace(M, C, HEAD_NOUT),), dtype=torch.uint8, device=dev)
-        sfx, xin = ("_i16", (z, zb)) if ctx.z16 else ("", (z,))
-        with _timed("bn_head_bwd_q6", 0, (8 if ctx.z16 else 16) * M * C + (0 if ctx.z16 else 4) * M * C + 6 * M * C):
-            L.call("bnn_bn_head_bwd_q6" + sfx, *xin, dy4, w4c, HEAD_NOUT, M, C, gw, gb, mean, invstd, mlo, float(ctx.p),
-                   int(ctx.seed), ctx.kb, None if ctx.z16 else dx, dgw, dgb, dw4, rows.lo, rows.hi, rows.sc, rows.res,
-                   cols.lo, cols.hi, cols.sc, cs, ws, L.stream())
-        if ctx.q6 or ctx.z16:
-            setattr(dx, _Q6_ATTR, (_q6_key(dx), rows, cols, cs))
+        with _timed("bn_head_bwd_q6", 0, 4 * z.nbytes * M * C + (0 if z.compact else 4) * M * C + 6 * M * C):
+            L.call(_entry("bnn_bn_head_bwd_q6", z), *z.args, dy4, w4c, HEAD_NOUT, M, C, gw, gb, mean, invstd, mlo,
+                   float(ctx.p), int(ctx.seed), ctx.kb, None if z.compact else dx, dgw, dgb, dw4, rows.lo, rows.hi,
+                   rows.sc, rows.res, cols.lo, cols.hi, cols.sc, cs, ws, L.stream())
+        if ctx.q6 or z.compact:
+            _attach(dx, _Q6_ATTR, rows, cols, cs)
         db4 = None
         if ctx.has_b4 and ctx.needs_input_grad[10]:
             if COL_SUMS and M <= 32768 and dy4.is_contiguous():   # one libbnn launch (fixed order)
@@ -2105,8 +2152,7 @@ def dropout_batch_norm_hardtanh(x, p, bn, seed=None):
     """nn.Dropout(p) -> nn.BatchNorm1d module (training mode) -> Hardtanh through libbnn.  The seed
     is drawn from torch's CPU generator (so torch.manual_seed makes runs repeatable) unless given."""
     if seed is None:
-        # device-step mode: a fixed base seed, the kernels add the device step counter
-        seed = _DEVICE_STEP.base_seed if _DEVICE_STEP is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        seed = dropout_seed()
     rm, rv, bn_training, factor = _bn_module_args(bn)
     if not bn_training:
         raise ValueError("dropout_batch_norm_hardtanh is the training-mode fusion")
@@ -2172,78 +2218,59 @@ class BatchNorm2dHardtanhPoolFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, training, momentum, eps, hardtanh, pool):
         _check(x, weight, bias, running_mean, running_var)
-        zq = _zq_of(x)                        # (int8/int16 sums, bias, fmt): x in its compact form
-        if zq is not None and not training:
+        c1bn = bool(getattr(x, _C1BN_WANT, False))
+        x = _preact_of(x, ("zq",))
+        if x.compact and not training:
             raise RuntimeError("a compact conv output needs the training-mode BatchNorm2d")
-        if zq is None:
-            x = x if x.is_contiguous() else x.contiguous()
+        ctx.c1bn = x.compact and training and pool == 2 and c1bn
         N, C, H, W = x.shape
         oh, ow = (H // 2, W // 2) if pool else (H, W)
         y = torch.empty((N, C, oh, ow), dtype=torch.float32, device=x.device)
-        w = weight.detach() if weight is not None else None
-        b = bias.detach() if bias is not None else None
+        w, b = _detached(weight, bias)
         ws = torch.empty((L.lib().bnn_bn2d_workspace(N, C),), dtype=torch.uint8, device=x.device)
         nel = N * C * H * W
         if training:
             mean = torch.empty((C,), dtype=torch.float32, device=x.device)
             invstd = torch.empty_like(mean)
-            xb = 4 if zq is None else zq[0].element_size()
-            with _timed("bn2d_fwd_train", 0, 2 * xb * nel + 4 * y.numel()):
-                if zq is None:
-                    L.call("bnn_bn2d_fwd_train", x, N, C, H, W, w, b, running_mean, running_var,
-                           float(momentum if momentum is not None else -1.0), float(eps), mean, invstd, y,
-                           int(hardtanh), int(pool), ws, L.stream())
-                else:
-                    L.call("bnn_bn2d_fwd_train_q", zq[0], zq[1], zq[2], N, C, H, W, w, b, running_mean, running_var,
-                           float(momentum if momentum is not None else -1.0), float(eps), mean, invstd, y,
-                           int(hardtanh), int(pool), ws, L.stream())
+            with _timed("bn2d_fwd_train", 0, 2 * x.nbytes * nel + 4 * y.numel()):
+                L.call(_entry("bnn_bn2d_fwd_train", x), *x.args, N, C, H, W, w, b, running_mean, running_var,
+                       _bn_momentum(momentum), float(eps), mean, invstd, y, int(hardtanh), int(pool), ws, L.stream())
         else:
             mean = running_mean
             invstd = (running_var + eps).rsqrt()
             with _timed("bn2d_fwd_eval", 0, 4 * nel + 4 * y.numel()):
-                L.call("bnn_bn2d_fwd_eval", x, N, C, H, W, w, b, running_mean, running_var, float(eps), y,
+                L.call("bnn_bn2d_fwd_eval", x.x, N, C, H, W, w, b, running_mean, running_var, float(eps), y,
                        int(hardtanh), int(pool), ws, L.stream())
-        if zq is None:
-            ctx.save_for_backward(x, w, b, mean, invstd, None, None)
-        else:
-            ctx.save_for_backward(zq[0], w, b, mean, invstd, zq[1], None)
-        ctx.zq_fmt = 0 if zq is None else zq[2]
-        ctx.c1bn = (zq is not None and training and pool == 2 and bool(getattr(x, _C1BN_WANT, False)))
-        ctx.shape = (N, C, H, W)
-        ctx.hardtanh, ctx.pool = hardtanh, pool
-        ctx.training = training
+        ctx.save_for_backward(*x.saved(), w, b, mean, invstd)
+        ctx.x = x.meta()
+        ctx.hardtanh, ctx.pool, ctx.training = hardtanh, pool, training
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, w, b, mean, invstd, xbias, _ = ctx.saved_tensors
+        *xt, w, b, mean, invstd = ctx.saved_tensors
+        x = PreAct.restored(ctx.x, xt)
         dy = dy if dy.is_contiguous() else dy.contiguous()
-        N, C, H, W = ctx.shape
+        N, C, H, W = x.shape
         dx = torch.empty((N, C, H, W), dtype=torch.float32, device=dy.device) if ctx.needs_input_grad[0] else None
-        dw = torch.empty((C,), dtype=torch.float32, device=dy.device) if w is not None else None
-        db = torch.empty((C,), dtype=torch.float32, device=dy.device) if b is not None else None
+        dw, db = _bn_param_grads(C, w, b, dy.device)
         ws = torch.empty((L.lib().bnn_bn2d_workspace(N, C),), dtype=torch.uint8, device=dy.device)
         nel = N * C * H * W
-        xb = 4 if ctx.zq_fmt == 0 else x.element_size()
         if ctx.c1bn and ctx.needs_input_grad[0]:
             # statistics only; the conv's filter gradient forms dx from them (bnn_conv2d_bwd_filter_bn)
             sg = torch.empty((C,), dtype=torch.float32, device=dy.device)
             sgx = torch.empty_like(sg)
-            with _timed("bn2d_bwd_stats", 0, xb * nel + 4 * dy.numel()):
-                L.call("bnn_bn2d_bwd_stats_q", x, xbias, ctx.zq_fmt, dy, N, C, H, W, w, b, mean, invstd,
+            with _timed("bn2d_bwd_stats", 0, x.nbytes * nel + 4 * dy.numel()):
+                L.call(_entry("bnn_bn2d_bwd_stats", x), *x.args, dy, N, C, H, W, w, b, mean, invstd,
                        int(ctx.hardtanh), int(ctx.pool), dw, db, sg, sgx, ws, L.stream())
             dx = _placeholder((N, C, H, W), dy.device)
-            setattr(dx, _C1BN_ATTR, (_q6_key(dx), x, xbias, ctx.zq_fmt, dy, mean, invstd, w, b, sg, sgx,
-                                     1.0 / (N * H * W), int(ctx.hardtanh)))
-            return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None,
-                    None, None, None, None, None, None, None)
-        with _timed("bn2d_bwd", 0, (2 * xb + 4) * nel + 8 * dy.numel()):
-            if ctx.zq_fmt:
-                L.call("bnn_bn2d_bwd_q", x, xbias, ctx.zq_fmt, dy, N, C, H, W, w, b, mean, invstd, int(ctx.hardtanh),
-                       int(ctx.pool), dx, dw, db, ws, L.stream())
-            else:
-                L.call("bnn_bn2d_bwd" if ctx.training else "bnn_bn2d_bwd_eval", x, dy, N, C, H, W, w, b, mean, invstd,
-                       int(ctx.hardtanh), int(ctx.pool), dx, dw, db, ws, L.stream())
+            _attach(dx, _C1BN_ATTR, *_C1bnHandoff(*x.args, dy, mean, invstd, w, b, sg, sgx, 1.0 / (N * H * W),
+                                                  int(ctx.hardtanh)))
+        else:
+            with _timed("bn2d_bwd", 0, (2 * x.nbytes + 4) * nel + 8 * dy.numel()):
+                # (eval mode: the running statistics are constants; fp32 inputs only)
+                L.call(_entry("bnn_bn2d_bwd", x) if ctx.training else "bnn_bn2d_bwd_eval", *x.args, dy, N, C, H, W, w,
+                       b, mean, invstd, int(ctx.hardtanh), int(ctx.pool), dx, dw, db, ws, L.stream())
         return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None, None, None)
 
@@ -2281,27 +2308,23 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
         ctx.q6 = _q6_wanted(z, z.shape[-1], training)
         ctx.i8c = (I8C_HANDOFF and bool(getattr(z, _I8C_WANT, False)) and training and not ctx.q6
                    and z.dim() == 2 and z.shape[-1] % 4 == 0)
-        zz = _z16_of(z)                       # (int16, bias): z in its compact form
-        zs = _s20_of(z)                       # (int16 low bits, nibbles, bias, scale): fc1's compact z1
-        if zz is None and zs is None:
-            z = _c2d(z)
+        fs = _fstats_of(z, *z.shape)
+        z = _preact_of(z, ("z16", "s20"))     # fc's own z16 output of the layer before, or fc1's s20 z1
         M, C = z.shape
         N = weight.shape[0]
         fp4 = backend == "fp4"
         ctx.fp6 = fp4 and DIGIT_GEMM == "fp6"
-        if zz is not None and not (training and ctx.fp6 and ctx.q6 and C % 256 == 0):
+        if z.kind == "z16" and not (training and ctx.fp6 and ctx.q6 and C % 256 == 0):
             raise RuntimeError("a z16 pre-activation needs the training-mode FP4/FP6 consumer (z16_ok)")
-        if zs is not None and not (training and ctx.fp6 and ctx.i8c and C % 256 == 0 and _fstats_of(z, M, C)):
+        if z.kind == "s20" and not (training and ctx.fp6 and ctx.i8c and C % 256 == 0 and fs):
             raise RuntimeError("an s20 pre-activation needs the training-mode FP4/FP6 consumer with the "
                                "int8 column-digit backward and the GEMM-epilogue statistics")
-        gw = bn_w.detach() if bn_w is not None else None
-        gb = bn_b.detach() if bn_b is not None else None
+        gw, gb, b = _detached(bn_w, bn_b, bias)
         if training:
             mean, invstd, mlo = _bn_stat_buffers(C, z.device)
             ws = _bn_ws(M, C, z.device)
-            mom = float(momentum if momentum is not None else -1.0)
-            with _timed("bn_fwd_stats", 0, (4 if zz is None else 2) * M * C):
-                fs = _fstats_of(z, M, C)
+            mom = _bn_momentum(momentum)
+            with _timed("bn_fwd_stats", 0, z.nbytes * M * C):
                 if fs is not None:
                     global PIX_STATS_USES, FP4_STATS_USES
                     if fs[5] == "pixels":
@@ -2310,18 +2333,13 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
                         FP4_STATS_USES += 1
                     L.call("bnn_bn_fwd_final_parts", fs[0], fs[1], fs[2], M, C, rm, rv, mom, float(eps), mean, invstd,
                            mlo, L.stream())
-                elif zz is None:
-                    assert zs is None
-                    L.call("bnn_bn_fwd_train", z, M, C, gw, gb, rm, rv, mom, float(eps), mean, invstd, mlo, None, 1, ws,
-                           L.stream())
                 else:
-                    L.call("bnn_bn_fwd_train_i16", zz[0], zz[1], M, C, gw, gb, rm, rv, mom, float(eps), mean, invstd,
-                           mlo, 0.0, 0, None, ws, L.stream())
+                    _bn_fwd_stats(z, M, C, gw, gb, rm, rv, mom, eps, mean, invstd, mlo, ws)
         else:
             mean, mlo = rm.contiguous(), None
             invstd = (rv + eps).rsqrt()
         need_dh = any(ctx.needs_input_grad[:3])
-        need_dw = ctx.needs_input_grad[8] or zz is not None
+        need_dw = ctx.needs_input_grad[8] or z.kind == "z16"
         # FP6 backward: both GEMMs' B operands (this layer's X_b^T and W_b^T) are written straight in
         # the FP4 panel layout gemm_fp6 stages from (no panel pass)
         qf = "fp4p" if ctx.fp6 else "i8"
@@ -2329,21 +2347,14 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
                         dtype=torch.uint8 if fp4 else torch.int8, device=z.device)
         ctx.qt_panel = need_dw and qf == "fp4p"
         qt = _qt_buffer(C, M, qf, z.device) if need_dw else None
-        nx = 2.5 if zs is not None else (4 if zz is None else 2)
         with _timed("bn_apply_pack" if stochastic is None else "bn_apply_pack_stoch", 0,
-                    nx * M * C + q.numel() + (qt.numel() if qt is not None else 0)):
-            if zs is not None or zz is not None:      # the compact forms: FP4 rows, qt in panels or absent
-                sfx, xin = ("_s20", zs) if zs is not None else ("_i16", zz)
-                stoch, seed = ("", ()) if stochastic is None else ("_stoch", (_u64(stochastic),))
-                L.call("bnn_bn_apply_pack" + stoch + sfx, *xin, M, C, mean, invstd, mlo, gw, gb, q, q.shape[1], qt,
-                       qt.shape[1], 1 if ctx.qt_panel else 0, *seed, L.stream())
-            elif stochastic is not None:
-                L.call("bnn_bn_apply_pack_stoch", z, M, C, mean, invstd, mlo, gw, gb, 1 if fp4 else 0, q, q.shape[1],
-                       qt, qt.shape[1] if qt is not None else 0, _QT_CODE[qf], _u64(stochastic), 0, L.stream())
-            else:
-                L.call("bnn_bn_apply_pack", z, M, C, mean, invstd, mlo, gw, gb, 1 if fp4 else 0, q, q.shape[1], qt,
-                       qt.shape[1] if qt is not None else 0, _QT_CODE[qf], L.stream())
-        b = bias.detach() if bias is not None else None
+                    z.nbytes * M * C + q.numel() + (qt.numel() if qt is not None else 0)):
+            if z.compact:         # FP4 rows, qt in panels or absent: only the panel flag and the seed to say
+                fmt, tail = (), (1 if ctx.qt_panel else 0,) + (() if stochastic is None else (_u64(stochastic),))
+            else:                 # the operands' formats, and the stochastic entry's seed and force flag
+                fmt, tail = (1 if fp4 else 0,), (_QT_CODE[qf],) + (() if stochastic is None else (_u64(stochastic), 0))
+            L.call(_entry("bnn_bn_apply_pack", z, "" if stochastic is None else "_stoch"), *z.args, M, C, mean, invstd,
+                   mlo, gw, gb, *fmt, q, q.shape[1], qt, qt.shape[1] if qt is not None else 0, *tail, L.stream())
         wq, wqt = packed_weight(weight, "fp4" if fp4 else "i8", True, need_dh, cache=True, qt_fmt=qf)
         chunk = (int(L.lib().bnn_gemm_fp4_bnstats_chunk(M, N, q.shape[1]))
                  if emit_stats and FP4_STATS and fp4 and M > 0 and N % 4 == 0 else 0)
@@ -2352,13 +2363,12 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
             # the next BatchNorm reads z = fl(I + bias) from int16 I and the bias (a detached view of
             # the Parameter: its consumer saves it for backward, so torch refuses a backward after an
             # in-place update of it)
-            bs = b
             if chunk:
-                y16, fst = _fp4_fwd_with_stats(q, wq, M, N, C, None, bs, chunk, True, drop)
-                y = _z16_carrier(y16, bs)
+                y16, fst = _fp4_fwd_with_stats(q, wq, M, N, C, None, b, chunk, True, drop)
+                y = _preact_carrier(PreAct("z16", y16, b))
                 setattr(y, _FSTATS_ATTR, fst)
             else:
-                y = _z16_carrier(gemm_fp4_i16(q, wq, M, N, k_true=C), bs)
+                y = _preact_carrier(PreAct("z16", gemm_fp4_i16(q, wq, M, N, k_true=C), b))
         elif fp4 and chunk:
             y, fst = _fp4_fwd_with_stats(q, wq, M, N, C, b, b, chunk, False, drop)
             setattr(y, _FSTATS_ATTR, fst)
@@ -2366,27 +2376,18 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
             y = gemm_fp4(q, wq, M, N, bias=b, k_true=C)
         else:
             y = gemm_i8(q, 1, wq, 1, M, N, bias=b, k_true=C)
-        if zs is not None:
-            ctx.save_for_backward(zs[0], gw, gb, mean, invstd, mlo, qt, wqt, zs[2])
-            ctx.s20 = (zs[1], zs[3])          # the nibble plane and the scale
-        elif zz is None:
-            ctx.save_for_backward(z, gw, gb, mean, invstd, mlo, qt, wqt, None)
-        else:
-            ctx.save_for_backward(zz[0], gw, gb, mean, invstd, mlo, qt, wqt, zz[1])
-        if zs is None:
-            ctx.s20 = None
-        ctx.z16 = zz is not None
-        ctx.weight_ref = weight
-        ctx.training = training
-        ctx.dims = (M, C, N)
-        ctx.has_bias = bias is not None
+        ctx.save_for_backward(*z.saved(), gw, gb, mean, invstd, mlo, qt, wqt)
+        ctx.z = z.meta()
+        ctx.weight_ref, ctx.training = weight, training
+        ctx.dims, ctx.has_bias = (M, C, N), bias is not None
         if ctx.fp6:
             setattr(y, _Q6_WANT, True)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        z, gw, gb, mean, invstd, mlo, qt, wqt, zb = ctx.saved_tensors
+        *zt, gw, gb, mean, invstd, mlo, qt, wqt = ctx.saved_tensors
+        z = PreAct.restored(ctx.z, zt)
         M, C, N = ctx.dims
         pre = _q6_take_required(dy) if ctx.fp6 else None       # digits of dy from the BatchNorm backward
         if pre is None:
@@ -2415,10 +2416,11 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
             st = None
             if ctx.fp6:
                 A = pre[0] if pre is not None else quant6_rows(dy)
-                if ctx.training and (ctx.q6 or ctx.i8c) and ctx.s20 is None and _bn_epi_ok(M, C, A.Kp):
+                if ctx.training and (ctx.q6 or ctx.i8c) and z.kind != "s20" and _bn_epi_ok(M, C, A.Kp):
                     # the BatchNorm backward's statistics come with dh from the GEMM's epilogue
-                    dh, part, R = gemm_fp6_bnstats(A, wqt, wqt.shape[1] // 32, C, z, zb if ctx.z16 else None,
-                                                   ctx.z16, mean, mlo, invstd, gw, gb, 1 if ctx.q6 else 2)
+                    z16 = z.kind == "z16"
+                    dh, part, R = gemm_fp6_bnstats(A, wqt, wqt.shape[1] // 32, C, z.x, z.args[1] if z16 else None,
+                                                   z16, mean, mlo, invstd, gw, gb, 1 if ctx.q6 else 2)
                     st = (part, R)
                 else:
                     dh = gemm_fp6(A, None, C, k_true=N, panels=wqt, panel_ks=wqt.shape[1] // 32)   # dY . W_b
@@ -2427,19 +2429,16 @@ class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
                 d, s = quant_rows(dy)
                 dh = gemm_i8(d, 3, wqt, 1, M, C, a_scale=s, k_true=N)
             del pre
-            dgw = torch.empty((C,), dtype=torch.float32, device=z.device) if gw is not None else None
-            dgb = torch.empty((C,), dtype=torch.float32, device=z.device) if gb is not None else None
+            dgw, dgb = _bn_param_grads(C, gw, gb, z.device)
             ws = _bn_ws(M, C, z.device)
             if ctx.q6:
-                dz = _bn_bwd_q6(z, dh, M, C, gw, gb, mean, invstd, mlo, True, 0.0, 0, dgw, dgb, ws, "bn_bwd_q6",
-                                z16=(z, zb) if ctx.z16 else None, pre=st)
+                dz = _bn_bwd_q6(z, dh, M, C, gw, gb, mean, invstd, mlo, True, 0.0, 0, dgw, dgb, ws, "bn_bwd_q6", pre=st)
             elif ctx.i8c:
-                dz = _bn_bwd_i8c(z, dh, M, C, gw, gb, mean, invstd, mlo, dgw, dgb, pre=st,
-                                 s20=(z, ctx.s20[0], zb, ctx.s20[1]) if ctx.s20 is not None else None)
+                dz = _bn_bwd_i8c(z, dh, M, C, gw, gb, mean, invstd, mlo, dgw, dgb, pre=st)
             else:
-                dz = torch.empty_like(z)
+                dz = torch.empty_like(z.x)
                 with _timed("bn_bwd", 0, 16 * M * C):
-                    _bn_bwd_call(ctx.training, z, dh, M, C, gw, gb, mean, invstd, mlo, True, dz, dgw, dgb, ws)
+                    _bn_bwd_call(ctx.training, z.x, dh, M, C, gw, gb, mean, invstd, mlo, True, dz, dgw, dgb, ws)
         return (dz, dgw if ctx.needs_input_grad[1] else None, dgb if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None, dw, db, None, None, None, None)
 
