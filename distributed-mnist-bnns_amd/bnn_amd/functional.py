@@ -1460,6 +1460,77 @@ def hinge_loss(input, target, margin=1.0, squared=False):
     return HingeLossFunction.apply(input, target, float(margin), bool(squared))
 
 
+# ----------------------------------------------------------------------------- evaluation metrics
+class MetricAccumulators:
+    """The two accumulators of bnn_eval_metrics in one int64 buffer (one allocation, one zero fill, one
+    host read): ``loss_sum`` float64 [1] -- the sum of the counted rows' lse(z) - z[y] -- and ``counts``
+    int64 [3 + C * C]: rows, top-1 hits, top-k hits, then the C x C confusion cells (row = label).  Works
+    on any device; ``eval_metrics`` takes CUDA ones."""
+
+    def __init__(self, C, device="cuda"):
+        self.C = int(C)
+        self.buf = torch.zeros((4 + self.C * self.C,), dtype=torch.int64, device=device)
+        self.loss_sum = self.buf[:1].view(torch.float64)
+        self.counts = self.buf[1:]
+
+    def zero_(self):
+        self.buf.zero_()       # in place: a captured launch keeps adding to the same memory
+        return self
+
+    def read(self):
+        """(loss_sum, counts [3 + C * C] int64 CPU tensor) from one host read."""
+        host = self.buf.cpu()
+        return float(host[:1].view(torch.float64).item()), host[1:]
+
+
+_METRICS_WS = {}
+
+
+def _metrics_workspace(M, device):
+    key = (str(device), M)
+    ws = _METRICS_WS.get(key)
+    if ws is None:
+        ws = torch.empty((int(L.lib().bnn_eval_metrics_workspace(M)),), dtype=torch.uint8, device=device)
+        if not torch.cuda.is_current_stream_capturing():     # a capture's allocation stays in its graph's pool
+            _METRICS_WS[key] = ws
+    return ws
+
+
+def eval_metrics_ok(z, y):
+    """Whether eval_metrics takes (z, y): CUDA fp32 [M, C] rows with a class count libbnn has and int64
+    labels [M] on the same device."""
+    return (torch.is_tensor(z) and torch.is_tensor(y) and z.is_cuda and z.dim() == 2 and z.dtype == torch.float32
+            and bool(L.lib().bnn_eval_metrics_ok(z.shape[1])) and y.dim() == 1 and y.dtype == torch.int64
+            and y.shape[0] == z.shape[0] and y.device == z.device)
+
+
+def eval_metrics(z, y, k, acc, ignore_index=-100, pred=None):
+    """Add the rows of z [M, C] (logits or log-probabilities) against the labels y to ``acc`` (a
+    MetricAccumulators(C) on z's device): the loss sum, rows / top-1 / top-``k`` counts and the confusion
+    cells of bnn_eval_metrics, ranking and tie rule as include/bnn.h states them.  ``pred`` (int32 [M],
+    optional) receives every row's top-ranked column.  One launch up to 16384 rows, two beyond; no host
+    synchronisation, capturable.  Returns ``acc``."""
+    _check(z)
+    if not eval_metrics_ok(z, y):
+        raise ValueError("bnn_amd: eval_metrics needs float32 CUDA [M, C] rows (C in 2, 10, 16, 32, 64) and int64 [M] "
+                         f"labels on the same device; got {tuple(z.shape)} {z.dtype} and {tuple(y.shape)} {y.dtype}")
+    M, C = z.shape
+    if acc.C != C or acc.buf.device != z.device:
+        raise ValueError(f"bnn_amd: eval_metrics: accumulators for C = {acc.C} on {acc.buf.device}, rows with "
+                         f"C = {C} on {z.device}")
+    if pred is not None and not (pred.dtype == torch.int32 and pred.shape == (M,) and pred.device == z.device
+                                 and pred.is_contiguous()):
+        raise ValueError("bnn_amd: eval_metrics: pred must be a contiguous int32 [M] tensor on z's device")
+    if M == 0:
+        return acc
+    z, y = z.contiguous(), y.contiguous()
+    work = _metrics_workspace(M, z.device)
+    with _timed("eval_metrics", 0, 4 * M * C + 8 * M + (4 * M if pred is not None else 0)):
+        L.call("bnn_eval_metrics", z, y, M, C, int(k), int(ignore_index), acc.loss_sum, acc.counts, pred, work,
+               work.numel(), L.stream())
+    return acc
+
+
 # ----------------------------------------------------------------------------- conv2d
 def _pair_same(v, what):
     if isinstance(v, (tuple, list)):

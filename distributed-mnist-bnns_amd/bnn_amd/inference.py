@@ -25,6 +25,7 @@ import torch.nn.functional as tF
 from . import _lib as L
 from . import functional as BF
 from . import nets
+from .metrics import Meter
 
 __all__ = ["freeze", "from_state", "FrozenMLP", "FrozenCNN"]
 
@@ -245,6 +246,17 @@ class _Frozen:
         for i in range(0, n, batch):
             hits += (self.predict(x[i:i + batch]) == labels[i:i + batch].to(x.device)).sum()
         return float(hits.item()) / n
+
+    def evaluate(self, x, labels, k=5, batch=4096):
+        """The held-out metrics of a test loop over (x, labels), run in batches of ``batch``: ``forward`` and one
+        metrics launch per batch into one device accumulator, one host read at the end.  Returns
+        ``metrics.Meter.result()``: {"n", "loss" (mean cross-entropy), "prec1", "preck" (percent), "k" (clipped
+        to the class count), "confusion" (int64 [C, C], row = label)}.  CPU tensors run the plain-torch
+        restatements of both."""
+        meter = Meter(self.t[self.OUT].shape[0], k=k, device=x.device)
+        for i in range(0, x.shape[0], batch):
+            meter.update(self.forward(x[i:i + batch]), labels[i:i + batch].to(device=x.device, dtype=torch.int64))
+        return meter.result()
 
 
 class FrozenMLP(_Frozen):

@@ -14,7 +14,10 @@ DistributedSampler order with seed 0 and no set_epoch (:100-108),
 timing and the reference's log line (:139-146), optional CSVs in the reference's format
 (mnist-dist3.py:132-135).  Differences: RCCL instead of gloo, inputs held in HBM
 (synthetic MNIST-shaped data unless --idx-images/--idx-labels point at real idx files), fused
-BatchNorm+Hardtanh, no fp32 copy of sign(input).
+BatchNorm+Hardtanh, no fp32 copy of sign(input).  Evaluation (bnn_amd.metrics; all off by default):
+--eval-topk K adds the held-out loss, prec@1 and prec@K to --eval N, --eval-idx-images / --eval-idx-labels
+evaluate on idx files (t10k), --checkpoint-best PATH keeps the best epoch's weights (utils.save_checkpoint's
+is_best), --train-acc appends the training batches' prec@1 to the log line.
 """
 import argparse
 import os
@@ -32,6 +35,7 @@ from .checkpoint import load_checkpoint, save_checkpoint
 from .graph import GraphedStep
 from .data import load_idx_dataset, shard_indices, synthetic_mnist
 from .inference import freeze
+from .metrics import Meter
 from .optim import LatentAdam, LatentSGD
 from .parallel import GradExchange
 
@@ -92,10 +96,28 @@ def parse(argv=None):
     ap.add_argument("--resume", default=None, help="resume from a checkpoint written by --checkpoint")
     ap.add_argument("--eval", type=int, default=0, metavar="N", help="after every epoch rank 0 freezes the model "
                     "(bnn_amd.inference) and prints its accuracy on N held-out samples")
+    ap.add_argument("--eval-topk", type=int, default=0, metavar="K", help="with --eval: also print the held-out loss, "
+                    "prec@1 and prec@K (bnn_amd.metrics; utils.accuracy's numbers), K in 1..10")
+    ap.add_argument("--eval-idx-images", default=None, help="with --eval N: evaluate on the first N images of this idx "
+                    "file (t10k) instead of the synthetic held-out draw; needs --eval-idx-labels")
+    ap.add_argument("--eval-idx-labels", default=None)
+    ap.add_argument("--checkpoint-best", default=None, metavar="PATH", help="with --eval: write a checkpoint here after "
+                    "every evaluation whose prec@1 is above the best so far (utils.save_checkpoint's is_best)")
+    ap.add_argument("--train-acc", action="store_true", help="count prec@1 of the training batches on the device and "
+                    "append it to the log line")
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--master-addr", default=os.environ.get("MASTER_ADDR", "127.0.0.1"))
     ap.add_argument("--master-port", default=os.environ.get("MASTER_PORT", "23456"))
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not 0 <= args.eval_topk <= 10:
+        raise SystemExit("--eval-topk K: K must lie in 1..10, the class count (0: off)")
+    if (args.eval_idx_images is None) != (args.eval_idx_labels is None):
+        raise SystemExit("--eval-idx-images and --eval-idx-labels go together: the held-out set needs both files")
+    for flag, on in (("--eval-topk", args.eval_topk > 0), ("--eval-idx-images / --eval-idx-labels",
+                     args.eval_idx_images is not None), ("--checkpoint-best", args.checkpoint_best is not None)):
+        if on and args.eval <= 0:
+            raise SystemExit(f"{flag} needs --eval N: it acts on the evaluation after every epoch")
+    return args
 
 
 def optimizer_kind(state_dict):
@@ -116,6 +138,13 @@ def check_resume_optimizer(path, want, map_location=None):
     if have is not None and have != want:
         raise SystemExit(f"--resume {path}: the checkpoint holds --optimizer {have} state, this run has "
                          f"--optimizer {want}; resume with --optimizer {have}")
+
+
+def checkpoint_prec1(path, map_location=None):
+    """The prec@1 a --checkpoint-best file was written at (its extra["prec1"]), or None."""
+    blob = torch.load(path, map_location=map_location, weights_only=True)
+    extra = blob.get("extra") if isinstance(blob, dict) else None
+    return float(extra["prec1"]) if extra and "prec1" in extra else None
 
 
 def load_dataset(args, device, rank, as_u8=True):
@@ -166,19 +195,34 @@ def train(gpu, args):
     if args.resume:
         check_resume_optimizer(args.resume, args.optimizer, map_location="cpu")
         first_epoch = load_checkpoint(args.resume, model, opt, map_location=device) + 1
+    best_prec1 = None
+    if args.resume and args.checkpoint_best:
+        best_prec1 = checkpoint_prec1(args.resume, map_location="cpu")     # carry on from the resumed run's best
     data, targets = load_dataset(args, device, rank, as_u8=args.model != "cnn" and not args.fp32_input)
     idx = torch.tensor(shard_indices(len(data), world, rank), device=device)
     nb = (len(idx) + args.batch_size - 1) // args.batch_size
     T, E = [], []
     graphed = static_x = static_y = None
-    frozen = held_x = held_y = None
+    frozen = held_x = held_y = ev = None
+    is_best = False
     if args.eval > 0 and not isinstance(model, (nets.MLP, nets.BinCNN)):
         raise SystemExit("--eval freezes the binarized MLPs (mlp / small / wide) and the cnn, not --model " + args.model)
+
+    # --train-acc: prec@1 of the training batches, counted on the device from each step's output (one launch,
+    # part of a captured step) and read where the loop reads the loss
+    train_meter = []
+
+    def _count(out, yb):
+        if args.train_acc:
+            if not train_meter:
+                train_meter.append(Meter(out.shape[1], k=1, device=device))
+            train_meter[0].update(out.detach(), yb)
+        return out
 
     def _step(xb, yb):
         for p in model.parameters():
             p.grad = None
-        lo = crit(model(xb), yb)
+        lo = crit(_count(model(xb), yb), yb)
         lo.backward()
         opt.step()
         return lo
@@ -213,7 +257,7 @@ def train(gpu, args):
                     exchange.zero_grad()
                 else:
                     opt.zero_grad(set_to_none=True)
-                loss = crit(model(x), y)
+                loss = crit(_count(model(x), y), y)
                 if quirk:
                     opt.param_groups[0]["lr"] *= 0.1
                     graphed = None          # the captured step holds the old lr (Adam's schedule, SGD's argument)
@@ -227,9 +271,13 @@ def train(gpu, args):
                 lv = loss.item()                # syncs, like the reference's loss.item()
                 if batch_idx * len(x) != 0:
                     T.append([batch_idx * len(x), meter.val])
+                acc = ""
+                if train_meter:                 # read and reset with the loss: the batches since the last line
+                    acc = "\tAcc: {:.2f}".format(train_meter[0].result()["prec1"])
+                    train_meter[0].reset()
                 if rank == 0:
                     print("Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f} \t Time: {:.3f}({:.3f})".format(
-                        epoch, batch_idx * len(x), len(data), 100.0 * batch_idx / nb, lv, meter.val, meter.avg),
+                        epoch, batch_idx * len(x), len(data), 100.0 * batch_idx / nb, lv, meter.val, meter.avg) + acc,
                         flush=True)
         torch.cuda.synchronize()
         if rank == 0:
@@ -238,12 +286,34 @@ def train(gpu, args):
         if args.eval > 0 and rank == 0:
             if frozen is None:
                 # held-out samples: a draw of bnn_amd.data the training set (seed 1234) does not use
-                held_x, held_y = synthetic_mnist(args.eval, seed=EVAL_SEED, device=device, as_u8=True)
+                if args.eval_idx_images:
+                    held_x, held_y = load_idx_dataset(args.eval_idx_images, args.eval_idx_labels, device)
+                    held_x, held_y = held_x[:args.eval], held_y[:args.eval]     # N clipped to the file's length
+                else:
+                    held_x, held_y = synthetic_mnist(args.eval, seed=EVAL_SEED, device=device, as_u8=True)
                 frozen = freeze(model)
             else:
                 frozen.refresh()
+            n_eval = len(held_x)
             print("Eval {} : accuracy {:.4f} on {} held-out samples".format(
-                epoch, frozen.accuracy(held_x, held_y, batch=max(1, min(args.eval, 65536))), args.eval), flush=True)
+                epoch, frozen.accuracy(held_x, held_y, batch=max(1, min(n_eval, 65536))), n_eval), flush=True)
+            if args.eval_topk > 0 or args.checkpoint_best:
+                ev = frozen.evaluate(held_x, held_y, k=max(1, args.eval_topk), batch=max(1, min(n_eval, 65536)))
+                if args.eval_topk > 0:
+                    print("Eval {} : loss {:.6f} prec@1 {:.2f} prec@{} {:.2f} on {} samples".format(
+                        epoch, ev["loss"], ev["prec1"], args.eval_topk, ev["preck"], ev["n"]), flush=True)
+                is_best = args.checkpoint_best is not None and (best_prec1 is None or ev["prec1"] > best_prec1)
+        if args.checkpoint_best:
+            # rank 0 evaluated; every rank joins save_checkpoint (it writes from rank 0 and barriers)
+            if world > 1:
+                flag = torch.tensor([int(is_best)], device=device)
+                dist.broadcast(flag, 0)
+                is_best = bool(flag.item())
+            if is_best:
+                if rank == 0:
+                    best_prec1 = ev["prec1"]
+                save_checkpoint(args.checkpoint_best, model, opt, epoch,
+                                extra={"prec1": best_prec1} if rank == 0 else None)
         if args.checkpoint:
             save_checkpoint(args.checkpoint, model, opt, epoch)
     if rank == 0:

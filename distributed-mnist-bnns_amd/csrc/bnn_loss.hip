@@ -17,25 +17,10 @@
 // kernel (up to 16384 rows: one 1024-thread workgroup does both); every order is fixed
 // (deterministic); lse is kept per row for the backward, whose loss gradient go is read on the
 // device (no host synchronisation: the step stays capturable in a HIP graph).
-#include "bnn_common.h"
+#include "bnn_rows.h"
 
 namespace bnn {
 namespace {
-
-constexpr int CE_T = 256;
-
-template <int C>
-__device__ __forceinline__ float row_lse(const float* __restrict__ pr, float (&v)[C]) {
-#pragma unroll
-  for (int j = 0; j < C; ++j) v[j] = pr[j];
-  float mx = v[0];
-#pragma unroll
-  for (int j = 1; j < C; ++j) mx = fmaxf(mx, v[j]);
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < C; ++j) s += expf(v[j] - mx);
-  return mx + logf(s);
-}
 
 // one row's loss term and count (0, 0 for an ignored row)
 template <int C>
@@ -122,9 +107,6 @@ __global__ __launch_bounds__(CE_T) void ce_fold_k(const double* __restrict__ par
 
 // small batches (M <= CE_ONE_MAX): the whole forward in ONE workgroup of 1024 threads, thread t
 // taking rows t, t + 1024, ... in order, then a fixed tree -- no second (fold) launch
-constexpr int CE_T1 = 1024;
-constexpr int64_t CE_ONE_MAX = 16384;
-
 template <int C>
 __global__ __launch_bounds__(CE_T1) void ce_fwd1_k(const float* __restrict__ p, const int64_t* __restrict__ y,
                                                   int64_t M, int64_t ignore, float* __restrict__ lse,
@@ -251,31 +233,13 @@ __device__ __forceinline__ double hinge_row(const float* __restrict__ x, const i
   return s;
 }
 
-// a workgroup's sum in thread order: a fixed shuffle tree per wave, then the waves in order (thread 0
-// returns the sum)
-template <int T>
-__device__ __forceinline__ double hinge_block_sum(double l) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) l += __shfl_xor(l, o, 64);
-  __shared__ double ws[T / 64];
-  if ((t & 63) == 0) ws[t >> 6] = l;
-  __syncthreads();
-  double s = 0.0;
-  if (t == 0) {
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) s += ws[w];
-  }
-  return s;
-}
-
 template <int C, bool DENSE>
 __global__ __launch_bounds__(CE_T) void hinge_fwd_k(const float* __restrict__ x, const int64_t* __restrict__ y,
                                                    const float* __restrict__ tg, int64_t M, float margin,
                                                    int squared, double* __restrict__ part) {
   const int64_t i = (int64_t)blockIdx.x * CE_T + threadIdx.x;
   const double l = i < M ? hinge_row<C, DENSE>(x, y, tg, i, margin, squared) : 0.0;
-  const double s = hinge_block_sum<CE_T>(l);
+  const double s = block_sum_in_order<CE_T>(l);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -284,7 +248,7 @@ __global__ __launch_bounds__(CE_T) void hinge_fold_k(const double* __restrict__ 
   // one workgroup: thread t sums blocks t, t + 256, ... in order, then the fixed tree over threads
   double s = 0.0;
   for (int64_t b = threadIdx.x; b < nb; b += CE_T) s += part[b];
-  s = hinge_block_sum<CE_T>(s);
+  s = block_sum_in_order<CE_T>(s);
   if (threadIdx.x == 0) loss[0] = (float)(s / count);
 }
 
@@ -308,7 +272,7 @@ __global__ __launch_bounds__(CE_T1) void hinge_fwd1_k(const float* __restrict__ 
     for (int u = 0; u < U; ++u)
       if (i0 + (int64_t)u * CE_T1 < M) l += a[u];
   }
-  const double s = hinge_block_sum<CE_T1>(l);
+  const double s = block_sum_in_order<CE_T1>(l);
   if (t == 0) loss[0] = (float)(s / count);
 }
 
@@ -335,16 +299,6 @@ __global__ __launch_bounds__(CE_T) void hinge_bwd_k(const float* __restrict__ x,
 }  // namespace bnn
 
 using namespace bnn;
-
-#define BNN_CE_SWITCH(C, ...)                        \
-  switch (C) {                                       \
-    case 10: { constexpr int CV = 10; __VA_ARGS__; } break; \
-    case 2: { constexpr int CV = 2; __VA_ARGS__; } break;   \
-    case 16: { constexpr int CV = 16; __VA_ARGS__; } break; \
-    case 32: { constexpr int CV = 32; __VA_ARGS__; } break; \
-    case 64: { constexpr int CV = 64; __VA_ARGS__; } break; \
-    default: break;                                  \
-  }
 
 BNN_API int bnn_cross_entropy_ok(int64_t C) { return C == 2 || C == 10 || C == 16 || C == 32 || C == 64; }
 

@@ -849,6 +849,35 @@ int bnn_hinge_fwd(const float* x, const int64_t* y, const float* t, int64_t M, i
 int bnn_hinge_bwd(const float* x, const int64_t* y, const float* t, int64_t M, int64_t C, float margin,
                   int32_t squared, const float* go, float* dx, bnn_stream_t stream);
 
+/* ---------------------------------------------------------------- evaluation metrics
+ * replaces: utils.py:142-155 accuracy(output, target, topk), and the criterion of a test loop.
+ * z [M][C] fp32, contiguous (C as bnn_cross_entropy_ok): logits or log-probabilities -- nothing below
+ * changes when a row is shifted.  y [M] int64 labels.  loss_sum[1] (double) and counts[3 + C*C] (int64)
+ * are ACCUMULATORS: the call adds to them, so a data set is evaluated in batches without the host; the
+ * caller zeroes them first.
+ *   Order of values: a ranks above b when a > b; a NaN ranks above every non-NaN; equal values, and two
+ *   NaNs, rank by the lower column index first (torch's argmax / topk treatment of NaN, with the tie rule
+ *   made explicit).  rank r = the number of columns that rank above column y[i].
+ *   pred[i] (int32, nullable)  = the top-ranked column, written for every row
+ *   a row with y[i] == ignore_index adds nothing anywhere; every other row is counted:
+ *   loss_sum[0]               += lse(z_i) - z_i[y_i]: bnn_cross_entropy_fwd's row term, bit for bit (the
+ *                                same fp32 arithmetic; a label outside [0, C) makes it NaN)
+ *   counts[0]                 += 1
+ *   counts[1]                 += r == 0       }
+ *   counts[2]                 += r < k        }  only where y[i] is in [0, C)
+ *   counts[3 + y[i]*C + pred] += 1            }  (the confusion matrix, rows = label)
+ * The terms are summed in double in an order fixed by M alone, and the call's sum is added to
+ * loss_sum[0] by one thread (no floating-point atomics: a repeated call sequence gives the same bits);
+ * the integer counts are exact in any order.  Launches as bnn_cross_entropy_fwd: one up to M = 16384,
+ * two beyond.  work: bnn_eval_metrics_workspace(M) bytes.  BNN_EINVAL (nothing launched) for a null
+ * z / y / loss_sum / counts / work with M > 0, M < 0, an unsupported C, k < 1 or k > C, a short
+ * workspace; M == 0 returns 0 and touches nothing. */
+int bnn_eval_metrics_ok(int64_t C);
+int64_t bnn_eval_metrics_workspace(int64_t M);
+int bnn_eval_metrics(const float* z, const int64_t* y, int64_t M, int64_t C, int32_t k, int64_t ignore_index,
+                     double* loss_sum, int64_t* counts, int32_t* pred /* nullable, [M] */, void* work,
+                     int64_t work_bytes, bnn_stream_t stream);
+
 /* ---------------------------------------------------------------- (3) STE backward helpers
  * Hardtanh backward: g_out = g_in * (-1 < x < 1) (strict), as nn.Hardtanh (mnist-dist2.py:51). */
 int bnn_hardtanh_bwd(const float* x, const float* g, float* out, int64_t n, bnn_stream_t stream);
