@@ -2,7 +2,7 @@
 
 Layers: ``functional`` (libbnn.so ops + autograd Functions), ``nn`` (BinarizeLinear /
 BinarizeConv2d modules with the reference's ``weight.org`` protocol), ``parallel`` (RCCL
-bucketed gradient exchange), ``optim`` (fused latent Adam / SGD + clamp), ``nets`` / ``trainer``
+bucketed gradient exchange), ``optim`` (fused latent Adam / SGD + clamp, Bop), ``nets`` / ``trainer``
 (the reference's training loop restated), ``data`` (synthetic MNIST + sampler), ``inference``
 (``freeze(model) -> FrozenMLP / FrozenCNN``: a trained network packed once and run without the float
 model), ``metrics`` (``accuracy`` / ``Meter``: held-out loss, precision@k and confusion counts on the device).

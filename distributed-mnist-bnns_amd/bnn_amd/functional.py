@@ -25,7 +25,7 @@ __all__ = [
     "KernelTimer", "timing", "sign", "sign_pack", "sign_pack_bits", "quant_rows", "quant_cols_t", "gemm_i8", "gemm_xnor",
     "quant6_rows", "quant6_cols_t", "gemm_fp6", "set_digit_gemm",
     "binary_linear", "binary_conv2d", "hardtanh_backward", "adam_clamp_", "adam_clamp_pack_", "packed_weight",
-    "sgd_clamp_", "sgd_clamp_multi_", "sgd_clamp_pack_",
+    "sgd_clamp_", "sgd_clamp_multi_", "sgd_clamp_pack_", "bop_", "bop_pack_",
     "invalidate_packed", "batch_norm_hardtanh",
     "bn_hardtanh_binary_linear", "batch_norm2d_hardtanh_pool", "dropout_batch_norm_hardtanh", "dropout_mask",
     "BinaryLinearFunction", "BinaryConv2dFunction",
@@ -457,6 +457,38 @@ def sgd_clamp_pack_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=
                qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
     _bump(p)
     ent["key"] = _pack_key(p)           # the operands just written match the bumped version
+    return True
+
+
+def _check_flips(flips, p):
+    if flips is not None and (flips.dtype != torch.int64 or flips.numel() < 1 or flips.device != p.device):
+        raise ValueError("flips: an int64 tensor on the weight's device (its first element is the counter)")
+
+
+def bop_pack_(w, grad, m, gamma, threshold, grad_scale=1.0, flips=None):
+    """bnn_bop on a 2-D binarized weight that also rewrites its cached packed operands (see
+    packed_weight), as adam_clamp_pack_ does for Adam.  Returns False (nothing done) when ``w`` has no
+    valid cache."""
+    if _ADAM_TILE256[0] is not None:
+        L.call("bnn_adam_pack_set_tile256", int(_ADAM_TILE256[0] != "0"))
+        _ADAM_TILE256[0] = None
+    ent = getattr(w, "_bnn_pack", None)
+    if ent is None or ent["key"] != _pack_key(w) or w.dim() != 2:
+        return False
+    _check(w, grad, m)
+    _check_flips(flips, w)
+    for t in (w, grad, m):
+        if not t.is_contiguous():
+            raise ValueError("bop_pack_: tensors must be contiguous")
+    N, K = w.shape
+    q, qt = ent["q"], ent["qt"]
+    nbytes = 20 * N * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
+    with _timed("sign_pack_tile_k<bop>", 0, nbytes):
+        L.call("bnn_bop_pack", w, grad, m, N, K, float(gamma), float(threshold), float(grad_scale), flips,
+               1 if ent["fmt"] == "fp4" else 0, q, q.shape[1] if q is not None else 0, qt,
+               qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
+    _bump(w)
+    ent["key"] = _pack_key(w)           # the operands just written match the bumped version
     return True
 
 
@@ -1847,6 +1879,22 @@ def sgd_clamp_multi_(items, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, n
         with _timed("sgd_clamp_multi_k", 0, nbytes):
             L.call("bnn_sgd_clamp_multi", len(chunk), *vp, float(lr), float(momentum), _sgd_omd(dampening),
                    float(weight_decay), int(bool(nesterov)), float(grad_scale), L.stream())
+
+
+def bop_(w, grad, m, gamma, threshold, grad_scale=1.0, flips=None):
+    """In-place Bop (Helwegen et al. 2019; bop_elem): ``m`` <- the gradient's moving average with rate
+    ``gamma``, ``w`` <- its sign as exactly +-1, flipped where the average exceeds ``threshold`` against it.
+    ``flips`` (an int64 device tensor, optional) gets the number of flipped elements added to its first
+    element."""
+    _check(w, grad, m)
+    _check_flips(flips, w)
+    invalidate_packed(w)        # a raw in-place write: cached packed operands would go stale
+    for t in (w, grad, m):
+        if not t.is_contiguous():
+            raise ValueError("bop_: tensors must be contiguous")
+    _bump(w)
+    with _timed("bop_k", 0, 20 * w.numel()):
+        L.call("bnn_bop", w, grad, m, w.numel(), float(gamma), float(threshold), float(grad_scale), flips, L.stream())
 
 
 # ----------------------------------------------------------------------------- BatchNorm1d (+ Hardtanh)

@@ -234,3 +234,9 @@ def binary_params(model):
             if m.bias is not None:
                 out.append(m.bias)
     return out
+
+
+def binary_weights(model):
+    """The weights, without the biases, of the BinarizeLinear/BinarizeConv2d modules: the parameters a
+    forward uses only through their sign, which ``optim.LatentBop`` keeps at +-1 (``bop_params``)."""
+    return [m.weight for m in model.modules() if isinstance(m, (BinarizeLinear, BinarizeConv2d))]

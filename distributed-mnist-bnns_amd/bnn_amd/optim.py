@@ -24,6 +24,10 @@ per-launch values), and the counter is advanced on the device after the last upd
 scripts (mnist.py, mnist-dist.py, mnist-mixed.py) and DDP demos (mnist-distributed-BNNS2.py): momentum,
 dampening, weight decay and Nesterov as torch computes them, the clamp, and the re-pack of a binarized
 layer's weight in one pass (bnn_sgd_clamp_pack).
+
+``LatentBop`` is the binary optimizer of Helwegen et al. (NeurIPS 2019; larq's Bop) for the binarized weights
+-- no latent weight, a moving average of the gradient, a flip where it exceeds a threshold against the
+weight -- fused with the same re-pack (bnn_bop_pack), and ``LatentAdam`` for every other parameter.
 """
 import os
 
@@ -113,6 +117,11 @@ class LatentAdam(torch.optim.Optimizer):
             self._sched.pop(gi, None)
             self._schedule(gi, group, steps.pop() + 1, group["params"][0].device, build=True)
 
+    def _own_update(self, p, group):
+        """A subclass's own update of ``p`` (LatentBop); True: done, Adam skips it.  Such a parameter still
+        keeps a ``"step"`` in its state, for the uniform-step logic above and build_schedules."""
+        return False
+
     def schedule_limit(self):
         """Device counter value at which the first device table runs out (None: no table)."""
         lens = [ent[0].shape[0] for ent in self._sched.values()]
@@ -146,6 +155,8 @@ class LatentAdam(torch.optim.Optimizer):
                 if sched is None and capturing:
                     raise RuntimeError("LatentAdam: no device schedule for this lr (build_schedules before capturing)")
             for p in live:
+                if self._own_update(p, group):
+                    continue
                 st = self.state[p]
                 if not st:
                     st["step"] = 0
@@ -268,3 +279,103 @@ class LatentSGD(torch.optim.Optimizer):
         if ds is not None:
             ds.advance()
         return loss
+
+
+class LatentBop(LatentAdam):
+    """Bop (Helwegen et al., "Latent Weights Do Not Exist: Rethinking Binarized Neural Network
+    Optimization", NeurIPS 2019; larq's Bop) for the parameters in ``bop_params`` -- the binarized layers'
+    weights, ``nets.binary_weights(model)`` -- and ``LatentAdam`` (lr, betas, eps, ``clamp_params``, the
+    device-step table) through the same launches for every other parameter.
+
+    A Bop weight is +-1, not a latent number: its state is ``bop_m``, the moving average of its gradient
+    with rate ``gamma``, and it flips where that average exceeds ``threshold`` and has the weight's sign.
+    The first step binarizes whatever the Parameter holds.  A 2-D weight with live packed operands gets
+    them rewritten by the same pass (bnn_bop_pack); anything else -- the conv weights -- takes the flat
+    pass (bnn_bop).  ``gamma`` and ``threshold`` are per param group and travel in the ``state_dict``; the
+    defaults are larq's, starting points rather than values tuned for these nets.
+
+    Every pass also counts the weights it flipped into the parameter's ``flips`` state, on the device;
+    ``flip_counts`` reads them: the flip ratio flips / (numel * steps) is what gamma and threshold are
+    tuned by.  Nothing in the Bop update depends on the step count, so a captured step replays it as it
+    is; a parameter's first step allocates its state and cannot be captured.
+    """
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, gamma=1e-4, threshold=1e-8, bop_params=(),
+                 clamp_params=(), grad_scale=1.0, device_step=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, clamp_params=clamp_params, grad_scale=grad_scale,
+                         device_step=device_step)
+        self._bop = {id(p) for p in bop_params}
+        for group in self.param_groups:
+            group.setdefault("gamma", gamma)
+            group.setdefault("threshold", threshold)
+            self._check_hyper(group)
+        self.defaults.update(gamma=gamma, threshold=threshold)
+
+    @staticmethod
+    def _check_hyper(group):
+        gamma, threshold = group["gamma"], group["threshold"]
+        if not 0.0 < gamma <= 1.0:
+            raise ValueError(f"Invalid gamma value: {gamma} (Bop's averaging rate lies in (0, 1])")
+        if not threshold >= 0.0:
+            raise ValueError(f"Invalid threshold value: {threshold} (Bop's flip threshold is not negative)")
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)        # gamma / threshold: the defaults unless given
+        if "gamma" in self.defaults:                # (the base constructor adds groups before they exist)
+            self._check_hyper(self.param_groups[-1])
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            self._check_hyper(group)
+        # torch casts every state tensor to the parameter's dtype; the counters are int64 and exact.  Saved
+        # parameter ids are positions in the groups' order, as state_dict() numbers them.
+        saved = state_dict["state"]
+        ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        ps = [p for g in self.param_groups for p in g["params"]]
+        for i, p in zip(ids, ps):
+            if i in saved and "flips" in saved[i]:
+                self.state[p]["flips"] = saved[i]["flips"].to(device=p.device, dtype=torch.int64).clone()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            for group in self.param_groups:
+                for p in group["params"]:
+                    if id(p) in self._bop and p.grad is not None and "bop_m" not in self.state.get(p, {}):
+                        raise RuntimeError("LatentBop: a captured step cannot be a parameter's first (it allocates "
+                                           "the gradient average and the flip counter); run one eager step before "
+                                           "capturing")
+        return super().step(closure)
+
+    def _own_update(self, p, group):
+        if id(p) not in self._bop:
+            return False
+        st = self.state[p]
+        if "bop_m" not in st:
+            st["step"] = 0
+            st["bop_m"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["flips"] = torch.zeros((1,), dtype=torch.int64, device=p.device)
+            st["flips_since"] = 0           # the step count at the last flip_counts(reset=True)
+        st["step"] += 1
+        g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+        args = (g, st["bop_m"], group["gamma"], group["threshold"], self.grad_scale, st["flips"])
+        if not BF.bop_pack_(p, *args):
+            BF.bop_(p, *args)
+        return True
+
+    def flip_counts(self, reset=False):
+        """{parameter: (flips, numel, steps)} of every Bop parameter that has stepped: the weights flipped
+        over its ``steps`` steps since the last reset (flip ratio = flips / (numel * steps)).  One host read
+        for all of them together."""
+        items = [(p, self.state[p]) for group in self.param_groups for p in group["params"]
+                 if "flips" in self.state.get(p, {})]
+        if not items:
+            return {}
+        counts = torch.cat([st["flips"] for _, st in items]).tolist()
+        out = {p: (int(c), p.numel(), st["step"] - st.get("flips_since", 0)) for (p, st), c in zip(items, counts)}
+        if reset:
+            for _, st in items:
+                st["flips"].zero_()
+                st["flips_since"] = st["step"]
+        return out

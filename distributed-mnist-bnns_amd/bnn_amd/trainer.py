@@ -7,7 +7,8 @@
 
 Flags keep the reference's names (-n/--nodes, -g/--gpus, -nr/--nr, --epochs, --seed, --lr,
 --log-interval; mnist-dist2.py:23-37).  Semantics kept: batch 64 by default (:88), Adam(lr) on
-the latent weights (:91; --optimizer sgd: the SGD of the ConvNet scripts, fused as LatentSGD),
+the latent weights (:91; --optimizer sgd: the SGD of the ConvNet scripts, fused as LatentSGD; --optimizer bop:
+Bop on the binarized weights, Adam on the rest, fused as LatentBop, with a per-epoch flip-ratio line),
 DistributedSampler order with seed 0 and no set_epoch (:100-108),
 1-based epochs with the per-batch ``lr *= 0.1`` whenever ``epoch % 40 == 0`` (:126-127), the
 .org restore -> step -> clamp protocol (:131-137, here fused into LatentAdam), AverageMeter batch
@@ -36,7 +37,7 @@ from .graph import GraphedStep
 from .data import load_idx_dataset, shard_indices, synthetic_mnist
 from .inference import freeze
 from .metrics import Meter
-from .optim import LatentAdam, LatentSGD
+from .optim import LatentAdam, LatentBop, LatentSGD
 from .parallel import GradExchange
 
 EVAL_SEED = 4321     # --eval's held-out synthetic samples (the training set is seed 1234)
@@ -84,13 +85,18 @@ def parse(argv=None):
     ap.add_argument("--loss", default="ce", choices=("ce", "hinge", "sqhinge"), help="the criterion: ce = "
                     "CrossEntropyLoss on the LogSoftmax output (mnist-dist2.py:118-137); hinge / sqhinge = the mean "
                     "(squared) hinge of models/binarized_modules.py on the logits, one-vs-all +-1 targets")
-    ap.add_argument("--optimizer", default="adam", choices=("adam", "sgd"), help="adam = LatentAdam "
+    ap.add_argument("--optimizer", default="adam", choices=("adam", "sgd", "bop"), help="adam = LatentAdam "
                     "(mnist-dist2.py:91); sgd = LatentSGD, torch.optim.SGD of the reference's ConvNet scripts (mnist.py, mnist-dist.py, "
-                    "mnist-mixed.py, mnist-distributed-BNNS2.py), with the flags below")
+                    "mnist-mixed.py, mnist-distributed-BNNS2.py), with the flags below; bop = LatentBop, the binary optimizer "
+                    "(Helwegen et al. 2019) on the binarized layers' weights and Adam(--lr) on every other parameter")
     ap.add_argument("--momentum", type=float, default=0.0, help="--optimizer sgd")
     ap.add_argument("--dampening", type=float, default=0.0, help="--optimizer sgd")
     ap.add_argument("--weight-decay", type=float, default=0.0, help="--optimizer sgd")
     ap.add_argument("--nesterov", action="store_true", help="--optimizer sgd")
+    ap.add_argument("--bop-gamma", type=float, default=1e-4, help="--optimizer bop: the rate of the gradient's moving "
+                    "average, in (0, 1]")
+    ap.add_argument("--bop-threshold", type=float, default=1e-8, help="--optimizer bop: a weight flips when the average "
+                    "exceeds this against it; not negative")
     ap.add_argument("--csv-prefix", default=None, help="write <prefix>_BATCH_TIME.csv / _EPOCH_TIME.csv")
     ap.add_argument("--checkpoint", default=None, help="write a latent-weight checkpoint here after every epoch")
     ap.add_argument("--resume", default=None, help="resume from a checkpoint written by --checkpoint")
@@ -121,8 +127,10 @@ def parse(argv=None):
 
 
 def optimizer_kind(state_dict):
-    """"adam" / "sgd": which optimizer wrote this state_dict, told from its param_groups."""
+    """"adam" / "sgd" / "bop": which optimizer wrote this state_dict, told from its param_groups."""
     groups = state_dict.get("param_groups") or [{}]
+    if "gamma" in groups[0]:        # before betas: LatentBop's groups carry Adam's too
+        return "bop"
     if "betas" in groups[0]:
         return "adam"
     if "momentum" in groups[0]:
@@ -185,6 +193,11 @@ def train(gpu, args):
         opt = LatentSGD(model.parameters(), lr=args.lr, momentum=args.momentum, dampening=args.dampening,
                         weight_decay=args.weight_decay, nesterov=args.nesterov,
                         clamp_params=nets.binary_params(model), device_step=dstep)
+    elif args.optimizer == "bop":
+        opt = LatentBop(model.parameters(), lr=args.lr, gamma=args.bop_gamma, threshold=args.bop_threshold,
+                        bop_params=nets.binary_weights(model), clamp_params=nets.binary_params(model),
+                        device_step=dstep)
+        bop_names = {id(p): n for n, p in model.named_parameters()}
     else:
         opt = LatentAdam(model.parameters(), lr=args.lr, clamp_params=nets.binary_params(model), device_step=dstep)
     if args.loss == "ce":
@@ -283,6 +296,13 @@ def train(gpu, args):
         if rank == 0:
             print("Training ", epoch, " : " + str(datetime.now() - start), flush=True)
         E.append([datetime.now() - start])
+        if args.optimizer == "bop":
+            # each binarized layer's flip ratio over the epoch, flips / (numel x steps): one host read
+            counts = opt.flip_counts(reset=True)
+            if rank == 0:
+                print("Flips {} : ".format(epoch) + " ".join(
+                    "{} {:.3e}".format(bop_names[id(p)], f / max(1, n * s)) for p, (f, n, s) in counts.items()),
+                    flush=True)
         if args.eval > 0 and rank == 0:
             if frozen is None:
                 # held-out samples: a draw of bnn_amd.data the training set (seed 1234) does not use

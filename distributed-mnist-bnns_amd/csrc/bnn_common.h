@@ -308,6 +308,47 @@ inline bool sgd_hyper_ok(float lr, float mu, float omd, float wd, int nesterov) 
   return true;
 }
 
+// Bop, the binary optimizer of Helwegen et al. (NeurIPS 2019; larq's Bop): no latent weight.  The weight is
+// +-1, the only state is m, an exponential moving average of the gradient, and a weight flips when m is
+// larger than the threshold and has the weight's sign (the descent direction then points across zero).
+// Every operation is one fp32 rounding:
+//   gi = g * gscale;  m' = m + gamma * (gi - m);  s = w < 0 ? -1 : +1;  w' = s * m' > thr ? -s : s
+// Any w is accepted -- 0, -0 and NaN count as +1 -- and w' is exactly +-1, so a parameter's first step
+// binarizes its initial value.  The comparison is strict: a tie or a NaN average does not flip.  m starts at
+// zero and nothing depends on a step count.  Shared by bnn_bop and the fused bnn_bop_pack so both produce
+// bit-identical weights and averages.  nflip counts the flips (w' != s) of the calling thread.
+struct BopArgs {
+  const float* g;
+  float* m;
+  float gamma, thr, gscale;
+  int64_t* flips;    // nullable: the launch adds its number of flipped elements to flips[0]
+};
+
+__device__ __forceinline__ float bop_elem(float w, float g, float& m, const BopArgs& a, int& nflip) {
+  // no mul+add contraction: every kernel that inlines this rounds identically
+#pragma clang fp contract(off)
+  const float gi = g * a.gscale;
+  m = m + a.gamma * (gi - m);
+  const float s = (w < 0.f) ? -1.f : 1.f;
+  const bool flip = s * m > a.thr;
+  nflip += flip;
+  return flip ? -s : s;
+}
+
+// A thread's flip count folded over its wave; one atomic per wave, none when the wave flipped nothing.  The
+// sum of integers does not depend on the order of the adds, so the total is deterministic.  Every lane of
+// the wave calls it (flips is uniform).
+__device__ __forceinline__ void bop_flush(int n, int64_t* flips) {
+  if (flips == nullptr) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if ((threadIdx.x & 63) == 0 && n != 0)
+    atomicAdd(reinterpret_cast<unsigned long long*>(flips), (unsigned long long)n);
+}
+
+// Argument checks shared by the two bnn_bop* entries (host): gamma in (0, 1], threshold >= 0 and not NaN
+inline bool bop_hyper_ok(float gamma, float thr) { return gamma > 0.f && gamma <= 1.f && thr >= 0.f; }
+
 // Fused nn.Dropout(p) in front of a BatchNorm (mnist-dist2.py:69-70: fc3 -> drop -> bn3).  The
 // keep mask is a counter-based hash of (seed, element index), so forward statistics, forward
 // apply and both backward passes regenerate the same mask without storing it; kept elements are

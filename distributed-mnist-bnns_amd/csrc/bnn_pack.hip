@@ -61,20 +61,29 @@ struct ColAffine {
 // row's offset in the streams, k = the column.
 //   U::Args                  the kernel argument (gradient, state streams, hyper-parameters)
 //   U::resolve(a)            the arguments of this launch (device-step table lookups)
-//   U::run4(prow, off, k, a) updates the weights prow[k .. k+3] and their state in place (16-B aligned
-//                            float4 runs),
-//   U::run1(prow, off, k, a) or one element; both return the new weight(s)
+//   U::run4(prow, off, k, a, acc) updates the weights prow[k .. k+3] and their state in place (16-B
+//                            aligned float4 runs),
+//   U::run1(prow, off, k, a, acc) or one element; both return the new weight(s)
+//   U::Acc                   what a thread accumulates over all of its runs (Bop: its flip count), and
+//   U::finish(acc, a)        what becomes of it, called once by every thread when its last run is done;
+//                            NoAcc = nothing: an empty struct and an empty call, which compile to no code
 //   U::null(a), U::vec(a)    host: a needed pointer is null / every stream is 16-B aligned
 // NoUpdate marks the kernels that only pack.
-struct NoUpdate {
+struct NoAcc {
+  struct Acc {};
+  template <class A>
+  static __device__ __forceinline__ void finish(const Acc&, const A&) {}
+};
+
+struct NoUpdate : NoAcc {
   struct Args {};
 };
 
 // Adam + clamp (adam_elem): g, m, v read; m, v written -- 7 fp32 streams with p
-struct AdamUpdate {
+struct AdamUpdate : NoAcc {
   using Args = AdamArgs;
   static __device__ __forceinline__ Args resolve(const Args& a) { return adam_resolve(a); }
-  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a) {
+  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a, Acc&) {
     const float4 pv = *reinterpret_cast<const float4*>(prow + k);
     const float4 gv = *reinterpret_cast<const float4*>(a.g + off + k);
     float4 mv = *reinterpret_cast<const float4*>(a.m + off + k);
@@ -89,7 +98,7 @@ struct AdamUpdate {
     *reinterpret_cast<float4*>(a.v + off + k) = vv;
     return np;
   }
-  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a) {
+  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a, Acc&) {
     float mm = a.m[off + k], vv = a.v[off + k];
     const float np = adam_elem(prow[k], a.g[off + k], mm, vv, a);
     prow[k] = np;
@@ -105,10 +114,10 @@ struct AdamUpdate {
 // streams with p), 1 written only (a parameter's first step: 4 streams), 2 read and written (5 streams).
 // A template parameter, not a branch on a.mu / a.first: the loads of an unrolled run stay together.
 template <int BUF>
-struct SgdUpdate {
+struct SgdUpdate : NoAcc {
   using Args = SgdArgs;
   static __device__ __forceinline__ Args resolve(const Args& a) { return a; }
-  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a) {
+  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a, Acc&) {
     const float4 pv = *reinterpret_cast<const float4*>(prow + k);
     const float4 gv = *reinterpret_cast<const float4*>(a.g + off + k);
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -122,7 +131,7 @@ struct SgdUpdate {
     if constexpr (BUF != 0) *reinterpret_cast<float4*>(a.buf + off + k) = bv;
     return np;
   }
-  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a) {
+  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a, Acc&) {
     float bb = 0.f;
     if constexpr (BUF == 2) bb = a.buf[off + k];
     const float np = sgd_elem(prow[k], a.g[off + k], bb, a);
@@ -134,21 +143,54 @@ struct SgdUpdate {
   static bool vec(const Args& a) { return aligned16(a.g) && (BUF == 0 || aligned16(a.buf)); }
 };
 
+// Bop (bop_elem): g, m read; m written -- 5 fp32 streams with w.  Acc = the thread's flip count, added to
+// a.flips once per wave by finish (bop_flush).
+struct BopUpdate {
+  using Args = BopArgs;
+  struct Acc {
+    int n = 0;
+  };
+  static __device__ __forceinline__ Args resolve(const Args& a) { return a; }
+  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a, Acc& acc) {
+    const float4 pv = *reinterpret_cast<const float4*>(prow + k);
+    const float4 gv = *reinterpret_cast<const float4*>(a.g + off + k);
+    float4 mv = *reinterpret_cast<const float4*>(a.m + off + k);
+    float4 np;
+    np.x = bop_elem(pv.x, gv.x, mv.x, a, acc.n);
+    np.y = bop_elem(pv.y, gv.y, mv.y, a, acc.n);
+    np.z = bop_elem(pv.z, gv.z, mv.z, a, acc.n);
+    np.w = bop_elem(pv.w, gv.w, mv.w, a, acc.n);
+    *reinterpret_cast<float4*>(prow + k) = np;
+    *reinterpret_cast<float4*>(a.m + off + k) = mv;
+    return np;
+  }
+  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a, Acc& acc) {
+    float mm = a.m[off + k];
+    const float np = bop_elem(prow[k], a.g[off + k], mm, a, acc.n);
+    prow[k] = np;
+    a.m[off + k] = mm;
+    return np;
+  }
+  static __device__ __forceinline__ void finish(const Acc& acc, const Args& a) { bop_flush(acc.n, a.flips); }
+  static bool null(const Args& a) { return !a.g || !a.m; }
+  static bool vec(const Args& a) { return aligned16(a.g) && aligned16(a.m); }
+};
+
 // One 4-element run of a latent-weight row updated in place (the update mode of sign_pack_tile_k: the
 // fused latent update of mnist-dist2.py:131-137 that also writes the next forward's ternary operands).
 // p and the policy's streams share the row-major [M][K] layout; prow = the weight's row, off = the row's
 // offset, columns k..k+3; sg = the new signs (0 beyond K).
 template <class U>
 __device__ __forceinline__ void update4(float* __restrict__ prow, int64_t off, int64_t k, int64_t K, bool vec,
-                                        const typename U::Args& a, int (&sg)[4]) {
+                                        const typename U::Args& a, int (&sg)[4], typename U::Acc& acc) {
   if (vec && k + 4 <= K) {
-    const float4 np = U::run4(prow, off, k, a);
+    const float4 np = U::run4(prow, off, k, a, acc);
     sg[0] = tsign(np.x), sg[1] = tsign(np.y), sg[2] = tsign(np.z), sg[3] = tsign(np.w);
   } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       sg[j] = 0;
-      if (k + j < K) sg[j] = tsign(U::run1(prow, off, k + j, a));
+      if (k + j < K) sg[j] = tsign(U::run1(prow, off, k + j, a, acc));
     }
   }
 }
@@ -219,6 +261,7 @@ __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict_
       }
     }
   }
+  typename U::Acc acc{};
   for (int it = 0; it < rtiles; ++it) {
   const int64_t ty = (int64_t)blockIdx.y * rtiles + it;
   if (rtiles > 1 && ty >= ntiles_y) break;   // uniform per workgroup
@@ -237,7 +280,7 @@ __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict_
       const int rr = ar + 16 * pr;
       const int64_t mr = m0 + rr;
       int sg[4] = {0, 0, 0, 0};
-      if (mr < M) update4<U>(const_cast<float*>(x) + mr * ldx, mr * ldx, k0 + ac, K, vec, a, sg);
+      if (mr < M) update4<U>(const_cast<float*>(x) + mr * ldx, mr * ldx, k0 + ac, K, vec, a, sg, acc);
 #pragma unroll
       for (int j = 0; j < 4; ++j) tile[rr][ac + j] = sg[j];
     }
@@ -346,6 +389,7 @@ __global__ __launch_bounds__(256) void sign_pack_tile_k(const float* __restrict_
     }
   }
   }
+  U::finish(acc, ad);     // every thread gets here: the loop's only exit is uniform
 }
 
 // The benched form of bnn_bn_apply_pack (FP4 rows + FP4 transpose, C % 256 == 0) on 256 x 256
@@ -486,17 +530,19 @@ __global__ __launch_bounds__(256) void adam_pack_fp4_k(float* __restrict__ p, ty
   const int64_t k0 = (int64_t)blockIdx.x * AP_T, m0 = (int64_t)blockIdx.y * AP_T;
   const int64_t cb = k0 + 4 * lane;
   uint16_t* img16 = reinterpret_cast<uint16_t*>(img);
+  typename U::Acc acc{};
 #pragma unroll ADAMPK_UNROLL
   for (int i = 0; i < AP_T / 4; ++i) {
     const int r = wave + 4 * i;
     const int64_t off = (m0 + r) * K + cb;            // N % 256 == 0: every row is in range
-    const float4 np = U::run4(p + off, off, 0, a);
+    const float4 np = U::run4(p + off, off, 0, a, acc);
     const uint32_t code = fp4_code(tsign(np.x)) | (fp4_code(tsign(np.y)) << 4) | (fp4_code(tsign(np.z)) << 8) |
                           (fp4_code(tsign(np.w)) << 12);
     *reinterpret_cast<uint16_t*>(q + (m0 + r) * ldq + k0 / 2 + 2 * lane) = (uint16_t)code;
     const int slot = (lane >> 1) ^ (((r >> 6) & 3) << 3);
     img16[(r * AP_LD + slot) * 2 + (lane & 1)] = (uint16_t)code;
   }
+  U::finish(acc, a);
   __syncthreads();
   const int mg = t & 7, kb = t >> 3;
   uint32_t out[8][4];
@@ -1186,7 +1232,7 @@ BNN_API int bnn_adam_pack_set_tile256(int32_t on) {
   return 0;
 }
 
-// the fused update + pack of policy U (AdamUpdate / SgdUpdate): one argument contract and one dispatch
+// the fused update + pack of policy U (AdamUpdate / SgdUpdate / BopUpdate): one argument contract and one dispatch
 template <class U>
 static int update_pack_impl(const char* name, float* p, const typename U::Args& a, int64_t N, int64_t K,
                             int32_t fmt, void* q, int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt,
@@ -1272,6 +1318,18 @@ BNN_API int bnn_sgd_clamp_pack(float* p, const float* grad, float* buf, int64_t 
   if (momentum == 0.f) return update_pack_impl<SgdUpdate<0>>(name, p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
   if (first) return update_pack_impl<SgdUpdate<1>>(name, p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
   return update_pack_impl<SgdUpdate<2>>(name, p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
+}
+
+BNN_API int bnn_bop_pack(float* w, const float* grad, float* m, int64_t N, int64_t K, float gamma, float threshold,
+                         float grad_scale, int64_t* flips, int32_t fmt, void* q, int64_t ldq, int8_t* qt,
+                         int64_t ldqt, int32_t qt_fmt, void* stream) {
+  if (!bop_hyper_ok(gamma, threshold)) {
+    set_error("bnn_bop_pack: gamma=%g must lie in (0, 1], threshold=%g must not be negative", (double)gamma,
+              (double)threshold);
+    return kErrInval;
+  }
+  const BopArgs a{grad, m, gamma, threshold, grad_scale, flips};
+  return update_pack_impl<BopUpdate>("bnn_bop_pack", w, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
 }
 
 static int sign_f32_impl(const char* name, const float* x, float* y, int64_t n, const Stoch* st, void* stream) {

@@ -262,6 +262,56 @@ BNN_API int bnn_sgd_clamp_multi(int32_t count, float* const* p, const float* con
   return check_launch("bnn_sgd_clamp_multi");
 }
 
+// Bop over a flat tensor (math: bop_elem in bnn_common.h): 5 fp32 streams (w, g, m read; w, m written).
+// vec: all three pointers 16-B aligned -> float4 runs and a scalar tail, else scalar throughout.
+namespace bnn {
+namespace {
+
+__global__ __launch_bounds__(256) void bop_k(float* __restrict__ w, int64_t n, BopArgs a, int vec) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int nf = 0;
+  int64_t tail = 0;
+  if (vec) {
+    const int64_t n4 = n / 4;
+    for (int64_t i = i0; i < n4; i += stride) {
+      float4 wv = reinterpret_cast<const float4*>(w)[i];
+      const float4 gv = reinterpret_cast<const float4*>(a.g)[i];
+      float4 mv = reinterpret_cast<const float4*>(a.m)[i];
+      wv.x = bop_elem(wv.x, gv.x, mv.x, a, nf);
+      wv.y = bop_elem(wv.y, gv.y, mv.y, a, nf);
+      wv.z = bop_elem(wv.z, gv.z, mv.z, a, nf);
+      wv.w = bop_elem(wv.w, gv.w, mv.w, a, nf);
+      reinterpret_cast<float4*>(w)[i] = wv;
+      reinterpret_cast<float4*>(a.m)[i] = mv;
+    }
+    tail = n4 * 4;
+  }
+  for (int64_t i = tail + i0; i < n; i += stride) {
+    float mi = a.m[i];
+    w[i] = bop_elem(w[i], a.g[i], mi, a, nf);
+    a.m[i] = mi;
+  }
+  bop_flush(nf, a.flips);
+}
+
+}  // namespace
+}  // namespace bnn
+
+BNN_API int bnn_bop(float* w, const float* grad, float* m, int64_t n, float gamma, float threshold, float grad_scale,
+                    int64_t* flips, void* stream) {
+  if (n < 0 || (n > 0 && (!w || !grad || !m)) || !bop_hyper_ok(gamma, threshold)) {
+    set_error("bnn_bop: bad arguments (n=%lld gamma=%g threshold=%g)", (long long)n, (double)gamma, (double)threshold);
+    return kErrInval;
+  }
+  if (n == 0) return 0;
+  const int vec = aligned16(w) && aligned16(grad) && aligned16(m);
+  const BopArgs a{grad, m, gamma, threshold, grad_scale, flips};
+  hipLaunchKernelGGL(bop_k, dim3(grid_for(vec ? (n + 3) / 4 : n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     w, n, a, vec);
+  return check_launch("bnn_bop");
+}
+
 BNN_API int bnn_adam_schedule(float lr, float beta1, float beta2, int64_t step0, int64_t n, float* out) {
   if (!out || n < 0 || step0 < 1) {
     set_error("bnn_adam_schedule: bad arguments");

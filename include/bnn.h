@@ -970,6 +970,32 @@ int bnn_sgd_clamp_pack(float* p, const float* grad, float* buf, int64_t N, int64
                        int32_t clamp, int32_t fmt, void* q, int64_t ldq, int8_t* qt, int64_t ldqt, int32_t qt_fmt,
                        bnn_stream_t stream);
 
+/* ---------------------------------------------------------------- Bop, the binary optimizer
+ * Helwegen et al., "Latent Weights Do Not Exist: Rethinking Binarized Neural Network Optimization"
+ * (NeurIPS 2019); larq's Bop.  No latent weight: w is +-1, the only state is m, an exponential moving
+ * average of the gradient (zeros before the first step), and a weight flips when the average exceeds the
+ * threshold and has the weight's sign.  Per element, every operation one fp32 rounding (no fma):
+ *   g = grad * grad_scale;  m = m + gamma * (g - m)
+ *   s = w < 0 ? -1 : +1                     (any w is accepted; 0, -0 and NaN count as +1)
+ *   w = (s * m > threshold) ? -s : s        (strict: a tie or a NaN average does not flip)
+ * so w leaves as exactly +-1.0f and a parameter's first step binarizes its initial value.  Nothing depends
+ * on a step count: a captured step replays these launches unchanged.  5 fp32 streams (w, grad, m read;
+ * w, m written).
+ * flips (nullable): the launch adds its exact number of flipped elements (w_new != s) to flips[0]; the
+ * first-step normalisation of a value that is not +-1 is not a flip.  Counted in registers, one 64-bit
+ * atomic add per wave that flipped anything; integer sums do not depend on the order, so it is deterministic.
+ * BNN_EINVAL: null w / grad / m with elements to do, gamma outside (0, 1], a negative or NaN threshold, the
+ * pack entry's ldq / ldqt conditions. */
+int bnn_bop(float* w, const float* grad, float* m, int64_t n, float gamma, float threshold, float grad_scale,
+            int64_t* flips, bnn_stream_t stream);
+/* bnn_bop fused with the next forward's weight packing: the contract of bnn_adam_clamp_pack (w [N][K]
+ * row-major, grad and m alike; q / qt / fmt / qt_fmt / ldq / ldqt as there; the same kernels with the Bop
+ * element, the same bnn_adam_pack_set_tile256 hook).  w, m and the count bit-identical to bnn_bop; q, qt
+ * bit-identical to sign-packing the updated weight, zero padding included. */
+int bnn_bop_pack(float* w, const float* grad, float* m, int64_t N, int64_t K, float gamma, float threshold,
+                 float grad_scale, int64_t* flips, int32_t fmt, void* q, int64_t ldq, int8_t* qt, int64_t ldqt,
+                 int32_t qt_fmt, bnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
