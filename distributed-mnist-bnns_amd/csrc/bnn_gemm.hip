@@ -904,166 +904,299 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_i8_bnsign_k(GemmP
   gemm_v2_body<1, 1, WAVES_M, WAVES_N, WM, WN, STAGES, BKT, 0, 0, 0, 0, 0, 1>(p);
 }
 
-// Launch of a BN-sign form.  The grid's tiles cover columns 0 .. gn*BN-1 <= 2 ldq4 of every row
-// < M (codes 0 at columns >= N); the rest of the row's pad is cleared here.
-template <int F4, int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0, int S16 = 0>
-int launch_bnsign(GemmParams p, hipStream_t s) {
-  constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
+// ------------------------------------------------------------------------------------------------
+// Launchers: one per kernel template, named launch_<kernel> and taking the kernel's own template
+// arguments, so a table row instantiates its launcher from the arguments that name it.
+
+// The grid of BM x BN tiles over the output, one workgroup per tile (fills p.gm, p.gn)
+template <int BM, int BN>
+dim3 tile_grid(GemmParams& p) {
   p.gm = (p.M + BM - 1) / BM;
   p.gn = (p.N + BN - 1) / BN;
-  const int64_t covered = (int64_t)p.gn * BN / 2;   // bytes of each q4 row the tiles write
-  if (covered < p.ldq4) {
-    const hipError_t e = hipMemset2DAsync(p.Q4 + covered, (size_t)p.ldq4, 0, (size_t)(p.ldq4 - covered), (size_t)p.M, s);
-    if (e != hipSuccess) {
-      set_error("bnn_gemm_bnsign: clearing the pad failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-  }
-  const dim3 grid((unsigned)((int64_t)p.gm * p.gn)), block(64 * WAVES_M * WAVES_N);
-  if constexpr (F4) {
-    hipLaunchKernelGGL((gemm_fp4_bnsign_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, S16>), grid, block, 0, s, p);
-    return check_launch("bnn_gemm_fp4_bnsign");
-  } else {
-    static_assert(IL == 0 && S16 == 0, "int8 BN-sign form: the 32x32 BK=64 kernels");
-    hipLaunchKernelGGL((gemm_i8_bnsign_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT>), grid, block, 0, s, p);
-    return check_launch("bnn_gemm_i8_affine_bnsign");
-  }
+  return dim3((unsigned)((int64_t)p.gm * p.gn));
 }
-
-template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0, int S16 = 0, int BST = 0>
-int launch_fp4h(GemmParams p, hipStream_t s) {
-  constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
-  p.gm = (p.M + BM - 1) / BM;
-  p.gn = (p.N + BN - 1) / BN;
-  hipLaunchKernelGGL((gemm_fp4_h_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, S16, BST>),
-                     dim3((unsigned)((int64_t)p.gm * p.gn)), dim3(64 * WAVES_M * WAVES_N), 0, s, p);
-  return check_launch("bnn_gemm_fp4");
-}
-
-template <int DA, int DB, int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0,
-          int DIAG = 0, int F4 = 0, int S16 = 0, int BST = 0>
-int launch_v2(GemmParams p, hipStream_t s) {
-  constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32;
-  p.gm = (p.M + BM - 1) / BM;
-  p.gn = (p.N + BN - 1) / BN;
-  const int64_t nblk = (int64_t)p.gm * p.gn;
-  if constexpr (F4) {
-    static_assert(DA == 1 && DB == 1 && DIAG == 0, "FP4 form");
-    hipLaunchKernelGGL((gemm_fp4_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, S16, BST>), dim3((unsigned)nblk),
-                       dim3(64 * WAVES_M * WAVES_N), 0, s, p);
-    return check_launch("bnn_gemm_fp4");
-  } else {
-    hipLaunchKernelGGL((gemm_i8_v2_k<DA, DB, WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, DIAG, S16, BST>),
-                       dim3((unsigned)nblk), dim3(64 * WAVES_M * WAVES_N), 0, s, p);
-    return check_launch("bnn_gemm_i8");
-  }
-}
-
-int g_variant = -1;  // tuning hook (bnn_gemm_set_variant); -1 = default table
-int g_raster = 0;    // tuning hook (bnn_gemm_set_raster): GemmParams::raster of the affine entry
 
 template <int DA, int DB, int WM, int WN>
-int launch(GemmParams p, hipStream_t s) {
-  constexpr int BM = 64 * WM, BN = 64 * WN;
-  p.gm = (p.M + BM - 1) / BM;
-  p.gn = (p.N + BN - 1) / BN;
-  const int64_t nblk = (int64_t)p.gm * p.gn;
-  hipLaunchKernelGGL((gemm_i8_k<DA, DB, WM, WN>), dim3((unsigned)nblk), dim3(256), 0, s, p);
+int launch_gemm_i8_k(GemmParams p, hipStream_t s) {
+  const dim3 grid = tile_grid<64 * WM, 64 * WN>(p);
+  hipLaunchKernelGGL((gemm_i8_k<DA, DB, WM, WN>), grid, dim3(256), 0, s, p);
   return check_launch("bnn_gemm_i8");
 }
 
-// Kernel table; the default choice per digit configuration and shape comes from
-// tools/gemm_sweep.py on MI355X (profiles/r01_gemm_sweep*.log).
-struct Variant {
-  int id;
-  const char* name;  // as rocprofv3 lists the instance
-  int (*fn)(GemmParams, hipStream_t);
-  int bk;
-};
+template <int DA, int DB, int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL, int DIAG, int S16, int BST>
+int launch_gemm_i8_v2_k(GemmParams p, hipStream_t s) {
+  const dim3 grid = tile_grid<WAVES_M * WM * 32, WAVES_N * WN * 32>(p);
+  hipLaunchKernelGGL((gemm_i8_v2_k<DA, DB, WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, DIAG, S16, BST>), grid,
+                     dim3(64 * WAVES_M * WAVES_N), 0, s, p);
+  return check_launch("bnn_gemm_i8");
+}
 
-const Variant kVariants[] = {
-    {0, "gemm_i8_k<1, 1, 2, 2>", launch<1, 1, 2, 2>, 64},
-    {1, "gemm_i8_v2_k<1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0>", launch_v2<1, 1, 2, 2, 2, 2, 3, 64>, 64},
-    {2, "gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 3, 64, 0, 0, 0>", launch_v2<1, 1, 2, 4, 4, 2, 3, 64>, 64},
-    {3, "gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 0, 0, 0>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128>, 128},
-    {4, "gemm_i8_v2_k<1, 1, 2, 2, 4, 4, 2, 64, 0, 0, 0>", launch_v2<1, 1, 2, 2, 4, 4, 2, 64>, 64},
-    {5, "gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 4, 64, 0, 0, 0>", launch_v2<1, 1, 2, 4, 4, 2, 4, 64>, 64},
-    {6, "gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 1, 0, 0>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 1>, 128},
-    // 16x16 MFMA shape (S16) of variants 3/6, 14, 33 (DVFS: higher clock held on 16x16)
-    {7, "gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 0, 0, 1>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 0, 0, 0, 1>, 128},
-    {8, "gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 1, 0, 1>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 1, 0, 0, 1>, 128},
-    {17, "gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 2, 128, 0, 0, 1>", launch_v2<3, 1, 2, 4, 2, 2, 2, 128, 0, 0, 0, 1>, 128},
-    {18, "gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 2, 128, 2, 0, 1>", launch_v2<3, 1, 2, 4, 2, 2, 2, 128, 2, 0, 0, 1>, 128},
-    {34, "gemm_fp4_k<2, 4, 4, 2, 2, 128, 0, 1>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 0, 0, 1, 1>, 128},
-    {35, "gemm_fp4_k<2, 4, 4, 2, 2, 128, 1, 1>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 1, 0, 1, 1>, 128},
-    // IL = 2: LDS-DMA pieces spread between the MFMAs (9, 18, 36: 16x16; 19: 16x16 + B prefetch)
-    {9, "gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 2, 0, 1>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 2, 0, 0, 1>, 128},
-    {19, "gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 2, 128, 0, 3, 1>", launch_v2<3, 1, 2, 4, 2, 2, 2, 128, 0, 3, 0, 1>, 128},
-    {36, "gemm_fp4_k<2, 4, 4, 2, 2, 128, 2, 1>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 2, 0, 1, 1>, 128},
-    {77, "diag: v6 without LDS fragment reads", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 1, 1>, 128},
-    {78, "diag: v6 without global->LDS staging", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 1, 2>, 128},
-    {10, "gemm_i8_k<3, 1, 2, 2>", launch<3, 1, 2, 2>, 64},
-    {11, "gemm_i8_v2_k<3, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0>", launch_v2<3, 1, 2, 2, 2, 2, 3, 64>, 64},
-    {12, "gemm_i8_v2_k<3, 1, 4, 2, 2, 2, 2, 64, 0, 0, 0>", launch_v2<3, 1, 4, 2, 2, 2, 2, 64>, 64},
-    {13, "gemm_i8_v2_k<3, 1, 2, 4, 2, 1, 3, 64, 0, 0, 0>", launch_v2<3, 1, 2, 4, 2, 1, 3, 64>, 64},
-    {14, "gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 2, 128, 0, 0, 0>", launch_v2<3, 1, 2, 4, 2, 2, 2, 128>, 128},
-    {15, "gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 3, 64, 0, 0, 0>", launch_v2<3, 1, 2, 4, 2, 2, 3, 64>, 64},
-    {16, "gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 4, 64, 0, 0, 0>", launch_v2<3, 1, 2, 4, 2, 2, 4, 64>, 64},
-    // timing-only diagnostics (wrong results; never picked by default)
-    {97, "diag: v14 without LDS fragment reads", launch_v2<3, 1, 2, 4, 2, 2, 2, 128, 0, 1>, 128},
-    {98, "diag: v14 without global->LDS staging", launch_v2<3, 1, 2, 4, 2, 2, 2, 128, 0, 2>, 128},
-    {20, "gemm_i8_k<3, 3, 2, 1>", launch<3, 3, 2, 1>, 64},
-    // FP4 (e2m1) ternary x ternary forms (bnn_gemm_fp4): K in bytes, 2 elements per byte
-    {30, "gemm_fp4_k<2, 4, 4, 2, 2, 128, 1, 0>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 1, 0, 1>, 128},
-    {31, "gemm_fp4_k<2, 2, 2, 2, 3, 64, 0, 0>", launch_v2<1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 1>, 64},
-    {32, "gemm_fp4_k<2, 4, 4, 2, 3, 64, 0, 0>", launch_v2<1, 1, 2, 4, 4, 2, 3, 64, 0, 0, 1>, 64},
-    {33, "gemm_fp4_k<2, 4, 4, 2, 2, 128, 0, 0>", launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 0, 0, 1>, 128},
-    // two workgroups per CU (A/B sweep, tools/fp4_half_ab.py): 128 x 256 tiles with BK 64 (3 / 2
-    // stages), 128 x 128 tiles of 2 waves with BK 128 + 16x16 MFMAs
-    {37, "gemm_fp4_h_k<1, 4, 4, 2, 3, 64, 0, 0>", launch_fp4h<1, 4, 4, 2, 3, 64, 0, 0>, 64},
-    {38, "gemm_fp4_h_k<1, 4, 4, 2, 2, 64, 0, 0>", launch_fp4h<1, 4, 4, 2, 2, 64, 0, 0>, 64},
-    {39, "gemm_fp4_h_k<1, 2, 4, 2, 2, 128, 2, 1>", launch_fp4h<1, 2, 4, 2, 2, 128, 2, 1>, 128},
-    {21, "gemm_i8_v2_k<3, 3, 2, 2, 2, 1, 2, 64, 0, 0, 0>", launch_v2<3, 3, 2, 2, 2, 1, 2, 64>, 64},
-    {22, "gemm_i8_v2_k<3, 3, 2, 4, 2, 1, 2, 64, 0, 0, 0>", launch_v2<3, 3, 2, 4, 2, 1, 2, 64>, 64},
-};
+template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0, int S16 = 0, int BST = 0>
+int launch_gemm_fp4_k(GemmParams p, hipStream_t s) {
+  const dim3 grid = tile_grid<WAVES_M * WM * 32, WAVES_N * WN * 32>(p);
+  hipLaunchKernelGGL((gemm_fp4_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, S16, BST>), grid,
+                     dim3(64 * WAVES_M * WAVES_N), 0, s, p);
+  return check_launch("bnn_gemm_fp4");
+}
 
-const Variant* find_variant(int id) {
-  for (const Variant& v : kVariants)
-    if (v.id == id) return &v;
+template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0, int S16 = 0, int BST = 0>
+int launch_gemm_fp4_h_k(GemmParams p, hipStream_t s) {
+  const dim3 grid = tile_grid<WAVES_M * WM * 32, WAVES_N * WN * 32>(p);
+  hipLaunchKernelGGL((gemm_fp4_h_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, S16, BST>), grid,
+                     dim3(64 * WAVES_M * WAVES_N), 0, s, p);
+  return check_launch("bnn_gemm_fp4");
+}
+
+// A BN-sign form's tiles cover columns 0 .. gn*BN-1 <= 2 ldq4 of every row < M (codes 0 at columns
+// >= N); the rest of the row's pad is cleared here, before the launch.
+int clear_q4_pad(const GemmParams& p, int BN, hipStream_t s) {
+  const int64_t covered = (int64_t)p.gn * BN / 2;   // bytes of each q4 row the tiles write
+  if (covered >= p.ldq4) return 0;
+  const hipError_t e = hipMemset2DAsync(p.Q4 + covered, (size_t)p.ldq4, 0, (size_t)(p.ldq4 - covered), (size_t)p.M, s);
+  if (e != hipSuccess) set_error("bnn_gemm_bnsign: clearing the pad failed: %s", hipGetErrorString(e));
+  return (int)e;
+}
+
+template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT, int IL = 0, int S16 = 0>
+int launch_gemm_fp4_bnsign_k(GemmParams p, hipStream_t s) {
+  const dim3 grid = tile_grid<WAVES_M * WM * 32, WAVES_N * WN * 32>(p);
+  if (const int e = clear_q4_pad(p, WAVES_N * WN * 32, s)) return e;
+  hipLaunchKernelGGL((gemm_fp4_bnsign_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT, IL, S16>), grid,
+                     dim3(64 * WAVES_M * WAVES_N), 0, s, p);
+  return check_launch("bnn_gemm_fp4_bnsign");
+}
+
+template <int WAVES_M, int WAVES_N, int WM, int WN, int STAGES, int BKT>
+int launch_gemm_i8_bnsign_k(GemmParams p, hipStream_t s) {
+  const dim3 grid = tile_grid<WAVES_M * WM * 32, WAVES_N * WN * 32>(p);
+  if (const int e = clear_q4_pad(p, WAVES_N * WN * 32, s)) return e;
+  hipLaunchKernelGGL((gemm_i8_bnsign_k<WAVES_M, WAVES_N, WM, WN, STAGES, BKT>), grid, dim3(64 * WAVES_M * WAVES_N), 0,
+                     s, p);
+  return check_launch("bnn_gemm_i8_affine_bnsign");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Dispatch.  One table of every gemm_i8_k / gemm_i8_v2_k / gemm_fp4_k / gemm_fp4_h_k / *_bnsign_k
+// instance the library can launch -- (row id, digit family, label, tile rows, columns and k-step,
+// statistics chunk, the kernel and its template arguments) -- and one decision function, select,
+// that maps a launch (family, epilogue, shape, row pitches) and the process-global switches to a
+// row.  The launching entries call the row's launcher and the queries read the row, so a query cannot
+// disagree with the launch, and a new row is launched, named and listed at once.  The instance
+// string is generated from the row's template arguments (the gemm_fp4 rows leave the trailing BST = 0
+// to its default).  The label is what bnn_gemm_i8_kernel reports: a prefix key, not an instance name
+// -- bench.py matches it against profiler names up to the next "," or ">" -- which is the row's own
+// string, the label of the row whose tile it runs on, or free text.
+// Ids below 100 are the variants of bnn_gemm_set_variant (family base 0 / 10 / 20 / 30 + v: A/B and
+// the tuning sweeps; the default choice per family and shape comes from tools/gemm_sweep.py on
+// MI355X, profiles/r01_gemm_sweep*.log); from 100 on, the forms that only select chooses: Bst = the
+// BatchNorm forward-statistics epilogue (chunk = the rows of one wave row of the tile), Bns = the
+// BN-sign epilogue, each on the 128 x 128 and the 256 x 256 tile of the family's default choices.
+enum { kFam11, kFam31, kFam33, kFamFp4 };   // digit families (a_digits, b_digits); row ids from 10 * family
+enum { kRowI8Bst128 = 100, kRowI8Bst256, kRowFp4Bst128, kRowFp4Bst256, kRowFp4Bns128, kRowFp4Bns256, kRowI8Bns128, kRowI8Bns256 };
+#define GEMM_SELF nullptr, -1         // label: the row's own instance string
+#define GEMM_AS(ID) nullptr, ID       // label: as row ID's
+#define GEMM_TEXT(S) S, -1            // label: free text
+// The gemm_i8_v2_k labels were typed when the template had 11 parameters (BST is the 12th); they stay
+// as text: they are bench.py's timer keys and the keys of the committed profiles.
+#define BNN_GEMM_INSTANCES(X) \
+  X(0, kFam11, GEMM_SELF, 128, 128, 64, 0, gemm_i8_k, 1, 1, 2, 2) \
+  X(1, kFam11, GEMM_TEXT("gemm_i8_v2_k<1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0>"), 128, 128, 64, 0, gemm_i8_v2_k, 1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0, 0) \
+  X(2, kFam11, GEMM_TEXT("gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 3, 64, 0, 0, 0>"), 256, 256, 64, 0, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 3, 64, 0, 0, 0, 0) \
+  X(3, kFam11, GEMM_TEXT("gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 0, 0, 0>"), 256, 256, 128, 0, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 2, 128, 0, 0, 0, 0) \
+  X(4, kFam11, GEMM_TEXT("gemm_i8_v2_k<1, 1, 2, 2, 4, 4, 2, 64, 0, 0, 0>"), 256, 256, 64, 0, gemm_i8_v2_k, 1, 1, 2, 2, 4, 4, 2, 64, 0, 0, 0, 0) \
+  X(5, kFam11, GEMM_TEXT("gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 4, 64, 0, 0, 0>"), 256, 256, 64, 0, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 4, 64, 0, 0, 0, 0) \
+  X(6, kFam11, GEMM_TEXT("gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 1, 0, 0>"), 256, 256, 128, 0, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 2, 128, 1, 0, 0, 0) \
+  /* 16x16 MFMA shape (S16) of variants 3/6, 14, 33 (DVFS: higher clock held on 16x16) */ \
+  X(7, kFam11, GEMM_TEXT("gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 0, 0, 1>"), 256, 256, 128, 0, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 2, 128, 0, 0, 1, 0) \
+  X(8, kFam11, GEMM_TEXT("gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 1, 0, 1>"), 256, 256, 128, 0, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 2, 128, 1, 0, 1, 0) \
+  X(17, kFam31, GEMM_TEXT("gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 2, 128, 0, 0, 1>"), 128, 256, 128, 0, gemm_i8_v2_k, 3, 1, 2, 4, 2, 2, 2, 128, 0, 0, 1, 0) \
+  X(18, kFam31, GEMM_TEXT("gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 2, 128, 2, 0, 1>"), 128, 256, 128, 0, gemm_i8_v2_k, 3, 1, 2, 4, 2, 2, 2, 128, 2, 0, 1, 0) \
+  X(34, kFamFp4, GEMM_SELF, 256, 256, 128, 0, gemm_fp4_k, 2, 4, 4, 2, 2, 128, 0, 1) \
+  X(35, kFamFp4, GEMM_SELF, 256, 256, 128, 0, gemm_fp4_k, 2, 4, 4, 2, 2, 128, 1, 1) \
+  /* IL = 2: LDS-DMA pieces spread between the MFMAs (9, 18, 36: 16x16; 19: 16x16 + B prefetch) */ \
+  X(9, kFam11, GEMM_TEXT("gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 2, 128, 2, 0, 1>"), 256, 256, 128, 0, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 2, 128, 2, 0, 1, 0) \
+  X(19, kFam31, GEMM_TEXT("gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 2, 128, 0, 3, 1>"), 128, 256, 128, 0, gemm_i8_v2_k, 3, 1, 2, 4, 2, 2, 2, 128, 0, 3, 1, 0) \
+  X(36, kFamFp4, GEMM_SELF, 256, 256, 128, 0, gemm_fp4_k, 2, 4, 4, 2, 2, 128, 2, 1) \
+  /* timing-only diagnostics (wrong results; never picked by default) */ \
+  X(77, kFam11, GEMM_TEXT("diag: v6 without LDS fragment reads"), 256, 256, 128, 0, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 2, 128, 1, 1, 0, 0) \
+  X(78, kFam11, GEMM_TEXT("diag: v6 without global->LDS staging"), 256, 256, 128, 0, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 2, 128, 1, 2, 0, 0) \
+  X(10, kFam31, GEMM_SELF, 128, 128, 64, 0, gemm_i8_k, 3, 1, 2, 2) \
+  X(11, kFam31, GEMM_TEXT("gemm_i8_v2_k<3, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0>"), 128, 128, 64, 0, gemm_i8_v2_k, 3, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0, 0) \
+  X(12, kFam31, GEMM_TEXT("gemm_i8_v2_k<3, 1, 4, 2, 2, 2, 2, 64, 0, 0, 0>"), 256, 128, 64, 0, gemm_i8_v2_k, 3, 1, 4, 2, 2, 2, 2, 64, 0, 0, 0, 0) \
+  X(13, kFam31, GEMM_TEXT("gemm_i8_v2_k<3, 1, 2, 4, 2, 1, 3, 64, 0, 0, 0>"), 128, 128, 64, 0, gemm_i8_v2_k, 3, 1, 2, 4, 2, 1, 3, 64, 0, 0, 0, 0) \
+  X(14, kFam31, GEMM_TEXT("gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 2, 128, 0, 0, 0>"), 128, 256, 128, 0, gemm_i8_v2_k, 3, 1, 2, 4, 2, 2, 2, 128, 0, 0, 0, 0) \
+  X(15, kFam31, GEMM_TEXT("gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 3, 64, 0, 0, 0>"), 128, 256, 64, 0, gemm_i8_v2_k, 3, 1, 2, 4, 2, 2, 3, 64, 0, 0, 0, 0) \
+  X(16, kFam31, GEMM_TEXT("gemm_i8_v2_k<3, 1, 2, 4, 2, 2, 4, 64, 0, 0, 0>"), 128, 256, 64, 0, gemm_i8_v2_k, 3, 1, 2, 4, 2, 2, 4, 64, 0, 0, 0, 0) \
+  X(97, kFam31, GEMM_TEXT("diag: v14 without LDS fragment reads"), 128, 256, 128, 0, gemm_i8_v2_k, 3, 1, 2, 4, 2, 2, 2, 128, 0, 1, 0, 0) \
+  X(98, kFam31, GEMM_TEXT("diag: v14 without global->LDS staging"), 128, 256, 128, 0, gemm_i8_v2_k, 3, 1, 2, 4, 2, 2, 2, 128, 0, 2, 0, 0) \
+  X(20, kFam33, GEMM_SELF, 128, 64, 64, 0, gemm_i8_k, 3, 3, 2, 1) \
+  /* FP4 (e2m1) ternary x ternary forms (bnn_gemm_fp4): K in bytes, 2 elements per byte */ \
+  X(30, kFamFp4, GEMM_SELF, 256, 256, 128, 0, gemm_fp4_k, 2, 4, 4, 2, 2, 128, 1, 0) \
+  X(31, kFamFp4, GEMM_SELF, 128, 128, 64, 0, gemm_fp4_k, 2, 2, 2, 2, 3, 64, 0, 0) \
+  X(32, kFamFp4, GEMM_SELF, 256, 256, 64, 0, gemm_fp4_k, 2, 4, 4, 2, 3, 64, 0, 0) \
+  X(33, kFamFp4, GEMM_SELF, 256, 256, 128, 0, gemm_fp4_k, 2, 4, 4, 2, 2, 128, 0, 0) \
+  /* two workgroups per CU (A/B sweep, tools/fp4_half_ab.py): 128 x 256 tiles with BK 64 (3 / 2 */ \
+  /* stages), 128 x 128 tiles of 2 waves with BK 128 + 16x16 MFMAs */ \
+  X(37, kFamFp4, GEMM_SELF, 128, 256, 64, 0, gemm_fp4_h_k, 1, 4, 4, 2, 3, 64, 0, 0) \
+  X(38, kFamFp4, GEMM_SELF, 128, 256, 64, 0, gemm_fp4_h_k, 1, 4, 4, 2, 2, 64, 0, 0) \
+  X(39, kFamFp4, GEMM_SELF, 128, 128, 128, 0, gemm_fp4_h_k, 1, 2, 4, 2, 2, 128, 2, 1) \
+  X(21, kFam33, GEMM_TEXT("gemm_i8_v2_k<3, 3, 2, 2, 2, 1, 2, 64, 0, 0, 0>"), 128, 64, 64, 0, gemm_i8_v2_k, 3, 3, 2, 2, 2, 1, 2, 64, 0, 0, 0, 0) \
+  X(22, kFam33, GEMM_TEXT("gemm_i8_v2_k<3, 3, 2, 4, 2, 1, 2, 64, 0, 0, 0>"), 128, 128, 64, 0, gemm_i8_v2_k, 3, 3, 2, 4, 2, 1, 2, 64, 0, 0, 0, 0) \
+  X(kRowI8Bst128, kFam11, GEMM_AS(1), 128, 128, 64, 64, gemm_i8_v2_k, 1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0, 1) \
+  X(kRowI8Bst256, kFam11, GEMM_AS(2), 256, 256, 64, 128, gemm_i8_v2_k, 1, 1, 2, 4, 4, 2, 3, 64, 0, 0, 0, 1) \
+  X(kRowFp4Bst128, kFamFp4, GEMM_AS(31), 128, 128, 64, 64, gemm_fp4_k, 2, 2, 2, 2, 3, 64, 0, 0, 1) \
+  X(kRowFp4Bst256, kFamFp4, GEMM_AS(36), 256, 256, 128, 128, gemm_fp4_k, 2, 4, 4, 2, 2, 128, 2, 1, 1) \
+  X(kRowFp4Bns128, kFamFp4, GEMM_AS(31), 128, 128, 64, 0, gemm_fp4_bnsign_k, 2, 2, 2, 2, 3, 64, 0, 0) \
+  X(kRowFp4Bns256, kFamFp4, GEMM_AS(36), 256, 256, 128, 0, gemm_fp4_bnsign_k, 2, 4, 4, 2, 2, 128, 2, 1) \
+  X(kRowI8Bns128, kFam11, GEMM_AS(1), 128, 128, 64, 0, gemm_i8_bnsign_k, 2, 2, 2, 2, 3, 64) \
+  X(kRowI8Bns256, kFam11, GEMM_AS(2), 256, 256, 64, 0, gemm_i8_bnsign_k, 2, 4, 4, 2, 3, 64)
+
+struct Inst {
+  int id, fam;
+  const char* text;   // the label as free text, or
+  int as;             // the row whose label this one shares (-1 with no text: its own instance string)
+  int bm, bn, bk;     // rows, columns and k-step per tile
+  int chunk;          // rows per statistics partial (0: no statistics epilogue)
+  const char* name;   // the instance, "kernel<template arguments>"
+  int (*launch)(GemmParams, hipStream_t);
+};
+#define BNN_STR_(...) #__VA_ARGS__
+#define BNN_STR(...) BNN_STR_(__VA_ARGS__)
+#define BNN_X(ID, FAM, LABEL, BM, BN, BKT, CHUNK, KERNEL, ...) \
+  {ID, FAM, LABEL, BM, BN, BKT, CHUNK, #KERNEL "<" BNN_STR(__VA_ARGS__) ">", launch_##KERNEL<__VA_ARGS__>},
+const Inst kInst[] = {BNN_GEMM_INSTANCES(BNN_X)};
+#undef BNN_X
+
+const Inst* row(int id) {
+  for (const Inst& r : kInst)
+    if (r.id == id) return &r;
   return nullptr;
 }
 
-const Variant* pick_kernel(int a_digits, int b_digits, int64_t M, int64_t N, int64_t K) {
-  if (a_digits == 0) {  // FP4 ternary form; K in bytes
-    const bool big = ((M + 255) / 256) * ((N + 255) / 256) >= 512;
-    int id = g_variant >= 0 ? 30 + g_variant : (big ? 36 : 31);   // sweep r01: 36 = 0.435 of FP4 peak
-    const Variant* v = find_variant(id);
-    if (v == nullptr) v = find_variant(31);
-    if (K % v->bk != 0) v = find_variant(big ? 32 : 31);
-    return v;
-  }
-  const int base = a_digits == 1 ? 0 : (b_digits == 1 ? 10 : 20);
-  int id, alt;  // alt = the BK=64 sibling used when K % 128 != 0
-  if (g_variant >= 0) {
-    id = base + g_variant;
-    alt = base + 1;
-  } else if (a_digits == 1) {   // sweep r01: 256x256 BK128 16x16-MFMA + DMA spread 0.49 of peak; 128x128 on small grids
-    const bool big = ((M + 255) / 256) * ((N + 255) / 256) >= 512;
-    id = big ? 9 : 1;
-    alt = big ? 2 : 1;
-  } else if (b_digits == 1) {   // 128x256 BK128 8 waves 16x16-MFMA + DMA spread: 0.51-0.56 of peak on dX / dW
-    const bool big = ((M + 127) / 128) * ((N + 255) / 256) >= 256;
-    id = big ? 18 : 13;
-    alt = big ? 15 : 13;
+const char* label(const Inst& r) { return r.text ? r.text : r.as >= 0 ? label(*row(r.as)) : r.name; }
+
+// The process-global switches select reads, each with its setter's semantics.
+struct GemmSwitches {
+  // bnn_gemm_set_variant: >= 0 forces row `family base + variant` of the table on the plain and int16
+  // launches (and on the plan the FP4 statistics form follows); an id the table does not hold, from
+  // 100 on or of another family: the family's row base + 1.  Where K is no multiple of the row's
+  // k-step: base + 1 (FP4: row 32 on big grids, else 31).
+  int variant = -1;
+  // bnn_gemm_set_raster: GemmParams::raster of bnn_gemm_i8_affine (1 = row-major tile order)
+  int raster = 0;
+  // bnn_gemm_i8_bnstats_set_tile: the tile of the u8-pixel statistics and s20 forms -- 0 = by grid
+  // size, 1 = always 128 x 128, 2 = always 256 x 256 (A/B hook; the chunk query and the launch read it)
+  int bnstats_tile = 0;
+} g_sw;
+
+enum { kPlain, kI16, kStats, kS20, kBnSign };   // the epilogue of a launch: bnn_gemm_instance's `form`
+
+struct GemmQuery {
+  int fam, epi;
+  int64_t M, N, K;
+  int64_t lda, ldb;   // row pitches in bytes: the v2 kernels address a tile's rows with 32-bit per-lane offsets
+};
+
+inline int64_t tiles(int64_t M, int64_t N, int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); }
+inline bool offsets_fit(int64_t lda, int64_t ldb) { return lda * 256 < (1LL << 31) && ldb * 256 < (1LL << 31); }
+
+// The one decision: the row a launch runs, nullptr where the family or the shape has no such form.
+// No HIP call.
+const Inst* select(const GemmQuery& q) {
+  const GemmSwitches& sw = g_sw;
+  const bool fp4 = q.fam == kFamFp4, pix = q.fam == kFam11;
+  const int base = 10 * q.fam;
+  // sweep r01: the 256 x 256 tiles from 512 of them on (0.49 of the int8 peak, 0.435 of FP4's), 128 x 128 below
+  const bool big = tiles(q.M, q.N, 256, 256) >= 512;
+  // the int16 output is FP4's, the s20 output (1,1)'s, the statistics and BN-sign epilogues both's
+  if (q.epi == kI16 ? !fp4 : q.epi == kS20 ? !pix : q.epi != kPlain && !fp4 && !pix) return nullptr;
+  // BN-sign: the tiles of the default choices (FP4 36 / 31, 31 also where K % 128 != 0; (1,1) 2 / 1,
+  // the BK = 64 rows the pixel GEMM takes at K = 832), whatever the switches say
+  if (q.epi == kBnSign)
+    return row(fp4 ? (big && q.K % 128 == 0 ? kRowFp4Bns256 : kRowFp4Bns128) : (big ? kRowI8Bns256 : kRowI8Bns128));
+  // the (1,1) statistics and s20 forms: the BK = 64 32x32 tiles only; bnstats_tile, never the variant
+  if (pix && q.epi != kPlain)
+    return row((sw.bnstats_tile != 0 ? sw.bnstats_tile == 2 : big) ? kRowI8Bst256 : kRowI8Bst128);
+  // the int8 families fall back to the 64-bit addressing of gemm_i8_k (the FP4 entries refuse such rows)
+  if (!fp4 && !offsets_fit(q.lda, q.ldb)) return row(base);
+  int id, alt;   // alt: the BK = 64 sibling where K % 128 != 0
+  if (fp4) {
+    id = big ? 36 : 31, alt = big ? 32 : 31;
+  } else if (pix) {   // 256x256 BK128 16x16-MFMA + DMA spread
+    id = big ? 9 : 1, alt = big ? 2 : 1;
+  } else if (q.fam == kFam31) {   // 128x256 BK128 8 waves 16x16-MFMA + DMA spread: 0.51-0.56 of peak on dX / dW
+    const bool big31 = tiles(q.M, q.N, 128, 256) >= 256;
+    id = big31 ? 18 : 13, alt = big31 ? 15 : 13;
   } else {
-    id = 22;
-    alt = 22;
+    id = alt = 22;
   }
-  const Variant* v = find_variant(id);
-  if (v == nullptr) v = find_variant(base + 1);
-  if (K % v->bk != 0) v = find_variant(alt);
-  return v;
+  if (sw.variant >= 0) {
+    id = base + sw.variant;
+    if (!fp4) alt = base + 1;
+  }
+  const Inst* r = id < kRowI8Bst128 ? row(id) : nullptr;
+  if (r == nullptr || r->fam != q.fam) r = row(base + 1);
+  if (q.K % r->bk != 0) r = row(alt);
+  // the FP4 statistics form: its own instances of the two default choices; none of any other row (the
+  // big-grid BK = 64 fallback, K % 128 != 0, would spill)
+  if (q.epi == kStats) return row(r->id == 36 ? kRowFp4Bst256 : r->id == 31 ? kRowFp4Bst128 : -1);
+  return r;
 }
+
+// Digit family of (a_digits, b_digits), as lenient as the label query always was; cfg_ok: strictly
+// one of the three int8 configurations
+inline int family_of(int a_digits, int b_digits) {
+  return a_digits == 0 ? kFamFp4 : a_digits == 1 ? kFam11 : b_digits == 1 ? kFam31 : kFam33;
+}
+inline bool cfg_ok(int a_digits, int b_digits) {
+  return (a_digits == 1 && b_digits == 1) || (a_digits == 3 && (b_digits == 1 || b_digits == 3));
+}
+
+// What the entries' argument checks differ in
+enum : unsigned {
+  kPositive = 1,     // M, N > 0 (else >= 0: the entry returns 0 for an empty product)
+  kOffsetsErr = 2,   // row pitches past the 32-bit tile offsets are an error (else select's fallback)
+  kLdc = 4,          // an output of row pitch ldc >= N
+  kStatExact = 8,    // |S| <= 128 K: sum S^2 over a column stays an exact double below 2^53
+};
+
+bool gemm_shape_ok(unsigned f, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
+  return ((f & kPositive) ? M > 0 && N > 0 : M >= 0 && N >= 0) && K > 0 && K % BK == 0 && lda >= K && ldb >= K &&
+         lda % 16 == 0 && ldb % 16 == 0 && M <= 0x7fffffff && N <= 0x7fffffff && K <= 0x7fffffff &&
+         (!(f & kOffsetsErr) || offsets_fit(lda, ldb)) &&
+         (!(f & kStatExact) || (double)M * (128.0 * K) * (128.0 * K) < 9007199254740992.0);
+}
+
+// The arguments every GEMM entry checks
+bool gemm_args_ok(unsigned f, const void* A, const void* B, int64_t lda, int64_t ldb, int64_t ldc, int64_t M, int64_t N,
+                  int64_t K) {
+  return A && B && aligned16(A) && aligned16(B) && gemm_shape_ok(f, M, N, K, lda, ldb) && (!(f & kLdc) || ldc >= N);
+}
+
+// int16 output: ldc % 4 == 0, 8-B aligned; K bytes = 2K ternary products per output, |sum| <= 2K must fit
+bool i16_out_ok(const int16_t* C16, int64_t ldc, int64_t K) {
+  return C16 && ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(C16) & 7) == 0 && 2 * K <= 32767;
+}
+
+// q4 row buffer of a BN-sign form: N % 4 == 0, ldq4 a multiple of 128 bytes covering round_up(N, 256)
+// nibbles, 16-B aligned
+bool bnsign_out_ok(const float* mean, const float* invstd, const uint8_t* q4, int64_t ldq4, int64_t N) {
+  return mean && invstd && q4 && N % 4 == 0 && ldq4 > 0 && ldq4 % 128 == 0 && 2 * ldq4 >= round_up(N, 256) &&
+         aligned16(q4);
+}
+
+// The fields every launch fills; the entries add their epilogue's by name
+GemmParams gemm_params(const void* A, int64_t lda, const void* B, int64_t ldb, const float* bias, int64_t M, int64_t N,
+                       int64_t K) {
+  GemmParams p{};
+  p.A = static_cast<const int8_t*>(A), p.lda = lda;
+  p.B = static_cast<const int8_t*>(B), p.ldb = ldb;
+  p.bias = bias;
+  p.M = (int)M, p.N = (int)N, p.K = (int)K;
+  return p;
+}
+
+inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 }  // namespace
 }  // namespace bnn
@@ -1075,11 +1208,7 @@ BNN_API int bnn_gemm_i8_affine(const int8_t* A, int64_t lda, int64_t a_plane, in
                                const float* a_scale, const float* b_scale, const float* bias,
                                const int64_t* row_off, const int64_t* col_off, double off_mul, float* C,
                                int64_t ldc, int64_t M, int64_t N, int64_t K, void* stream) {
-  const bool cfg_ok = (a_digits == 1 && b_digits == 1) || (a_digits == 3 && b_digits == 1) ||
-                      (a_digits == 3 && b_digits == 3);
-  if (!A || !B || !C || !cfg_ok || M < 0 || N < 0 || K <= 0 || K % BK != 0 || lda < K || ldb < K ||
-      lda % 16 != 0 || ldb % 16 != 0 || ldc < N || !aligned16(A) || !aligned16(B) ||
-      M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff ||
+  if (!C || !cfg_ok(a_digits, b_digits) || !gemm_args_ok(kLdc, A, B, lda, ldb, ldc, M, N, K) ||
       (a_digits > 1 && (a_plane < M * lda || a_plane % 16 != 0)) ||
       (b_digits > 1 && (b_plane < N * ldb || b_plane % 16 != 0))) {
     set_error("bnn_gemm_i8_affine: bad arguments (M=%lld N=%lld K=%lld lda=%lld ldb=%lld digits=%d,%d; "
@@ -1089,69 +1218,57 @@ BNN_API int bnn_gemm_i8_affine(const int8_t* A, int64_t lda, int64_t a_plane, in
     return kErrInval;
   }
   if (M == 0 || N == 0) return 0;
-  GemmParams p{A, B, lda, ldb, a_plane, b_plane, a_scale, b_scale, bias, C, ldc,
-               (int)M, (int)N, (int)K, 0, 0, row_off, col_off, off_mul};
-  p.raster = g_raster;
-  // v2 kernels address a tile's rows with 32-bit per-lane offsets (< 256 rows x ld)
-  if (lda * 256 >= (1LL << 31) || ldb * 256 >= (1LL << 31))
-    return find_variant(a_digits == 1 ? 0 : (b_digits == 1 ? 10 : 20))->fn(p, reinterpret_cast<hipStream_t>(stream));
-  return pick_kernel(a_digits, b_digits, M, N, K)->fn(p, reinterpret_cast<hipStream_t>(stream));
+  GemmParams p = gemm_params(A, lda, B, ldb, bias, M, N, K);
+  p.a_plane = a_plane, p.b_plane = b_plane, p.a_scale = a_scale, p.b_scale = b_scale;
+  p.C = C, p.ldc = ldc;
+  p.row_off = row_off, p.col_off = col_off, p.off_mul = off_mul;
+  p.raster = g_sw.raster;
+  return select(GemmQuery{family_of(a_digits, b_digits), kPlain, M, N, K, lda, ldb})->launch(p, S(stream));
 }
 
-// The statistics form runs the 32x32 (1,1) kernels only: 128x128 tiles (64-row chunks) on grids
-// below 512 of the 256x256 tiles (128-row chunks), as pick_kernel's BK=64 choices
-// bnn_gemm_i8_bnstats_set_tile: 0 = by grid size (above), 1 = always the 128 x 128 tile, 2 = always
-// 256 x 256 (A/B hook; the chunk query and the launch read the same setting)
-static int g_i8_bnstats_tile = 0;
-
-static const Variant* i8_bnstats_variant(int64_t M, int64_t N) {
-  const bool big = ((M + 255) / 256) * ((N + 255) / 256) >= 512;
-  if (g_i8_bnstats_tile != 0) return find_variant(g_i8_bnstats_tile == 2 ? 2 : 1);
-  return find_variant(big ? 2 : 1);
+BNN_API int bnn_gemm_i8(const int8_t* A, int64_t lda, int64_t a_plane, int32_t a_digits,
+                        const int8_t* B, int64_t ldb, int64_t b_plane, int32_t b_digits,
+                        const float* a_scale, const float* b_scale, const float* bias, float* C,
+                        int64_t ldc, int64_t M, int64_t N, int64_t K, void* stream) {
+  return bnn_gemm_i8_affine(A, lda, a_plane, a_digits, B, ldb, b_plane, b_digits, a_scale, b_scale, bias,
+                            nullptr, nullptr, 0.0, C, ldc, M, N, K, stream);
 }
 
 BNN_API int32_t bnn_gemm_i8_bnstats_set_tile(int32_t tile) {
-  if (tile < 0) return g_i8_bnstats_tile;
+  if (tile < 0) return g_sw.bnstats_tile;
   if (tile > 2) return kErrInval;
-  g_i8_bnstats_tile = tile;
+  g_sw.bnstats_tile = tile;
   return 0;
 }
 
+// The statistics form runs the 32x32 BK = 64 (1,1) kernels only: 128 x 128 tiles (64-row chunks) on
+// grids below 512 of the 256 x 256 tiles (128-row chunks), or as bnn_gemm_i8_bnstats_set_tile says
 BNN_API int64_t bnn_gemm_i8_bnstats_chunk(int64_t M, int64_t N) {
-  return i8_bnstats_variant(M, N)->id == 2 ? 128 : 64;
+  return select(GemmQuery{kFam11, kStats, M, N, BK, 0, 0})->chunk;
 }
 
 // The shape bounds of the statistics form (the plain kernel has fallbacks where it has none)
-static bool i8_bnstats_shape_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
-  return M > 0 && N > 0 && K > 0 && K % BK == 0 && lda >= K && ldb >= K && lda % 16 == 0 && ldb % 16 == 0 &&
-         M <= 0x7fffffff && N <= 0x7fffffff && K <= 0x7fffffff && lda * 256 < (1LL << 31) &&
-         ldb * 256 < (1LL << 31) &&
-         // |S| <= 128 K: sum S^2 over a column stays an exact double below 2^53
-         (double)M * (128.0 * K) * (128.0 * K) < 9007199254740992.0;
-}
-
 BNN_API int bnn_gemm_i8_bnstats_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
-  return i8_bnstats_shape_ok(M, N, K, lda, ldb) ? 1 : 0;
+  return gemm_shape_ok(kPositive | kOffsetsErr | kStatExact, M, N, K, lda, ldb) ? 1 : 0;
 }
 
 BNN_API int bnn_gemm_i8_affine_bnstats(const int8_t* A, int64_t lda, const int8_t* B, int64_t ldb,
                                        const float* b_scale, const float* bias, const int64_t* col_off,
                                        double off_mul, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                                        double* stat, int64_t stat_rows, void* stream) {
-  const int64_t chunk = M > 0 ? bnn_gemm_i8_bnstats_chunk(M, N) : 1;
-  if (!A || !B || !C || !stat || !i8_bnstats_shape_ok(M, N, K, lda, ldb) || ldc < N || !aligned16(A) ||
-      !aligned16(B) || stat_rows != (M + chunk - 1) / chunk) {
+  const Inst* r = select(GemmQuery{kFam11, kStats, M, N, K, lda, ldb});
+  const int64_t chunk = M > 0 ? r->chunk : 1;
+  if (!C || !stat || !gemm_args_ok(kPositive | kOffsetsErr | kStatExact | kLdc, A, B, lda, ldb, ldc, M, N, K) ||
+      stat_rows != (M + chunk - 1) / chunk) {
     set_error("bnn_gemm_i8_affine_bnstats: bad arguments (M=%lld N=%lld K=%lld stat_rows=%lld; want %lld)",
               (long long)M, (long long)N, (long long)K, (long long)stat_rows, (long long)((M + chunk - 1) / chunk));
     return kErrInval;
   }
-  GemmParams p{A, B, lda, ldb, 0, 0, nullptr, b_scale, bias, C, ldc,
-               (int)M, (int)N, (int)K, 0, 0, nullptr, col_off, off_mul};
-  p.stat = stat;
-  p.stat_rows = stat_rows;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return i8_bnstats_variant(M, N)->id == 2 ? launch_v2<1, 1, 2, 4, 4, 2, 3, 64, 0, 0, 0, 0, 1>(p, st)
-                                           : launch_v2<1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0, 0, 1>(p, st);
+  GemmParams p = gemm_params(A, lda, B, ldb, bias, M, N, K);
+  p.b_scale = b_scale, p.col_off = col_off, p.off_mul = off_mul;
+  p.C = C, p.ldc = ldc;
+  p.stat = stat, p.stat_rows = stat_rows;
+  return r->launch(p, S(stream));
 }
 
 // bnn_gemm_i8_affine_bnstats writing the s20 form of z (XIn XF 2): z = fl(fl(S * a) + bias) with
@@ -1168,79 +1285,63 @@ BNN_API int bnn_gemm_i8_affine_bnstats_s20(const int8_t* A, int64_t lda, const i
                                            const int64_t* col_off, double off_mul, int64_t k_true, int16_t* Slo,
                                            uint8_t* Shi, int64_t ldc, int64_t M, int64_t N, int64_t K, double* stat,
                                            int64_t stat_rows, const float* b_scale, const float* bias, void* stream) {
-  const int64_t chunk = M > 0 ? bnn_gemm_i8_bnstats_chunk(M, N) : 1;
-  if (!A || !B || !Slo || !Shi || !col_off || !stat || !i8_bnstats_shape_ok(M, N, K, lda, ldb) || ldc < N ||
-      ldc % 4 != 0 || !aligned16(A) || !aligned16(B) || (reinterpret_cast<uintptr_t>(Slo) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(Shi) & 1) != 0 || !bnn_gemm_i8_s20_ok(M, N, K, k_true, off_mul) ||
-      stat_rows != (M + chunk - 1) / chunk) {
+  const Inst* r = select(GemmQuery{kFam11, kS20, M, N, K, lda, ldb});
+  const int64_t chunk = M > 0 ? r->chunk : 1;
+  if (!Slo || !Shi || !col_off || !stat ||
+      !gemm_args_ok(kPositive | kOffsetsErr | kStatExact | kLdc, A, B, lda, ldb, ldc, M, N, K) || ldc % 4 != 0 ||
+      (reinterpret_cast<uintptr_t>(Slo) & 7) != 0 || (reinterpret_cast<uintptr_t>(Shi) & 1) != 0 ||
+      !bnn_gemm_i8_s20_ok(M, N, K, k_true, off_mul) || stat_rows != (M + chunk - 1) / chunk) {
     set_error("bnn_gemm_i8_affine_bnstats_s20: bad arguments (M=%lld N=%lld K=%lld k_true=%lld off_mul=%g "
               "stat_rows=%lld)", (long long)M, (long long)N, (long long)K, (long long)k_true, off_mul,
               (long long)stat_rows);
     return kErrInval;
   }
   // b_scale / bias enter only the statistics (the stored S carries neither)
-  GemmParams p{A, B, lda, ldb, 0, 0, nullptr, b_scale, bias, nullptr, ldc,
-               (int)M, (int)N, (int)K, 0, 0, nullptr, col_off, off_mul};
-  p.stat = stat;
-  p.stat_rows = stat_rows;
-  p.S20lo = Slo;
-  p.S20hi = Shi;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return i8_bnstats_variant(M, N)->id == 2 ? launch_v2<1, 1, 2, 4, 4, 2, 3, 64, 0, 0, 0, 0, 1>(p, st)
-                                           : launch_v2<1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0, 0, 1>(p, st);
-}
-
-BNN_API int bnn_gemm_i8(const int8_t* A, int64_t lda, int64_t a_plane, int32_t a_digits,
-                        const int8_t* B, int64_t ldb, int64_t b_plane, int32_t b_digits,
-                        const float* a_scale, const float* b_scale, const float* bias, float* C,
-                        int64_t ldc, int64_t M, int64_t N, int64_t K, void* stream) {
-  return bnn_gemm_i8_affine(A, lda, a_plane, a_digits, B, ldb, b_plane, b_digits, a_scale, b_scale, bias,
-                            nullptr, nullptr, 0.0, C, ldc, M, N, K, stream);
+  GemmParams p = gemm_params(A, lda, B, ldb, bias, M, N, K);
+  p.b_scale = b_scale, p.col_off = col_off, p.off_mul = off_mul;
+  p.ldc = ldc, p.S20lo = Slo, p.S20hi = Shi;
+  p.stat = stat, p.stat_rows = stat_rows;
+  return r->launch(p, S(stream));
 }
 
 BNN_API int bnn_gemm_fp4(const uint8_t* A, int64_t lda, const uint8_t* B, int64_t ldb, const float* bias,
                          float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, void* stream) {
-  if (!A || !B || !C || M < 0 || N < 0 || K <= 0 || K % BK != 0 || lda < K || ldb < K || lda % 16 != 0 ||
-      ldb % 16 != 0 || ldc < N || !aligned16(A) || !aligned16(B) || M > 0x7fffffff || N > 0x7fffffff ||
-      K > 0x7fffffff || lda * 256 >= (1LL << 31) || ldb * 256 >= (1LL << 31)) {
+  if (!C || !gemm_args_ok(kOffsetsErr | kLdc, A, B, lda, ldb, ldc, M, N, K)) {
     set_error("bnn_gemm_fp4: bad arguments (M=%lld N=%lld K=%lld bytes; K must be a positive multiple of 64 "
               "and below 2^23 bytes)",
               (long long)M, (long long)N, (long long)K);
     return kErrInval;
   }
   if (M == 0 || N == 0) return 0;
-  GemmParams p{reinterpret_cast<const int8_t*>(A), reinterpret_cast<const int8_t*>(B), lda, ldb, 0, 0,
-               nullptr, nullptr, bias, C, ldc, (int)M, (int)N, (int)K, 0, 0, nullptr, nullptr, 0.0};
-  return pick_kernel(0, 0, M, N, K)->fn(p, reinterpret_cast<hipStream_t>(stream));
+  GemmParams p = gemm_params(A, lda, B, ldb, bias, M, N, K);
+  p.C = C, p.ldc = ldc;
+  return select(GemmQuery{kFamFp4, kPlain, M, N, K, lda, ldb})->launch(p, S(stream));
 }
 
 BNN_API int bnn_gemm_fp4_i16(const uint8_t* A, int64_t lda, const uint8_t* B, int64_t ldb, int16_t* C16,
                              int64_t ldc, int64_t M, int64_t N, int64_t K, void* stream) {
-  // K bytes = 2K ternary products per output: |sum| <= 2K must fit int16
-  if (!C16 || ldc % 4 != 0 || (reinterpret_cast<uintptr_t>(C16) & 7) != 0 || 2 * K > 32767) {
+  if (!i16_out_ok(C16, ldc, K)) {
     set_error("bnn_gemm_fp4_i16: bad arguments (ldc=%lld, K=%lld bytes; ldc %% 4 == 0, 8-B aligned output, "
               "2K <= 32767)", (long long)ldc, (long long)K);
     return kErrInval;
   }
-  if (!A || !B || M < 0 || N < 0 || K <= 0 || K % BK != 0 || lda < K || ldb < K || lda % 16 != 0 ||
-      ldb % 16 != 0 || ldc < N || !aligned16(A) || !aligned16(B) || M > 0x7fffffff || N > 0x7fffffff ||
-      lda * 256 >= (1LL << 31) || ldb * 256 >= (1LL << 31)) {
+  if (!gemm_args_ok(kOffsetsErr | kLdc, A, B, lda, ldb, ldc, M, N, K)) {
     set_error("bnn_gemm_fp4_i16: bad arguments (M=%lld N=%lld K=%lld bytes)", (long long)M, (long long)N,
               (long long)K);
     return kErrInval;
   }
   if (M == 0 || N == 0) return 0;
-  GemmParams p{reinterpret_cast<const int8_t*>(A), reinterpret_cast<const int8_t*>(B), lda, ldb, 0, 0,
-               nullptr, nullptr, nullptr, nullptr, ldc, (int)M, (int)N, (int)K, 0, 0, nullptr, nullptr, 0.0, C16};
-  return pick_kernel(0, 0, M, N, K)->fn(p, reinterpret_cast<hipStream_t>(stream));
+  GemmParams p = gemm_params(A, lda, B, ldb, nullptr, M, N, K);
+  p.C16 = C16, p.ldc = ldc;
+  return select(GemmQuery{kFamFp4, kI16, M, N, K, lda, ldb})->launch(p, S(stream));
 }
 
 // The FP4 forward with the next BatchNorm's forward statistics (its own instances of the default
 // choices: 256x256 tiles with 128-row chunks on big grids, 128x128 with 64-row chunks otherwise)
 // 0: no statistics form for this shape (the big-grid BK=64 fallback, K % 128 != 0, would spill)
 BNN_API int64_t bnn_gemm_fp4_bnstats_chunk(int64_t M, int64_t N, int64_t K) {
-  const int id = pick_kernel(0, 0, M, N, K)->id;
-  return id == 31 ? 64 : (id == 36 ? 128 : 0);
+  const Inst* r = select(GemmQuery{kFamFp4, kStats, M, N, K, 0, 0});
+  return r ? r->chunk : 0;
 }
 
 BNN_API int bnn_gemm_fp4_bnstats(const uint8_t* A, int64_t lda, const uint8_t* B, int64_t ldb, const float* bias,
@@ -1251,57 +1352,35 @@ BNN_API int bnn_gemm_fp4_bnstats(const uint8_t* A, int64_t lda, const uint8_t* B
     set_error("bnn_gemm_fp4_bnstats: drop_p must be in [0, 1) (got %g)", (double)drop_p);
     return kErrInval;
   }
-  const int64_t chunk = (M > 0 && N > 0 && K > 0) ? bnn_gemm_fp4_bnstats_chunk(M, N, K) : 1;
-  const bool c16 = C16 != nullptr;
-  if (chunk <= 0 || !A || !B || (C == nullptr) == (C16 == nullptr) || (c16 && bias) || !stat || M <= 0 || N <= 0 || K <= 0 ||
-      K % BK != 0 || lda < K || ldb < K || lda % 16 != 0 || ldb % 16 != 0 || ldc < N || !aligned16(A) ||
-      !aligned16(B) || M > 0x7fffffff || N > 0x7fffffff || lda * 256 >= (1LL << 31) || ldb * 256 >= (1LL << 31) ||
-      (c16 && (ldc % 4 != 0 || (reinterpret_cast<uintptr_t>(C16) & 7) != 0 || 2 * K > 32767)) ||
-      stat_rows != (M + chunk - 1) / chunk) {
+  const Inst* r = select(GemmQuery{kFamFp4, kStats, M, N, K, lda, ldb});
+  if (!r || (C == nullptr) == (C16 == nullptr) || (C16 && bias) || !stat ||
+      !gemm_args_ok(kPositive | kOffsetsErr | kLdc, A, B, lda, ldb, ldc, M, N, K) || (C16 && !i16_out_ok(C16, ldc, K)) ||
+      stat_rows != (M + r->chunk - 1) / r->chunk) {
     set_error("bnn_gemm_fp4_bnstats: bad arguments (M=%lld N=%lld K=%lld bytes, stat_rows=%lld; one of C / C16, "
               "no bias with C16)", (long long)M, (long long)N, (long long)K, (long long)stat_rows);
     return kErrInval;
   }
-  GemmParams p{reinterpret_cast<const int8_t*>(A), reinterpret_cast<const int8_t*>(B), lda, ldb, 0, 0,
-               nullptr, nullptr, bias, C, ldc, (int)M, (int)N, (int)K, 0, 0, nullptr, nullptr, 0.0, C16};
-  p.stat = stat;
-  p.stat_rows = stat_rows;
-  p.stat_bias = zbias;
-  p.stat_drop = make_drop(drop_p, drop_seed);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return chunk == 128 ? launch_v2<1, 1, 2, 4, 4, 2, 2, 128, 2, 0, 1, 1, 1>(p, st)
-                      : launch_v2<1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 1, 0, 1>(p, st);
+  GemmParams p = gemm_params(A, lda, B, ldb, bias, M, N, K);
+  p.C = C, p.C16 = C16, p.ldc = ldc;
+  p.stat = stat, p.stat_rows = stat_rows, p.stat_bias = zbias, p.stat_drop = make_drop(drop_p, drop_seed);
+  return r->launch(p, S(stream));
 }
 
 // ---- BN-sign epilogue entries (frozen-model inference: DESIGN.md §11) -------------------------
-// q4 row buffer of a BN-sign form: N % 4 == 0, ldq4 a multiple of 128 bytes covering round_up(N, 256)
-// nibbles, 16-B aligned
-static bool bnsign_out_ok(const float* mean, const float* invstd, const uint8_t* q4, int64_t ldq4, int64_t N) {
-  return mean && invstd && q4 && N % 4 == 0 && ldq4 > 0 && ldq4 % 128 == 0 && 2 * ldq4 >= round_up(N, 256) &&
-         aligned16(q4);
-}
-
 BNN_API int bnn_gemm_fp4_bnsign(const uint8_t* A, int64_t lda, const uint8_t* B, int64_t ldb, const float* bias,
                                 const float* mean, const float* invstd, const float* gamma, const float* beta,
                                 uint8_t* q4, int64_t ldq4, int64_t M, int64_t N, int64_t K, void* stream) {
-  if (!A || !B || M < 0 || N < 0 || K <= 0 || K % BK != 0 || lda < K || ldb < K || lda % 16 != 0 ||
-      ldb % 16 != 0 || !aligned16(A) || !aligned16(B) || M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff ||
-      lda * 256 >= (1LL << 31) || ldb * 256 >= (1LL << 31) || !bnsign_out_ok(mean, invstd, q4, ldq4, N)) {
+  if (!gemm_args_ok(kOffsetsErr, A, B, lda, ldb, 0, M, N, K) || !bnsign_out_ok(mean, invstd, q4, ldq4, N)) {
     set_error("bnn_gemm_fp4_bnsign: bad arguments (M=%lld N=%lld K=%lld bytes ldq4=%lld; K a positive multiple "
               "of 64, N %% 4 == 0, ldq4 %% 128 == 0 with 2 ldq4 >= round_up(N, 256), 16-B aligned q4)",
               (long long)M, (long long)N, (long long)K, (long long)ldq4);
     return kErrInval;
   }
   if (M == 0) return 0;
-  GemmParams p{reinterpret_cast<const int8_t*>(A), reinterpret_cast<const int8_t*>(B), lda, ldb, 0, 0,
-               nullptr, nullptr, bias, nullptr, 0, (int)M, (int)N, (int)K, 0, 0, nullptr, nullptr, 0.0};
+  GemmParams p = gemm_params(A, lda, B, ldb, bias, M, N, K);
   p.bn_mean = mean, p.bn_invstd = invstd, p.bn_gamma = gamma, p.bn_beta = beta;
   p.Q4 = q4, p.ldq4 = ldq4;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // the tile shapes of bnn_gemm_fp4's default table (variants 36 and 31; 31's also where K % 128 != 0)
-  const bool big = ((M + 255) / 256) * ((N + 255) / 256) >= 512;
-  return (big && K % 128 == 0) ? launch_bnsign<1, 2, 4, 4, 2, 2, 128, 2, 1>(p, st)
-                               : launch_bnsign<1, 2, 2, 2, 2, 3, 64, 0, 0>(p, st);
+  return select(GemmQuery{kFamFp4, kBnSign, M, N, K, lda, ldb})->launch(p, S(stream));
 }
 
 BNN_API int bnn_gemm_i8_affine_bnsign(const int8_t* A, int64_t lda, const int8_t* B, int64_t ldb,
@@ -1309,41 +1388,56 @@ BNN_API int bnn_gemm_i8_affine_bnsign(const int8_t* A, int64_t lda, const int8_t
                                       double off_mul, const float* mean, const float* invstd, const float* gamma,
                                       const float* beta, uint8_t* q4, int64_t ldq4, int64_t M, int64_t N, int64_t K,
                                       void* stream) {
-  if (!A || !B || M < 0 || N < 0 || K <= 0 || K % BK != 0 || lda < K || ldb < K || lda % 16 != 0 ||
-      ldb % 16 != 0 || !aligned16(A) || !aligned16(B) || M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff ||
-      lda * 256 >= (1LL << 31) || ldb * 256 >= (1LL << 31) || !bnsign_out_ok(mean, invstd, q4, ldq4, N)) {
+  if (!gemm_args_ok(kOffsetsErr, A, B, lda, ldb, 0, M, N, K) || !bnsign_out_ok(mean, invstd, q4, ldq4, N)) {
     set_error("bnn_gemm_i8_affine_bnsign: bad arguments (M=%lld N=%lld K=%lld ldq4=%lld; K a positive multiple "
               "of 64, N %% 4 == 0, ldq4 %% 128 == 0 with 2 ldq4 >= round_up(N, 256), 16-B aligned q4)",
               (long long)M, (long long)N, (long long)K, (long long)ldq4);
     return kErrInval;
   }
   if (M == 0) return 0;
-  GemmParams p{A, B, lda, ldb, 0, 0, nullptr, b_scale, bias, nullptr, 0,
-               (int)M, (int)N, (int)K, 0, 0, nullptr, col_off, off_mul};
+  GemmParams p = gemm_params(A, lda, B, ldb, bias, M, N, K);
+  p.b_scale = b_scale, p.col_off = col_off, p.off_mul = off_mul;
   p.bn_mean = mean, p.bn_invstd = invstd, p.bn_gamma = gamma, p.bn_beta = beta;
   p.Q4 = q4, p.ldq4 = ldq4;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // the BK=64 32x32 tiles the pixel GEMM's default table picks at K = 832 (variants 2 and 1)
-  const bool big = ((M + 255) / 256) * ((N + 255) / 256) >= 512;
-  return big ? launch_bnsign<0, 2, 4, 4, 2, 3, 64>(p, st) : launch_bnsign<0, 2, 2, 2, 2, 3, 64>(p, st);
+  return select(GemmQuery{kFam11, kBnSign, M, N, K, lda, ldb})->launch(p, S(stream));
 }
 
+// The label of the plain launch (the timer key of bench.py and the committed profiles).  The int8
+// families' fallback rule as bnn_gemm_i8_affine's, with K the padded row length the caller passes
+// as lda; the FP4 form has no fallback (bnn_gemm_fp4 rejects such shapes).
 BNN_API const char* bnn_gemm_i8_kernel(int32_t a_digits, int32_t b_digits, int64_t M, int64_t N,
                                        int64_t K) {
-  // same fallback rule as bnn_gemm_i8 (K here is the padded row length the caller passes as lda);
-  // the FP4 form has no fallback (bnn_gemm_fp4 rejects such shapes)
-  if (a_digits != 0 && K * 256 >= (1LL << 31)) return find_variant(a_digits == 1 ? 0 : (b_digits == 1 ? 10 : 20))->name;
-  return pick_kernel(a_digits, b_digits, M, N, K)->name;
+  return label(*select(GemmQuery{family_of(a_digits, b_digits), kPlain, M, N, K, K, K}));
 }
 
-// Tuning hook: select a kernel variant for every later bnn_gemm_i8 call in this process
-// (-1 = built-in default).  Not part of the stable ABI contract; used by tools/gemm_sweep.py.
+// Host-only query: the instance the entry of `form` (the epilogue enum: 0 plain, 1 int16, 2 statistics,
+// 3 s20, 4 BN-sign) launches on rows of K bytes under the current switches; a_digits = 0: the FP4
+// entries.  "" where the family has no such entry or the entry refuses the shape.
+BNN_API const char* bnn_gemm_instance(int32_t form, int32_t a_digits, int32_t b_digits, int64_t M, int64_t N,
+                                      int64_t K) {
+  if (form < kPlain || form > kBnSign || (a_digits != 0 && !cfg_ok(a_digits, b_digits))) return "";
+  const int fam = family_of(a_digits, b_digits);
+  const unsigned f = kPositive | (fam != kFamFp4 && form == kPlain ? 0 : kOffsetsErr) |
+                     (fam == kFam11 && (form == kStats || form == kS20) ? kStatExact : 0);
+  if (!gemm_shape_ok(f, M, N, K, K, K) || (form == kI16 && 2 * K > 32767)) return "";
+  const Inst* r = select(GemmQuery{fam, form, M, N, K, K, K});
+  return r ? r->name : "";
+}
+
+// The index-th row of the instance table; "" past either end.
+BNN_API const char* bnn_gemm_instance_at(int32_t index) {
+  return index >= 0 && index < (int)(sizeof(kInst) / sizeof(kInst[0])) ? kInst[index].name : "";
+}
+
+// Tuning hooks (GemmSwitches); not part of the stable ABI contract.  bnn_gemm_set_variant: -1 = the
+// built-in default (tools/gemm_sweep.py).
 BNN_API int bnn_gemm_set_raster(int32_t r) {
-  g_raster = r;
+  g_sw.raster = r;
   return 0;
 }
 
 BNN_API int bnn_gemm_set_variant(int32_t v) {
-  g_variant = v;
+  g_sw.variant = v;
   return 0;
 }
+

@@ -247,15 +247,28 @@ int bnn_gemm_i8_affine_bnsign(const int8_t* A, int64_t lda, const int8_t* B, int
                               uint8_t* q4, int64_t ldq4, int64_t M, int64_t N, int64_t K, bnn_stream_t stream);
 
 /* Tuning hook (not part of the stable contract): select the bnn_gemm_i8 kernel variant for all
- * later calls in this process; -1 restores the built-in default table (tools/gemm_sweep.py). */
+ * later calls in this process; -1 restores the built-in default table (tools/gemm_sweep.py).  The
+ * variant is added to the launch's family base (0 / 10 / 20, FP4 30); an id that is not a variant of
+ * that family is answered by the family's variant 1. */
 int bnn_gemm_set_variant(int32_t variant);
 /* Tuning hook: tile order of later bnn_gemm_i8_affine calls (0 = grouped raster, 1 = row-major). */
 int bnn_gemm_set_raster(int32_t raster);
-/* Name of the kernel instance bnn_gemm_i8 launches for this configuration (as rocprofv3 lists
- * it), so host-side HIP-event timings can be matched with profiles; a_digits = b_digits = 0
- * names the bnn_gemm_fp4 kernel (K in bytes). */
+/* Label of the kernel bnn_gemm_i8 launches for this configuration, so host-side HIP-event timings
+ * can be matched with profiles: a prefix key of the name rocprofv3 lists (up to a "," or the ">"),
+ * not the instance itself; a_digits = 0 labels the bnn_gemm_fp4 kernel (K in bytes). */
 const char* bnn_gemm_i8_kernel(int32_t a_digits, int32_t b_digits, int64_t M, int64_t N,
                                int64_t K);
+/* Host-only: the instance ("kernel<template arguments>") the entry of `form` launches on this
+ * shape, rows of K bytes, under the current switches.  form 0 = plain (bnn_gemm_i8[_affine],
+ * bnn_gemm_fp4), 1 = int16 output (bnn_gemm_fp4_i16), 2 = statistics (bnn_gemm_i8_affine_bnstats,
+ * bnn_gemm_fp4_bnstats), 3 = s20 (bnn_gemm_i8_affine_bnstats_s20), 4 = BN-sign (bnn_gemm_*_bnsign);
+ * a_digits = 0: the FP4 entries.  "" where there is no such entry or it refuses the shape.  The same
+ * decision the launch makes, so it names what runs where the label does not (the statistics forms
+ * of the pixel GEMM under bnn_gemm_i8_bnstats_set_tile, or with K % 128 == 0 on a big grid). */
+const char* bnn_gemm_instance(int32_t form, int32_t a_digits, int32_t b_digits, int64_t M, int64_t N,
+                              int64_t K);
+/* Host-only: the index-th instance bnn_gemm.hip can launch; "" past either end of the list. */
+const char* bnn_gemm_instance_at(int32_t index);
 
 /* ---------------------------------------------------------------- fp32 x ternary on the FP6 MFMA
  * The fp32 operand of the backward GEMMs (dY) and of the first layer's forward (pixels) as FOUR

@@ -35,6 +35,14 @@ def host(t):
     return t.detach().cpu().numpy()
 
 
+def gemm_instances(lib):
+    """Every instance bnn_gemm.hip can launch (bnn_gemm_instance_at)."""
+    out = []
+    while lib.bnn_gemm_instance_at(len(out)):
+        out.append(lib.bnn_gemm_instance_at(len(out)).decode())
+    return out
+
+
 def run_linear(F, x, w, b, dy, binarize, backend="mfma"):
     xt = dev(x).requires_grad_(True)
     wt = dev(w).requires_grad_(True)
@@ -121,10 +129,13 @@ def test_every_fp4_variant_is_exact(F, M, N, K):
     x4, _ = F.sign_pack_fp4(dev(x))
     w4, _ = F.sign_pack_fp4(dev(w))
     names = set()
+    listed = gemm_instances(_lib.lib())
     try:
         for v in range(0, 7):
             _lib.call("bnn_gemm_set_variant", v)
             name = F.gemm_kernel_name(0, 0, M, N, x4.shape[1])
+            inst = _lib.lib().bnn_gemm_instance(0, 0, 0, M, N, x4.shape[1]).decode()
+            assert inst in listed and inst.startswith(("gemm_fp4_k<", "gemm_fp4_h_k<")), (v, inst)
             if name in names:
                 continue
             names.add(name)
@@ -791,11 +802,16 @@ def test_every_gemm_variant_is_exact(F, cfg, M, N, K):
     At = dev(A if da == 3 else A[0])
     Bt = dev(B if db == 3 else B[0])
     names = set()
+    listed = gemm_instances(_lib.lib())
+    # 10: (1,1) base + 10 is a (3,1) row, so an unknown id here -- row 1 answers and the result is exact
+    foreign = [10] if cfg == (1, 1) and (M, N, K) == (64, 64, 64) else []
     try:
-        for v in range(0, 10):
+        for v in list(range(0, 10)) + foreign:
             _lib.call("bnn_gemm_set_variant", v)
             name = F.gemm_kernel_name(da, db, M, N, K)
-            if name in names:
+            inst = _lib.lib().bnn_gemm_instance(0, da, db, M, N, K).decode()
+            assert inst in listed and inst.startswith((f"gemm_i8_k<{da}, {db}, ", f"gemm_i8_v2_k<{da}, {db}, ")), (v, inst)
+            if name in names and v not in foreign:
                 continue
             names.add(name)
             C = host(F.gemm_i8(At, da, Bt, db, M, N, a_scale=dev(sa) if sa is not None else None,

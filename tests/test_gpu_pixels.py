@@ -308,6 +308,31 @@ def test_pixels_gemm_bn_forward_statistics(F, t10k, M, N, normalize):
     float64 chunk sums / M2 of z = a*(S + s0*R) + b computed from the exact integer sums; the
     final (bnn_bn_fwd_final_parts) within 1e-6 of bnn_bn_fwd_train's statistics of the stored z
     (which differ only by z's fp32 rounding), running statistics likewise."""
+    check_pixels_statistics(F, t10k, M, N, normalize)
+
+
+BST_ROW = {1: "gemm_i8_v2_k<1, 1, 2, 2, 2, 2, 3, 64, 0, 0, 0, 1>",     # the 128 x 128 tile, 64-row chunks
+           2: "gemm_i8_v2_k<1, 1, 2, 4, 4, 2, 3, 64, 0, 0, 0, 1>"}     # the 256 x 256 tile, 128-row chunks
+
+
+@pytest.mark.parametrize("tile", [1, 2])
+@pytest.mark.parametrize("M,N", [(1000, 3072), (77, 200)])
+def test_pixels_gemm_bn_forward_statistics_forced_tile(F, t10k, M, N, tile):
+    """The same under bnn_gemm_i8_bnstats_set_tile 1 and 2: the chunk comes from the query, and the
+    launch runs the statistics row of the forced tile.  (77, 200) on the 256 x 256 tile: one partial
+    chunk row, a ragged N."""
+    from bnn_amd import _lib as L
+    prev = L.lib().bnn_gemm_i8_bnstats_set_tile(-1)
+    try:
+        L.call("bnn_gemm_i8_bnstats_set_tile", tile)
+        assert L.lib().bnn_gemm_instance(2, 1, 1, M, N, 832).decode() == BST_ROW[tile]
+        assert L.lib().bnn_gemm_i8_bnstats_chunk(M, N) == 64 * tile
+        check_pixels_statistics(F, t10k, M, N, None)
+    finally:
+        L.call("bnn_gemm_i8_bnstats_set_tile", prev)
+
+
+def check_pixels_statistics(F, t10k, M, N, normalize):
     from bnn_amd import _lib as L
     rng = np.random.default_rng(M + N)
     u = t10k[rng.integers(0, 10000, M)]

@@ -35,7 +35,8 @@ def main():
             name = L.lib().bnn_gemm_i8_kernel(1, 1, M, N, K).decode()
             t = timeit(lambda: L.call("bnn_gemm_i8_affine", L.ptr(A), K, 0, 1, L.ptr(B), K, 0, 1, None, None, None,
                                       None, None, 0.0, L.ptr(C), N, M, N, K, L.stream()))
-            print(f"gemm {M}x{N}x{K} {name}: {t:.0f} us  ({2 * M * N * K / t / 1e6:.0f} TOPS)", flush=True)
+            inst = L.lib().bnn_gemm_instance(0, 1, 1, M, N, K).decode()
+            print(f"gemm {M}x{N}x{K} {name} [{inst}]: {t:.0f} us  ({2 * M * N * K / t / 1e6:.0f} TOPS)", flush=True)
             del A, B
 
 

@@ -46,7 +46,8 @@ def main():
             torch.cuda.synchronize()
             res.setdefault(v, []).append(s.elapsed_time(e) / 5)
             name = L.lib().bnn_gemm_i8_kernel(1, 1, M, N, Kp).decode()
-            print(f"round {rnd} v{v} {name}: {s.elapsed_time(e) / 5 * 1e3:.0f} us equal={ok}", flush=True)
+            inst = L.lib().bnn_gemm_instance(0, 1, 1, M, N, Kp).decode()
+            print(f"round {rnd} v{v} {name} [{inst}]: {s.elapsed_time(e) / 5 * 1e3:.0f} us equal={ok}", flush=True)
     L.call("bnn_gemm_set_variant", -1)
     for v, t in res.items():
         print(f"v{v}: min {min(t) * 1e3:.0f} us")
