@@ -76,7 +76,7 @@ def timing(timer):
 
 @contextlib.contextmanager
 def _timed(name, ops=0.0, nbytes=0.0):
-    if _TIMER is None:
+    if _TIMER is None or name is None:          # None: a launch that is not timed
         yield
         return
     s = torch.cuda.Event(enable_timing=True)
@@ -393,41 +393,70 @@ def adam_schedule(lr, beta1, beta2, step0, n, device):
 _ADAM_TILE256 = [os.environ.get("BNN_ADAM_TILE256")]
 
 
-def adam_clamp_pack_(p, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-8,
-                     grad_scale=1.0, clamp=True, sched=None, ctr=None):
-    """bnn_adam_clamp on a 2-D latent weight that also rewrites its cached packed operands (see
-    packed_weight).  Returns False (nothing done) when ``p`` has no valid cache."""
+def _flag(v):
+    return int(bool(v))
+
+
+def _contiguous(fn, *ts):
+    for t in ts:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{fn}: tensors must be contiguous")
+
+
+def _check_flips(flips, p):
+    if flips is not None and (flips.dtype != torch.int64 or flips.numel() < 1 or flips.device != p.device):
+        raise ValueError("flips: an int64 tensor on the weight's device (its first element is the counter)")
+
+
+def _packed_update(fn, label, entry, p, tensors, streams, scalars, flips=None):
+    """One fused update + re-pack of a 2-D weight whose packed operands are cached (packed_weight):
+    ``entry``(p, *tensors, N, K, *scalars, <the cached operands>), timed as ``label`` over ``streams`` fp32
+    streams and the operands.  Returns False (nothing done) when ``p`` has no valid cache."""
     if _ADAM_TILE256[0] is not None:
         L.call("bnn_adam_pack_set_tile256", int(_ADAM_TILE256[0] != "0"))
         _ADAM_TILE256[0] = None
     ent = getattr(p, "_bnn_pack", None)
     if ent is None or ent["key"] != _pack_key(p) or p.dim() != 2:
         return False
-    _check(p, grad, exp_avg, exp_avg_sq)
-    for t in (p, grad, exp_avg, exp_avg_sq):
-        if not t.is_contiguous():
-            raise ValueError("adam_clamp_pack_: tensors must be contiguous")
+    _check(p, *tensors)
+    _check_flips(flips, p)
+    _contiguous(fn, p, *tensors)
     N, K = p.shape
     q, qt = ent["q"], ent["qt"]
-    nbytes = 28 * N * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
-    tail = (1 if ent["fmt"] == "fp4" else 0, q, q.shape[1] if q is not None else 0,
-            qt, qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
-    with _timed("sign_pack_tile_k<adam>", 0, nbytes):
-        if sched is not None:
-            L.call("bnn_adam_clamp_pack_sched", p, grad, exp_avg, exp_avg_sq, N, K, float(beta1), float(beta2),
-                   float(eps), sched, ctr, float(grad_scale), int(bool(clamp)), *tail)
-        else:
-            L.call("bnn_adam_clamp_pack", p, grad, exp_avg, exp_avg_sq, N, K, float(lr), float(beta1), float(beta2),
-                   float(eps), int(step), float(grad_scale), int(bool(clamp)), *tail)
+    nbytes = 4 * streams * N * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
+    with _timed(label, 0, nbytes):
+        L.call(entry, p, *tensors, N, K, *scalars, 1 if ent["fmt"] == "fp4" else 0, q,
+               q.shape[1] if q is not None else 0, qt, qt.shape[1] if qt is not None else 0,
+               _QT_CODE[ent["qt_fmt"]], L.stream())
     _bump(p)
     ent["key"] = _pack_key(p)           # the operands just written match the bumped version
     return True
 
 
-def _sgd_omd(dampening):
-    """The multiplier 1 - dampening that libbnn's SGD entries take, formed in double as torch forms
-    its ``alpha`` (the C side casts it to float)."""
-    return 1.0 - float(dampening)
+def _adam_entry(base, step, lr, beta1, beta2, eps, grad_scale, clamp, sched, ctr):
+    """(entry, scalar arguments) of an Adam launch: the per-launch form, or with ``sched`` the device-step one."""
+    if sched is not None:
+        return base + "_sched", (float(beta1), float(beta2), float(eps), sched, ctr, float(grad_scale), _flag(clamp))
+    return base, (float(lr), float(beta1), float(beta2), float(eps), int(step), float(grad_scale), _flag(clamp))
+
+
+def adam_clamp_pack_(p, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-8,
+                     grad_scale=1.0, clamp=True, sched=None, ctr=None):
+    """bnn_adam_clamp on a 2-D latent weight that also rewrites its cached packed operands (see
+    packed_weight).  Returns False (nothing done) when ``p`` has no valid cache."""
+    entry, scalars = _adam_entry("bnn_adam_clamp_pack", step, lr, beta1, beta2, eps, grad_scale, clamp, sched, ctr)
+    return _packed_update("adam_clamp_pack_", "sign_pack_tile_k<adam>", entry, p, (grad, exp_avg, exp_avg_sq), 7,
+                          scalars)
+
+
+def _sgd_hyper(lr, momentum, dampening, weight_decay, nesterov):
+    """The scalar arguments every SGD entry begins with.  The multiplier 1 - dampening is formed in double as
+    torch forms its ``alpha`` (the C side casts it to float)."""
+    return float(lr), float(momentum), 1.0 - float(dampening), float(weight_decay), _flag(nesterov)
+
+
+def _sgd_streams(buf, first):
+    return 3 if buf is None else (4 if first else 5)
 
 
 def sgd_clamp_pack_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
@@ -436,60 +465,17 @@ def sgd_clamp_pack_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=
     packed_weight), as adam_clamp_pack_ does for Adam.  ``buf`` is the momentum buffer (None exactly
     when momentum is 0); ``first``: it holds nothing yet and is only written.  Returns False
     (nothing done) when ``p`` has no valid cache."""
-    if _ADAM_TILE256[0] is not None:
-        L.call("bnn_adam_pack_set_tile256", int(_ADAM_TILE256[0] != "0"))
-        _ADAM_TILE256[0] = None
-    ent = getattr(p, "_bnn_pack", None)
-    if ent is None or ent["key"] != _pack_key(p) or p.dim() != 2:
-        return False
-    _check(p, grad, buf)
-    for t in (p, grad, buf):
-        if t is not None and not t.is_contiguous():
-            raise ValueError("sgd_clamp_pack_: tensors must be contiguous")
-    N, K = p.shape
-    q, qt = ent["q"], ent["qt"]
-    streams = 3 if buf is None else (4 if first else 5)
-    nbytes = 4 * streams * N * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
-    with _timed("sign_pack_tile_k<sgd>", 0, nbytes):
-        L.call("bnn_sgd_clamp_pack", p, grad, buf, N, K, float(lr), float(momentum), _sgd_omd(dampening),
-               float(weight_decay), int(bool(nesterov)), int(bool(first)), float(grad_scale), int(bool(clamp)),
-               1 if ent["fmt"] == "fp4" else 0, q, q.shape[1] if q is not None else 0, qt,
-               qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
-    _bump(p)
-    ent["key"] = _pack_key(p)           # the operands just written match the bumped version
-    return True
-
-
-def _check_flips(flips, p):
-    if flips is not None and (flips.dtype != torch.int64 or flips.numel() < 1 or flips.device != p.device):
-        raise ValueError("flips: an int64 tensor on the weight's device (its first element is the counter)")
+    return _packed_update("sgd_clamp_pack_", "sign_pack_tile_k<sgd>", "bnn_sgd_clamp_pack", p, (grad, buf),
+                          _sgd_streams(buf, first), (*_sgd_hyper(lr, momentum, dampening, weight_decay, nesterov),
+                                                     _flag(first), float(grad_scale), _flag(clamp)))
 
 
 def bop_pack_(w, grad, m, gamma, threshold, grad_scale=1.0, flips=None):
     """bnn_bop on a 2-D binarized weight that also rewrites its cached packed operands (see
     packed_weight), as adam_clamp_pack_ does for Adam.  Returns False (nothing done) when ``w`` has no
     valid cache."""
-    if _ADAM_TILE256[0] is not None:
-        L.call("bnn_adam_pack_set_tile256", int(_ADAM_TILE256[0] != "0"))
-        _ADAM_TILE256[0] = None
-    ent = getattr(w, "_bnn_pack", None)
-    if ent is None or ent["key"] != _pack_key(w) or w.dim() != 2:
-        return False
-    _check(w, grad, m)
-    _check_flips(flips, w)
-    for t in (w, grad, m):
-        if not t.is_contiguous():
-            raise ValueError("bop_pack_: tensors must be contiguous")
-    N, K = w.shape
-    q, qt = ent["q"], ent["qt"]
-    nbytes = 20 * N * K + (q.numel() if q is not None else 0) + (qt.numel() if qt is not None else 0)
-    with _timed("sign_pack_tile_k<bop>", 0, nbytes):
-        L.call("bnn_bop_pack", w, grad, m, N, K, float(gamma), float(threshold), float(grad_scale), flips,
-               1 if ent["fmt"] == "fp4" else 0, q, q.shape[1] if q is not None else 0, qt,
-               qt.shape[1] if qt is not None else 0, _QT_CODE[ent["qt_fmt"]], L.stream())
-    _bump(w)
-    ent["key"] = _pack_key(w)           # the operands just written match the bumped version
-    return True
+    return _packed_update("bop_pack_", "sign_pack_tile_k<bop>", "bnn_bop_pack", w, (grad, m), 5,
+                          (float(gamma), float(threshold), float(grad_scale), flips), flips)
 
 
 # ----------------------------------------------------------------------------- (2) GEMMs
@@ -1794,21 +1780,16 @@ def _bump(p):
     torch.autograd.graph.increment_version(p)
 
 
-def adam_clamp_(p, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-8,
-                grad_scale=1.0, clamp=True, sched=None, ctr=None):
-    """In-place fused Adam (torch formula) + clamp to [-1, 1] on a latent weight."""
-    _check(p, grad, exp_avg, exp_avg_sq)
+def _flat_update(fn, label, entry, p, tensors, streams, scalars, flips=None):
+    """One in-place update of a flat tensor: ``entry``(p, *tensors, numel, *scalars), timed as ``label``
+    (None: not timed) over ``streams`` fp32 streams."""
+    _check(p, *tensors)
+    _check_flips(flips, p)
     invalidate_packed(p)        # a raw in-place write: cached packed operands would go stale
-    for t in (p, grad, exp_avg, exp_avg_sq):
-        if not t.is_contiguous():
-            raise ValueError("adam_clamp_: tensors must be contiguous")
+    _contiguous(fn, p, *tensors)
     _bump(p)
-    if sched is not None:
-        L.call("bnn_adam_clamp_sched", p, grad, exp_avg, exp_avg_sq, p.numel(), float(beta1), float(beta2), float(eps),
-               sched, ctr, float(grad_scale), int(bool(clamp)), L.stream())
-        return
-    L.call("bnn_adam_clamp", p, grad, exp_avg, exp_avg_sq, p.numel(), float(lr), float(beta1), float(beta2), float(eps),
-           int(step), float(grad_scale), int(bool(clamp)), L.stream())
+    with _timed(label, 0, 4 * streams * p.numel()):
+        L.call(entry, p, *tensors, p.numel(), *scalars, L.stream())
 
 
 ADAM_MULTI_MAX = 16     # tensors per bnn_adam_clamp_multi launch
@@ -1825,22 +1806,37 @@ def _multi_arrays(chunk, ntensors, *ints):
     return arr + [(ct * k)(*vals) for ct, vals in ints]
 
 
+def _multi_update(fn, label, entry, items, ntensors, ints, scalars, streams=None):
+    """``entry`` over items = [(p, <ntensors - 1 more tensors>, <one value per (ctype, cast) of ``ints``>)], one
+    launch per ADAM_MULTI_MAX of them: ``entry``(count, <_multi_arrays>, *scalars); with a ``label``, timed under
+    it over streams(item) fp32 streams per element."""
+    for i in range(0, len(items), ADAM_MULTI_MAX):
+        chunk = items[i:i + ADAM_MULTI_MAX]
+        for it in chunk:
+            _check(*it[:ntensors])
+            invalidate_packed(it[0])
+            _contiguous(fn, *it[:ntensors])
+            _bump(it[0])
+        nbytes = sum(4 * it[0].numel() * streams(it) for it in chunk) if label else 0
+        vp = _multi_arrays(chunk, ntensors, *[(ct, [cast(it[ntensors + j]) for it in chunk])
+                                              for j, (ct, cast) in enumerate(ints)])
+        with _timed(label, 0, nbytes):
+            L.call(entry, len(chunk), *vp, *scalars, L.stream())
+
+
+def adam_clamp_(p, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-8,
+                grad_scale=1.0, clamp=True, sched=None, ctr=None):
+    """In-place fused Adam (torch formula) + clamp to [-1, 1] on a latent weight."""
+    entry, scalars = _adam_entry("bnn_adam_clamp", step, lr, beta1, beta2, eps, grad_scale, clamp, sched, ctr)
+    _flat_update("adam_clamp_", None, entry, p, (grad, exp_avg, exp_avg_sq), 7, scalars)
+
+
 def adam_clamp_multi_(items, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, sched=None, ctr=None):
     """adam_clamp_ on several tensors in one launch per ADAM_MULTI_MAX: items = [(p, grad, exp_avg,
     exp_avg_sq, step, clamp)], bit-identical per tensor to adam_clamp_ (bnn_adam_clamp_multi)."""
-    for i in range(0, len(items), ADAM_MULTI_MAX):
-        chunk = items[i:i + ADAM_MULTI_MAX]
-        for p, g, m, v, _, _ in chunk:
-            _check(p, g, m, v)
-            invalidate_packed(p)
-            for t in (p, g, m, v):
-                if not t.is_contiguous():
-                    raise ValueError("adam_clamp_multi_: tensors must be contiguous")
-            _bump(p)
-        vp = _multi_arrays(chunk, 4, (ctypes.c_int64, [int(it[4]) for it in chunk]),
-                           (ctypes.c_int32, [int(bool(it[5])) for it in chunk]))
-        L.call("bnn_adam_clamp_multi", len(chunk), *vp, float(lr), float(beta1), float(beta2), float(eps), sched, ctr,
-               float(grad_scale), L.stream())
+    _multi_update("adam_clamp_multi_", None, "bnn_adam_clamp_multi", items, 4,
+                  ((ctypes.c_int64, int), (ctypes.c_int32, _flag)),
+                  (float(lr), float(beta1), float(beta2), float(eps), sched, ctr, float(grad_scale)))
 
 
 def sgd_clamp_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
@@ -1848,37 +1844,18 @@ def sgd_clamp_(p, grad, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, 
     """In-place fused SGD (torch.optim.SGD's formula, bit-identical to its CPU fp32 result) + clamp to
     [-1, 1] on a latent weight.  ``buf``: the momentum buffer, None exactly when momentum is 0;
     ``first``: the buffer holds nothing yet (it becomes the gradient, torch's clone rule)."""
-    _check(p, grad, buf)
-    invalidate_packed(p)        # a raw in-place write: cached packed operands would go stale
-    for t in (p, grad, buf):
-        if t is not None and not t.is_contiguous():
-            raise ValueError("sgd_clamp_: tensors must be contiguous")
-    _bump(p)
-    with _timed("sgd_clamp_k", 0, 4 * p.numel() * (3 if buf is None else (4 if first else 5))):
-        L.call("bnn_sgd_clamp", p, grad, buf, p.numel(), float(lr), float(momentum), _sgd_omd(dampening),
-               float(weight_decay), int(bool(nesterov)), int(bool(first)), float(grad_scale), int(bool(clamp)),
-               L.stream())
+    _flat_update("sgd_clamp_", "sgd_clamp_k", "bnn_sgd_clamp", p, (grad, buf), _sgd_streams(buf, first),
+                 (*_sgd_hyper(lr, momentum, dampening, weight_decay, nesterov), _flag(first), float(grad_scale),
+                  _flag(clamp)))
 
 
 def sgd_clamp_multi_(items, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0):
     """sgd_clamp_ on several tensors in one launch per ADAM_MULTI_MAX: items = [(p, grad, buf, first,
     clamp)] (buf None when momentum is 0), bit-identical per tensor to sgd_clamp_ (bnn_sgd_clamp_multi)."""
-    for i in range(0, len(items), ADAM_MULTI_MAX):
-        chunk = items[i:i + ADAM_MULTI_MAX]
-        nbytes = 0
-        for p, g, b, first, _ in chunk:
-            _check(p, g, b)
-            invalidate_packed(p)
-            for t in (p, g, b):
-                if t is not None and not t.is_contiguous():
-                    raise ValueError("sgd_clamp_multi_: tensors must be contiguous")
-            _bump(p)
-            nbytes += 4 * p.numel() * (3 if b is None else (4 if first else 5))
-        vp = _multi_arrays(chunk, 3, (ctypes.c_int32, [int(bool(it[3])) for it in chunk]),
-                           (ctypes.c_int32, [int(bool(it[4])) for it in chunk]))
-        with _timed("sgd_clamp_multi_k", 0, nbytes):
-            L.call("bnn_sgd_clamp_multi", len(chunk), *vp, float(lr), float(momentum), _sgd_omd(dampening),
-                   float(weight_decay), int(bool(nesterov)), float(grad_scale), L.stream())
+    _multi_update("sgd_clamp_multi_", "sgd_clamp_multi_k", "bnn_sgd_clamp_multi", items, 3,
+                  ((ctypes.c_int32, _flag), (ctypes.c_int32, _flag)),
+                  (*_sgd_hyper(lr, momentum, dampening, weight_decay, nesterov), float(grad_scale)),
+                  lambda it: _sgd_streams(it[2], it[3]))
 
 
 def bop_(w, grad, m, gamma, threshold, grad_scale=1.0, flips=None):
@@ -1886,15 +1863,8 @@ def bop_(w, grad, m, gamma, threshold, grad_scale=1.0, flips=None):
     ``gamma``, ``w`` <- its sign as exactly +-1, flipped where the average exceeds ``threshold`` against it.
     ``flips`` (an int64 device tensor, optional) gets the number of flipped elements added to its first
     element."""
-    _check(w, grad, m)
-    _check_flips(flips, w)
-    invalidate_packed(w)        # a raw in-place write: cached packed operands would go stale
-    for t in (w, grad, m):
-        if not t.is_contiguous():
-            raise ValueError("bop_: tensors must be contiguous")
-    _bump(w)
-    with _timed("bop_k", 0, 20 * w.numel()):
-        L.call("bnn_bop", w, grad, m, w.numel(), float(gamma), float(threshold), float(grad_scale), flips, L.stream())
+    _flat_update("bop_", "bop_k", "bnn_bop", w, (grad, m), 5,
+                 (float(gamma), float(threshold), float(grad_scale), flips), flips)
 
 
 # ----------------------------------------------------------------------------- BatchNorm1d (+ Hardtanh)

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "bnn_common.h"
+#include "bnn_update.h"   // the update policies U that sign_pack_tile_k / adam_pack_fp4_k fuse
 
 namespace bnn {
 namespace {
@@ -53,127 +54,6 @@ struct ColAffine {
   const float* gamma;  // nullable
   const float* beta;   // nullable
   int vec;             // all four 16-B aligned -> float4 parameter loads
-};
-
-// The latent update a packing kernel fuses: an update policy U says which element runs and which state
-// streams it loads and stores, and is all that sign_pack_tile_k / adam_pack_fp4_k know of an optimizer.
-// The weight and the policy's streams share one row-major layout: prow = the weight's row, off = that
-// row's offset in the streams, k = the column.
-//   U::Args                  the kernel argument (gradient, state streams, hyper-parameters)
-//   U::resolve(a)            the arguments of this launch (device-step table lookups)
-//   U::run4(prow, off, k, a, acc) updates the weights prow[k .. k+3] and their state in place (16-B
-//                            aligned float4 runs),
-//   U::run1(prow, off, k, a, acc) or one element; both return the new weight(s)
-//   U::Acc                   what a thread accumulates over all of its runs (Bop: its flip count), and
-//   U::finish(acc, a)        what becomes of it, called once by every thread when its last run is done;
-//                            NoAcc = nothing: an empty struct and an empty call, which compile to no code
-//   U::null(a), U::vec(a)    host: a needed pointer is null / every stream is 16-B aligned
-// NoUpdate marks the kernels that only pack.
-struct NoAcc {
-  struct Acc {};
-  template <class A>
-  static __device__ __forceinline__ void finish(const Acc&, const A&) {}
-};
-
-struct NoUpdate : NoAcc {
-  struct Args {};
-};
-
-// Adam + clamp (adam_elem): g, m, v read; m, v written -- 7 fp32 streams with p
-struct AdamUpdate : NoAcc {
-  using Args = AdamArgs;
-  static __device__ __forceinline__ Args resolve(const Args& a) { return adam_resolve(a); }
-  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a, Acc&) {
-    const float4 pv = *reinterpret_cast<const float4*>(prow + k);
-    const float4 gv = *reinterpret_cast<const float4*>(a.g + off + k);
-    float4 mv = *reinterpret_cast<const float4*>(a.m + off + k);
-    float4 vv = *reinterpret_cast<const float4*>(a.v + off + k);
-    float4 np;
-    np.x = adam_elem(pv.x, gv.x, mv.x, vv.x, a);
-    np.y = adam_elem(pv.y, gv.y, mv.y, vv.y, a);
-    np.z = adam_elem(pv.z, gv.z, mv.z, vv.z, a);
-    np.w = adam_elem(pv.w, gv.w, mv.w, vv.w, a);
-    *reinterpret_cast<float4*>(prow + k) = np;
-    *reinterpret_cast<float4*>(a.m + off + k) = mv;
-    *reinterpret_cast<float4*>(a.v + off + k) = vv;
-    return np;
-  }
-  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a, Acc&) {
-    float mm = a.m[off + k], vv = a.v[off + k];
-    const float np = adam_elem(prow[k], a.g[off + k], mm, vv, a);
-    prow[k] = np;
-    a.m[off + k] = mm;
-    a.v[off + k] = vv;
-    return np;
-  }
-  static bool null(const Args& a) { return !a.g || !a.m || !a.v; }
-  static bool vec(const Args& a) { return aligned16(a.g) && aligned16(a.m) && aligned16(a.v); }
-};
-
-// SGD + clamp (sgd_elem).  BUF = what happens to the momentum buffer: 0 none (momentum 0: g read, 3 fp32
-// streams with p), 1 written only (a parameter's first step: 4 streams), 2 read and written (5 streams).
-// A template parameter, not a branch on a.mu / a.first: the loads of an unrolled run stay together.
-template <int BUF>
-struct SgdUpdate : NoAcc {
-  using Args = SgdArgs;
-  static __device__ __forceinline__ Args resolve(const Args& a) { return a; }
-  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a, Acc&) {
-    const float4 pv = *reinterpret_cast<const float4*>(prow + k);
-    const float4 gv = *reinterpret_cast<const float4*>(a.g + off + k);
-    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (BUF == 2) bv = *reinterpret_cast<const float4*>(a.buf + off + k);
-    float4 np;
-    np.x = sgd_elem(pv.x, gv.x, bv.x, a);
-    np.y = sgd_elem(pv.y, gv.y, bv.y, a);
-    np.z = sgd_elem(pv.z, gv.z, bv.z, a);
-    np.w = sgd_elem(pv.w, gv.w, bv.w, a);
-    *reinterpret_cast<float4*>(prow + k) = np;
-    if constexpr (BUF != 0) *reinterpret_cast<float4*>(a.buf + off + k) = bv;
-    return np;
-  }
-  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a, Acc&) {
-    float bb = 0.f;
-    if constexpr (BUF == 2) bb = a.buf[off + k];
-    const float np = sgd_elem(prow[k], a.g[off + k], bb, a);
-    prow[k] = np;
-    if constexpr (BUF != 0) a.buf[off + k] = bb;
-    return np;
-  }
-  static bool null(const Args& a) { return !a.g || (BUF != 0 && !a.buf); }
-  static bool vec(const Args& a) { return aligned16(a.g) && (BUF == 0 || aligned16(a.buf)); }
-};
-
-// Bop (bop_elem): g, m read; m written -- 5 fp32 streams with w.  Acc = the thread's flip count, added to
-// a.flips once per wave by finish (bop_flush).
-struct BopUpdate {
-  using Args = BopArgs;
-  struct Acc {
-    int n = 0;
-  };
-  static __device__ __forceinline__ Args resolve(const Args& a) { return a; }
-  static __device__ __forceinline__ float4 run4(float* prow, int64_t off, int64_t k, const Args& a, Acc& acc) {
-    const float4 pv = *reinterpret_cast<const float4*>(prow + k);
-    const float4 gv = *reinterpret_cast<const float4*>(a.g + off + k);
-    float4 mv = *reinterpret_cast<const float4*>(a.m + off + k);
-    float4 np;
-    np.x = bop_elem(pv.x, gv.x, mv.x, a, acc.n);
-    np.y = bop_elem(pv.y, gv.y, mv.y, a, acc.n);
-    np.z = bop_elem(pv.z, gv.z, mv.z, a, acc.n);
-    np.w = bop_elem(pv.w, gv.w, mv.w, a, acc.n);
-    *reinterpret_cast<float4*>(prow + k) = np;
-    *reinterpret_cast<float4*>(a.m + off + k) = mv;
-    return np;
-  }
-  static __device__ __forceinline__ float run1(float* prow, int64_t off, int64_t k, const Args& a, Acc& acc) {
-    float mm = a.m[off + k];
-    const float np = bop_elem(prow[k], a.g[off + k], mm, a, acc.n);
-    prow[k] = np;
-    a.m[off + k] = mm;
-    return np;
-  }
-  static __device__ __forceinline__ void finish(const Acc& acc, const Args& a) { bop_flush(acc.n, a.flips); }
-  static bool null(const Args& a) { return !a.g || !a.m; }
-  static bool vec(const Args& a) { return aligned16(a.g) && aligned16(a.m); }
 };
 
 // One 4-element run of a latent-weight row updated in place (the update mode of sign_pack_tile_k: the
@@ -1302,7 +1182,7 @@ BNN_API int bnn_adam_clamp_pack_sched(float* p, const float* grad, float* exp_av
   AdamArgs a{grad, exp_avg, exp_avg_sq, beta1, beta2, eps, 0.f, 1.f, grad_scale, clamp};
   a.sched = sched;
   a.ctr = ctr;
-  return update_pack_impl<AdamUpdate>("bnn_adam_clamp_pack", p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
+  return update_pack_impl<AdamUpdate>("bnn_adam_clamp_pack_sched", p, a, N, K, fmt, q, ldq, qt, ldqt, qt_fmt, stream);
 }
 
 BNN_API int bnn_sgd_clamp_pack(float* p, const float* grad, float* buf, int64_t N, int64_t K, float lr,

@@ -4,10 +4,14 @@
 //     p.data.copy_(p.org); optimizer.step(); p.org.copy_(p.data.clamp_(-1,1))
 // around torch.optim.Adam (mnist-dist2.py:91).  bnn_adam_clamp applies Adam to the latent
 // weight and clamps it in one HBM pass (7 fp32 streams: p, g, m, v read; p, m, v written).
+//
+// Every flat and multi-tensor pass here -- Adam, SGD, Bop -- is the one span below driven by an update
+// policy (bnn_update.h), the same policies the packing kernels of bnn_pack.hip fuse with the re-pack.
 #include <algorithm>
 #include <cmath>
 
 #include "bnn_common.h"
+#include "bnn_update.h"
 
 namespace bnn {
 namespace {
@@ -32,16 +36,58 @@ __global__ __launch_bounds__(256) void hardtanh_bwd_k(const float* __restrict__ 
   for (int64_t i = tail + i0; i < n; i += stride) out[i] = f(x[i], g[i]);
 }
 
-// Adam + clamp over a flat tensor (math: adam_elem in bnn_common.h).
-__global__ __launch_bounds__(256) void adam_clamp_k(float* __restrict__ p, int64_t n, AdamArgs a0) {
-  const AdamArgs a = adam_resolve(a0);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float mi = a.m[i], vi = a.v[i];
-    p[i] = adam_elem(p[i], a.g[i], mi, vi, a);
-    a.m[i] = mi;
-    a.v[i] = vi;
+// Threads per block of every update launch.  A constant, not blockDim.x: with blockDim.x in the span every
+// instance compiled to the remainder-workgroup form of the block size (a dependent global_load_ushort at each
+// wave's start), as the parent's sgd_span kernels did and its kernels that read blockDim.x themselves did not.
+constexpr int UPD_THREADS = 256;
+
+// One tensor's grid-stride pass of update policy U over p[0 .. n) and the policy's streams (a flat tensor is
+// one row of the policies' layout).  vec: p and every stream 16-B aligned -> float4 runs and a scalar tail,
+// else scalar throughout.  Both go through the same element, so the result does not depend on vec.
+template <class U>
+__device__ __forceinline__ void update_span(float* __restrict__ p, int64_t n, const typename U::Args& a, int vec,
+                                            typename U::Acc& acc) {
+  const int64_t stride = (int64_t)gridDim.x * UPD_THREADS;
+  const int64_t i0 = (int64_t)blockIdx.x * UPD_THREADS + threadIdx.x;
+  int64_t tail = 0;
+  if (vec) {
+    const int64_t n4 = n / 4;
+    for (int64_t i = i0; i < n4; i += stride) U::run4(p, 0, 4 * i, a, acc);
+    tail = n4 * 4;
   }
+  for (int64_t i = tail + i0; i < n; i += stride) U::run1(p, 0, i, a, acc);
+}
+
+template <class U>
+__global__ __launch_bounds__(UPD_THREADS) void update_flat_k(float* __restrict__ p, int64_t n, typename U::Args a0, int vec) {
+  const typename U::Args a = U::resolve(a0);
+  typename U::Acc acc{};
+  update_span<U>(p, n, a, vec, acc);
+  U::finish(acc, a);
+}
+
+// Multi-tensor form: up to ADAM_MT tensors (the small parameters -- biases, BatchNorm affine
+// parameters, the head -- each of which would otherwise be its own launch of a few microseconds)
+// in ONE launch, blockIdx.y = tensor, each with its own arguments (Adam: its bias corrections or the
+// device-step table; SGD: its first and clamp flags).
+constexpr int ADAM_MT = 16;
+template <class U>
+struct UpdateMulti {
+  float* p[ADAM_MT];
+  int64_t n[ADAM_MT];
+  typename U::Args a[ADAM_MT];
+  int vec[ADAM_MT];
+};
+static_assert(sizeof(UpdateMulti<AdamUpdate>) <= 4096 && sizeof(UpdateMulti<SgdUpdate<-1>>) <= 4096,
+              "a kernel takes at most 4 KB of arguments");
+
+template <class U>
+__global__ __launch_bounds__(UPD_THREADS) void update_multi_k(UpdateMulti<U> um) {
+  const int j = blockIdx.y;
+  const typename U::Args a = U::resolve(um.a[j]);
+  typename U::Acc acc{};
+  update_span<U>(um.p[j], um.n[j], a, um.vec[j], acc);
+  U::finish(acc, a);
 }
 
 }  // namespace
@@ -58,6 +104,57 @@ namespace {
 
 inline int grid_for(int64_t n) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192));
+}
+
+// A flat pass's pointers and length are good: an empty tensor is nothing to do, whatever its pointers.
+template <class U>
+bool update_flat_ok(const float* p, int64_t n, const typename U::Args& a) {
+  return n >= 0 && (n == 0 || (p && !U::null(a)));
+}
+
+// The flat pass of policy U: one argument contract and one launch for every flat entry.  ok = the entry's
+// own hyper-parameter check.
+template <class U>
+int update_flat_impl(const char* name, float* p, int64_t n, const typename U::Args& a, bool ok, void* stream) {
+  if (!ok || !update_flat_ok<U>(p, n, a)) {
+    set_error("%s: bad arguments", name);
+    return kErrInval;
+  }
+  if (n == 0) return 0;
+  const int vec = aligned16(p) && U::vec(a);
+  hipLaunchKernelGGL(update_flat_k<U>, dim3(grid_for(vec ? (n + 3) / 4 : n)), dim3(UPD_THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream), p, n, a, vec);
+  return check_launch(name);
+}
+
+// The multi-tensor pass of policy U.  ok = the entry's check of its own arrays and hyper-parameters;
+// args_of(j, a) fills tensor j's arguments, false: they are bad.  Empty tensors are left out of the launch.
+template <class U, class ArgsOf>
+int update_multi_impl(const char* name, int32_t count, float* const* p, const int64_t* n, bool ok, ArgsOf args_of,
+                      void* stream) {
+  if (!ok || count < 0 || count > ADAM_MT || (count > 0 && (!p || !n))) {
+    set_error("%s: bad arguments (count %d, at most %d tensors per launch)", name, count, ADAM_MT);
+    return kErrInval;
+  }
+  UpdateMulti<U> um{};
+  int64_t work = 0;      // the most threads a tensor can use
+  int k = 0;
+  for (int j = 0; j < count; ++j) {
+    typename U::Args a{};
+    if (n[j] < 0 || !args_of(j, a) || (n[j] > 0 && (!p[j] || U::null(a)))) {
+      set_error("%s: bad tensor %d", name, j);
+      return kErrInval;
+    }
+    if (n[j] == 0) continue;
+    um.p[k] = p[j], um.n[k] = n[j], um.a[k] = a, um.vec[k] = aligned16(p[j]) && U::vec(a);
+    work = std::max(work, um.vec[k] ? (n[j] + 3) / 4 : n[j]);
+    ++k;
+  }
+  if (k == 0) return 0;
+  const unsigned gx = (unsigned)std::min<int64_t>((work + UPD_THREADS - 1) / UPD_THREADS, 1024);
+  hipLaunchKernelGGL(update_multi_k<U>, dim3(gx, (unsigned)k), dim3(UPD_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+                     um);
+  return check_launch(name);
 }
 
 }  // namespace
@@ -77,239 +174,72 @@ BNN_API int bnn_hardtanh_bwd(const float* x, const float* g, float* out, int64_t
   return check_launch("bnn_hardtanh_bwd");
 }
 
+// Adam + clamp (math: adam_elem in bnn_common.h), per-launch bias corrections or the device-step table.
 BNN_API int bnn_adam_clamp(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                            float lr, float beta1, float beta2, float eps, int64_t step,
                            float grad_scale, int32_t clamp, void* stream) {
-  if (n < 0 || (n > 0 && (!p || !grad || !exp_avg || !exp_avg_sq)) || step < 1) {   // n == 0: nothing to do
-    set_error("bnn_adam_clamp: bad arguments");
-    return kErrInval;
-  }
-  if (n == 0) return 0;
-  float step_size, bc2_sqrt;
-  adam_bias_correction(lr, beta1, beta2, step, &step_size, &bc2_sqrt);
-  const AdamArgs a{grad, exp_avg, exp_avg_sq, beta1, beta2, eps, step_size, bc2_sqrt, grad_scale, clamp};
-  hipLaunchKernelGGL(adam_clamp_k, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, n, a);
-  return check_launch("bnn_adam_clamp");
+  AdamArgs a{grad, exp_avg, exp_avg_sq, beta1, beta2, eps, 0.f, 1.f, grad_scale, clamp};
+  if (step >= 1) adam_bias_correction(lr, beta1, beta2, step, &a.step_size, &a.bc2_sqrt);
+  return update_flat_impl<AdamUpdate>("bnn_adam_clamp", p, n, a, step >= 1, stream);
 }
 
 BNN_API int bnn_adam_clamp_sched(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                                  float beta1, float beta2, float eps, const float* sched, const int64_t* ctr,
                                  float grad_scale, int32_t clamp, void* stream) {
-  if (n < 0 || (n > 0 && (!p || !grad || !exp_avg || !exp_avg_sq)) || !sched || !ctr) {
-    set_error("bnn_adam_clamp_sched: bad arguments");
-    return kErrInval;
-  }
-  if (n == 0) return 0;
   AdamArgs a{grad, exp_avg, exp_avg_sq, beta1, beta2, eps, 0.f, 1.f, grad_scale, clamp};
   a.sched = sched;
   a.ctr = ctr;
-  hipLaunchKernelGGL(adam_clamp_k, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, n, a);
-  return check_launch("bnn_adam_clamp_sched");
+  return update_flat_impl<AdamUpdate>("bnn_adam_clamp_sched", p, n, a, sched && ctr, stream);
 }
-
-// Multi-tensor form: up to ADAM_MT tensors (the small parameters -- biases, BatchNorm affine
-// parameters, the head -- each of which would otherwise be its own launch of a few microseconds)
-// in ONE launch, blockIdx.y = tensor; per-tensor bias corrections (or the device-step table).
-namespace bnn {
-namespace {
-constexpr int ADAM_MT = 16;
-struct AdamMulti {
-  float* p[ADAM_MT];
-  const float* g[ADAM_MT];
-  float* m[ADAM_MT];
-  float* v[ADAM_MT];
-  int64_t n[ADAM_MT];
-  float step_size[ADAM_MT], bc2_sqrt[ADAM_MT];
-  int clamp[ADAM_MT];
-  float b1, b2, eps, gscale;
-  const float* sched;
-  const int64_t* ctr;
-};
-
-__global__ __launch_bounds__(256) void adam_clamp_multi_k(AdamMulti am) {
-  const int j = blockIdx.y;
-  AdamArgs a{am.g[j], am.m[j], am.v[j], am.b1, am.b2, am.eps, am.step_size[j], am.bc2_sqrt[j], am.gscale,
-             am.clamp[j]};
-  a.sched = am.sched;
-  a.ctr = am.ctr;
-  a = adam_resolve(a);
-  float* __restrict__ p = am.p[j];
-  const int64_t n = am.n[j], stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float mi = a.m[i], vi = a.v[i];
-    p[i] = adam_elem(p[i], a.g[i], mi, vi, a);
-    a.m[i] = mi;
-    a.v[i] = vi;
-  }
-}
-}  // namespace
-}  // namespace bnn
 
 BNN_API int bnn_adam_clamp_multi(int32_t count, float* const* p, const float* const* grad, float* const* exp_avg,
                                  float* const* exp_avg_sq, const int64_t* n, const int64_t* step,
                                  const int32_t* clamp, float lr, float beta1, float beta2, float eps,
                                  const float* sched, const int64_t* ctr, float grad_scale, void* stream) {
-  if (count < 0 || count > ADAM_MT || (count > 0 && (!p || !grad || !exp_avg || !exp_avg_sq || !n || !step || !clamp)) ||
-      ((sched == nullptr) != (ctr == nullptr))) {
-    set_error("bnn_adam_clamp_multi: bad arguments (count %d, at most %d tensors per launch)", count, ADAM_MT);
-    return kErrInval;
-  }
-  AdamMulti am{};
-  int64_t nmax = 0;
-  int k = 0;
-  for (int j = 0; j < count; ++j) {
-    if (n[j] < 0 || (n[j] > 0 && (!p[j] || !grad[j] || !exp_avg[j] || !exp_avg_sq[j])) || (!sched && step[j] < 1)) {
-      set_error("bnn_adam_clamp_multi: bad tensor %d", j);
-      return kErrInval;
-    }
-    if (n[j] == 0) continue;
-    am.p[k] = p[j], am.g[k] = grad[j], am.m[k] = exp_avg[j], am.v[k] = exp_avg_sq[j], am.n[k] = n[j];
-    am.clamp[k] = clamp[j];
-    if (sched) {
-      am.step_size[k] = 0.f, am.bc2_sqrt[k] = 1.f;     // from the device-step table
-    } else {
-      adam_bias_correction(lr, beta1, beta2, step[j], &am.step_size[k], &am.bc2_sqrt[k]);
-    }
-    nmax = std::max(nmax, n[j]);
-    ++k;
-  }
-  if (k == 0) return 0;
-  am.b1 = beta1, am.b2 = beta2, am.eps = eps, am.gscale = grad_scale, am.sched = sched, am.ctr = ctr;
-  const unsigned gx = (unsigned)std::min<int64_t>((nmax + 255) / 256, 1024);
-  hipLaunchKernelGGL(adam_clamp_multi_k, dim3(gx, (unsigned)k), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), am);
-  return check_launch("bnn_adam_clamp_multi");
+  const bool ok = (count <= 0 || (grad && exp_avg && exp_avg_sq && step && clamp)) && ((sched == nullptr) == (ctr == nullptr));
+  return update_multi_impl<AdamUpdate>("bnn_adam_clamp_multi", count, p, n, ok, [&](int j, AdamArgs& a) {
+    if (!sched && step[j] < 1) return false;
+    a = AdamArgs{grad[j], exp_avg[j], exp_avg_sq[j], beta1, beta2, eps, 0.f, 1.f, grad_scale, clamp[j]};
+    a.sched = sched;       // the device-step table, else this tensor's own bias corrections
+    a.ctr = ctr;
+    if (!sched) adam_bias_correction(lr, beta1, beta2, step[j], &a.step_size, &a.bc2_sqrt);
+    return true;
+  }, stream);
 }
 
 // torch.optim.SGD + clamp (math: sgd_elem in bnn_common.h): 5 fp32 streams (p, g, buf read; p, buf
 // written), 2 + 1 without momentum.  Nothing depends on the step count, so a captured step replays
-// these launches as they are.
-namespace bnn {
-namespace {
-
-// one tensor's grid-stride pass; rd / wr (uniform): the momentum buffer is read / written
-__device__ __forceinline__ void sgd_span(float* __restrict__ p, int64_t n, const SgdArgs& a) {
-  const bool wr = a.mu != 0.f, rd = wr && !a.first;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float bi = rd ? a.buf[i] : 0.f;
-    p[i] = sgd_elem(p[i], a.g[i], bi, a);
-    if (wr) a.buf[i] = bi;
-  }
-}
-
-__global__ __launch_bounds__(256) void sgd_clamp_k(float* __restrict__ p, int64_t n, SgdArgs a) { sgd_span(p, n, a); }
-
-struct SgdMulti {
-  float* p[ADAM_MT];
-  const float* g[ADAM_MT];
-  float* buf[ADAM_MT];
-  int64_t n[ADAM_MT];
-  int first[ADAM_MT], clamp[ADAM_MT];
-  float lr, mu, omd, wd, gscale;
-  int nesterov;
-};
-
-__global__ __launch_bounds__(256) void sgd_clamp_multi_k(SgdMulti sm) {
-  const int j = blockIdx.y;
-  const SgdArgs a{sm.g[j], sm.buf[j], sm.lr, sm.mu, sm.omd, sm.wd, sm.gscale, sm.nesterov, sm.first[j], sm.clamp[j]};
-  sgd_span(sm.p[j], sm.n[j], a);
-}
-
-}  // namespace
-}  // namespace bnn
-
+// these launches as they are.  SgdUpdate<-1>: the buffer is read / written as a.mu and a.first say.
 BNN_API int bnn_sgd_clamp(float* p, const float* grad, float* buf, int64_t n, float lr, float momentum, float omd,
                           float weight_decay, int32_t nesterov, int32_t first, float grad_scale, int32_t clamp,
                           void* stream) {
-  if (n < 0 || (n > 0 && (!p || !grad)) || (momentum != 0.f && !buf) ||
-      !sgd_hyper_ok(lr, momentum, omd, weight_decay, nesterov)) {
-    set_error("bnn_sgd_clamp: bad arguments");
-    return kErrInval;
-  }
-  if (n == 0) return 0;
   const SgdArgs a{grad, buf, lr, momentum, omd, weight_decay, grad_scale, nesterov != 0, first != 0, clamp};
-  hipLaunchKernelGGL(sgd_clamp_k, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, n, a);
-  return check_launch("bnn_sgd_clamp");
+  const bool ok = (momentum == 0.f || buf) && sgd_hyper_ok(lr, momentum, omd, weight_decay, nesterov);
+  return update_flat_impl<SgdUpdate<-1>>("bnn_sgd_clamp", p, n, a, ok, stream);
 }
 
 BNN_API int bnn_sgd_clamp_multi(int32_t count, float* const* p, const float* const* grad, float* const* buf,
                                 const int64_t* n, const int32_t* first, const int32_t* clamp, float lr,
                                 float momentum, float omd, float weight_decay, int32_t nesterov, float grad_scale,
                                 void* stream) {
-  if (count < 0 || count > ADAM_MT || (count > 0 && (!p || !grad || !n || !first || !clamp)) ||
-      (count > 0 && momentum != 0.f && !buf) || !sgd_hyper_ok(lr, momentum, omd, weight_decay, nesterov)) {
-    set_error("bnn_sgd_clamp_multi: bad arguments (count %d, at most %d tensors per launch)", count, ADAM_MT);
-    return kErrInval;
-  }
-  SgdMulti sm{};
-  int64_t nmax = 0;
-  int k = 0;
-  for (int j = 0; j < count; ++j) {
-    if (n[j] < 0 || (n[j] > 0 && (!p[j] || !grad[j] || (momentum != 0.f && !buf[j])))) {
-      set_error("bnn_sgd_clamp_multi: bad tensor %d", j);
-      return kErrInval;
-    }
-    if (n[j] == 0) continue;
-    sm.p[k] = p[j], sm.g[k] = grad[j], sm.buf[k] = momentum != 0.f ? buf[j] : nullptr, sm.n[k] = n[j];
-    sm.first[k] = first[j] != 0, sm.clamp[k] = clamp[j];
-    nmax = std::max(nmax, n[j]);
-    ++k;
-  }
-  if (k == 0) return 0;
-  sm.lr = lr, sm.mu = momentum, sm.omd = omd, sm.wd = weight_decay, sm.gscale = grad_scale, sm.nesterov = nesterov != 0;
-  const unsigned gx = (unsigned)std::min<int64_t>((nmax + 255) / 256, 1024);
-  hipLaunchKernelGGL(sgd_clamp_multi_k, dim3(gx, (unsigned)k), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), sm);
-  return check_launch("bnn_sgd_clamp_multi");
+  const bool ok = (count <= 0 || (grad && first && clamp && (momentum == 0.f || buf))) &&
+                  sgd_hyper_ok(lr, momentum, omd, weight_decay, nesterov);
+  return update_multi_impl<SgdUpdate<-1>>("bnn_sgd_clamp_multi", count, p, n, ok, [&](int j, SgdArgs& a) {
+    a = SgdArgs{grad[j], momentum != 0.f ? buf[j] : nullptr, lr, momentum, omd, weight_decay, grad_scale,
+                nesterov != 0, first[j] != 0, clamp[j]};
+    return true;
+  }, stream);
 }
 
-// Bop over a flat tensor (math: bop_elem in bnn_common.h): 5 fp32 streams (w, g, m read; w, m written).
-// vec: all three pointers 16-B aligned -> float4 runs and a scalar tail, else scalar throughout.
-namespace bnn {
-namespace {
-
-__global__ __launch_bounds__(256) void bop_k(float* __restrict__ w, int64_t n, BopArgs a, int vec) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int nf = 0;
-  int64_t tail = 0;
-  if (vec) {
-    const int64_t n4 = n / 4;
-    for (int64_t i = i0; i < n4; i += stride) {
-      float4 wv = reinterpret_cast<const float4*>(w)[i];
-      const float4 gv = reinterpret_cast<const float4*>(a.g)[i];
-      float4 mv = reinterpret_cast<const float4*>(a.m)[i];
-      wv.x = bop_elem(wv.x, gv.x, mv.x, a, nf);
-      wv.y = bop_elem(wv.y, gv.y, mv.y, a, nf);
-      wv.z = bop_elem(wv.z, gv.z, mv.z, a, nf);
-      wv.w = bop_elem(wv.w, gv.w, mv.w, a, nf);
-      reinterpret_cast<float4*>(w)[i] = wv;
-      reinterpret_cast<float4*>(a.m)[i] = mv;
-    }
-    tail = n4 * 4;
-  }
-  for (int64_t i = tail + i0; i < n; i += stride) {
-    float mi = a.m[i];
-    w[i] = bop_elem(w[i], a.g[i], mi, a, nf);
-    a.m[i] = mi;
-  }
-  bop_flush(nf, a.flips);
-}
-
-}  // namespace
-}  // namespace bnn
-
+// Bop (math: bop_elem in bnn_common.h): 5 fp32 streams (w, g, m read; w, m written).
 BNN_API int bnn_bop(float* w, const float* grad, float* m, int64_t n, float gamma, float threshold, float grad_scale,
                     int64_t* flips, void* stream) {
-  if (n < 0 || (n > 0 && (!w || !grad || !m)) || !bop_hyper_ok(gamma, threshold)) {
+  const BopArgs a{grad, m, gamma, threshold, grad_scale, flips};
+  if (!bop_hyper_ok(gamma, threshold) || !update_flat_ok<BopUpdate>(w, n, a)) {    // its own, fuller text
     set_error("bnn_bop: bad arguments (n=%lld gamma=%g threshold=%g)", (long long)n, (double)gamma, (double)threshold);
     return kErrInval;
   }
-  if (n == 0) return 0;
-  const int vec = aligned16(w) && aligned16(grad) && aligned16(m);
-  const BopArgs a{grad, m, gamma, threshold, grad_scale, flips};
-  hipLaunchKernelGGL(bop_k, dim3(grid_for(vec ? (n + 3) / 4 : n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     w, n, a, vec);
-  return check_launch("bnn_bop");
+  return update_flat_impl<BopUpdate>("bnn_bop", w, n, a, true, stream);
 }
 
 BNN_API int bnn_adam_schedule(float lr, float beta1, float beta2, int64_t step0, int64_t n, float* out) {
