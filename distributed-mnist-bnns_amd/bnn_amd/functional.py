@@ -1631,6 +1631,26 @@ def _zq_fmt(x, binarize_input, stride, dilation, groups, C, KH, KW, H, W, pad, N
     return fmt
 
 
+# Wide-channel forward: a binarised-input convolution whose shape bnn_conv2d_fwd_wide_ok
+# takes (C % 64 == 0, C > 64 or Co > 64, stride 1, ...) runs as an FP4-MFMA implicit GEMM instead of the
+# generic kernel; same bits.  BNN_CONV_WIDE=0: today's path (A/B and the tests).
+CONV_WIDE = os.environ.get("BNN_CONV_WIDE", "1") != "0"
+CONV_WIDE_CALLS = 0
+_CONV_WIDE_WS = {}
+
+
+def _conv_wide_workspace(nbytes, device):
+    """The packed operands' scratch, one per (device, stream, size): allocated at the first call, so a
+    region captured after warm-up allocates nothing."""
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream, nbytes)
+    ws = _CONV_WIDE_WS.get(key)
+    if ws is None:
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        if not torch.cuda.is_current_stream_capturing():     # a capture's allocation stays in its graph's pool
+            _CONV_WIDE_WS[key] = ws
+    return ws
+
+
 def conv_out_hw(H, W, KH, KW, stride, padding, dilation):
     """(OH, OW) of a convolution.  Raises ValueError when the dilated kernel is larger than the
     padded input in either dimension (torch refuses the same shapes; the library's make_shape too)."""
@@ -1645,6 +1665,7 @@ class BinaryConv2dFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, binarize_input, stride, padding, dilation, groups, emit_compact=False,
                 stochastic=None):
+        global CONV_WIDE_CALLS
         _check(x, weight, bias)
         OH, OW = conv_out_hw(x.shape[2], x.shape[3], weight.shape[2], weight.shape[3], stride, padding, dilation)
         _conv_env()
@@ -1680,6 +1701,15 @@ class BinaryConv2dFunction(torch.autograd.Function):
         if ctx.empty:             # empty batch: F.conv2d returns [0, Co, OH, OW]
             return y
         macs = N * Co * OH * OW * (C // groups) * KH * KW
+        if (CONV_WIDE and binarize_input
+                and L.lib().bnn_conv2d_fwd_wide_ok(N, C, H, W, Co, KH, KW, stride, padding, dilation, groups)):
+            ws = _conv_wide_workspace(int(L.lib().bnn_conv2d_fwd_wide_workspace(N, C, H, W, Co, KH, KW, padding)),
+                                      x.device)
+            with _timed("conv2d_fwd_wide", 2 * macs, 4 * (x.numel() + y.numel() + w.numel())):
+                L.call("bnn_conv2d_fwd_wide", x, w, b, y, N, C, H, W, Co, KH, KW, stride, padding, dilation, groups,
+                       ws, ws.numel(), L.stream())
+            CONV_WIDE_CALLS += 1
+            return y
         with _timed("conv2d_fwd", 2 * macs, 4 * (x.numel() + y.numel() + w.numel())):
             L.call("bnn_conv2d_fwd", x, int(binarize_input), w, b, y, N, C, H, W, Co, KH, KW, stride, padding, dilation,
                    groups, L.stream())

@@ -402,6 +402,32 @@ int bnn_conv2d_fwd_q(const float* x, const float* w_latent, void* y, int32_t yfm
  * bnn_conv_set_mfma), else 0: the host asks before emitting a compact conv output. */
 int bnn_conv2d_fwd_q_ok(int32_t yfmt, int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
                         int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+/* The binarised-input forward for wide channels, on the FP4 MFMA: y = fl((float)I + bias[co])
+ * with I the exact integer sum, bit-identical to bnn_conv2d_fwd(binarize_input = 1) on the same arguments
+ * (bias nullable).  Shapes taken (bnn_conv2d_fwd_wide_ok = 1): groups 1, stride 1, dilation 1, pad <=
+ * min(KH, KW) - 1, C % 64 == 0, C > 64 or Co > 64, C KH KW < 2^24, and one 64-channel block's window --
+ * 128 + (KH-1)(W + 2 pad) + KW-1 positions -- plus its KH KW x 128 weight rows, 32 B each, within 160 KiB
+ * of LDS (3x3 up to W + 2 pad = 1919, 5x5 up to 447).  `work` is scratch of
+ * bnn_conv2d_fwd_wide_workspace(...) bytes (0 for a shape not taken), 16-B aligned; it may hold anything
+ * on entry and is rewritten by every call (the packed input and weight).  A shape not taken, a null
+ * pointer or a short workspace return BNN_EINVAL with nothing launched; N == 0 returns 0.
+ * bnn_conv2d_fwd_wide_kernel: the GEMM instance the call launches, with its LDS bytes and the modelled
+ * cycles of its fragment reads ("conv_wide_gemm_k<2> lds=88064 b128=4"); "" for a shape not taken.  The
+ * entry and the three queries share one decision function.  The string is valid until the calling
+ * thread's next query. */
+int bnn_conv2d_fwd_wide_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                           int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int64_t bnn_conv2d_fwd_wide_workspace(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                      int64_t KW, int32_t pad);
+int bnn_conv2d_fwd_wide(const float* x, const float* w_latent, const float* bias, float* y, int64_t N, int64_t C,
+                        int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad,
+                        int32_t dil, int32_t groups, void* work, int64_t work_bytes, bnn_stream_t stream);
+const char* bnn_conv2d_fwd_wide_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                       int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+/* Timing hook (not part of the stable contract; tools/conv_wide_bench.py): the launches later
+ * bnn_conv2d_fwd_wide calls make -- bit 0 the input pack, bit 1 the weight pack, bit 2 the GEMM; 7 = all
+ * (the default; anything else leaves y or the workspace as an earlier call made them).  mask < 0 queries. */
+int bnn_conv2d_fwd_wide_set_stages(int32_t mask);
 /* Frozen-model inference (bnn_amd.inference.FrozenCNN): the binary convolution with eval-mode
  * BatchNorm2d -> Hardtanh -> MaxPool2d(2, 2) in its epilogue.  Geometry of both entries: stride 1,
  * dilation 1, groups 1, C == 1 (KW <= 8) or C % 16 == 0 (<= 64, at most 256 output pixels), Co <= 64,
