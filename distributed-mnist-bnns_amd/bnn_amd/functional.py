@@ -1637,6 +1637,12 @@ def _zq_fmt(x, binarize_input, stride, dilation, groups, C, KH, KW, H, W, pad, N
 CONV_WIDE = os.environ.get("BNN_CONV_WIDE", "1") != "0"
 CONV_WIDE_CALLS = 0
 _CONV_WIDE_WS = {}
+# Wide-channel input gradient: where bnn_conv2d_bwd_data_wide_ok takes the shape, dX runs as a
+# bf16-MFMA implicit GEMM on the exact three-plane split of dy instead of the generic kernel -- the same
+# exact products summed in another order, whether or not the forward binarised its input or took the wide
+# path.  BNN_CONV_WIDE_BWD=0: today's path (A/B and the tests).
+CONV_WIDE_BWD = os.environ.get("BNN_CONV_WIDE_BWD", "1") != "0"
+CONV_WIDE_BWD_CALLS = 0
 
 
 def _conv_wide_workspace(nbytes, device):
@@ -1753,9 +1759,19 @@ class BinaryConv2dFunction(torch.autograd.Function):
             return (None, dw if ctx.needs_input_grad[1] else None, db, None, None, None, None, None, None, None)
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            with _timed("conv2d_bwd_data", 2 * macs, 4 * (dy.numel() + dx.numel() + w.numel())):
-                L.call("bnn_conv2d_bwd_data", dy, w, dx, N, C, H, W, Co, KH, KW, stride, padding, dilation, groups,
-                       L.stream())
+            if CONV_WIDE_BWD and L.lib().bnn_conv2d_bwd_data_wide_ok(N, C, H, W, Co, KH, KW, stride, padding,
+                                                                    dilation, groups):
+                global CONV_WIDE_BWD_CALLS
+                ws = _conv_wide_workspace(
+                    int(L.lib().bnn_conv2d_bwd_data_wide_workspace(N, C, H, W, Co, KH, KW, padding)), x.device)
+                with _timed("conv2d_bwd_data_wide", 2 * macs, 4 * (dy.numel() + dx.numel() + w.numel())):
+                    L.call("bnn_conv2d_bwd_data_wide", dy, w, dx, N, C, H, W, Co, KH, KW, stride, padding, dilation,
+                           groups, ws, ws.numel(), L.stream())
+                CONV_WIDE_BWD_CALLS += 1
+            else:
+                with _timed("conv2d_bwd_data", 2 * macs, 4 * (dy.numel() + dx.numel() + w.numel())):
+                    L.call("bnn_conv2d_bwd_data", dy, w, dx, N, C, H, W, Co, KH, KW, stride, padding, dilation,
+                           groups, L.stream())
         need_db = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or need_db:
             dw = torch.empty_like(w)

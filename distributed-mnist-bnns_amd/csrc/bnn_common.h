@@ -53,6 +53,19 @@ __device__ __forceinline__ int tsign(float x) { return (x > 0.f) - (x < 0.f); }
 // FP4 (e2m1) code of a ternary value: +1 = 0b0010, -1 = 0b1010, 0 = 0b0000.
 __device__ __forceinline__ uint32_t fp4_code(int s) { return s > 0 ? 0x2u : (s < 0 ? 0xAu : 0u); }
 
+// The exact split of an fp32 value into three bf16 planes, y = d1 + d2 + d3 (finite, normal y): every
+// plane times a ternary weight is an exact MFMA product (conv_bwd_data_bf3_k, conv_wide_bwd_data_k).
+__device__ __forceinline__ void bf16x3_split(float y, unsigned short& d1, unsigned short& d2, unsigned short& d3) {
+  const uint32_t u = __float_as_uint(y);
+  const uint32_t h1 = u & 0xFFFF0000u;                 // truncation: y - d1 is exact in fp32
+  const float r1 = y - __uint_as_float(h1);
+  const uint32_t h2 = __float_as_uint(r1) & 0xFFFF0000u;
+  const float r2 = r1 - __uint_as_float(h2);           // <= 8 significant bits left: exact in bf16
+  d1 = (unsigned short)(h1 >> 16);
+  d2 = (unsigned short)(h2 >> 16);
+  d3 = (unsigned short)(__float_as_uint(r2) >> 16);
+}
+
 // The input of a BatchNorm pass, in one of three forms (XF):
 //  0  fp32 x [M][C];
 //  1  (z16) the int16 exact dot products I of the ternary BinarizeLinear that produced it

@@ -981,17 +981,6 @@ struct B3Data {
   int rowt;  // 1: pixel tiles are image rows (W <= 16, lanes >= W idle); 0: 16 consecutive pixels
 };
 
-__device__ __forceinline__ void bf16x3_split(float y, unsigned short& d1, unsigned short& d2, unsigned short& d3) {
-  const uint32_t u = __float_as_uint(y);
-  const uint32_t h1 = u & 0xFFFF0000u;                 // truncation: y - d1 is exact in fp32
-  const float r1 = y - __uint_as_float(h1);
-  const uint32_t h2 = __float_as_uint(r1) & 0xFFFF0000u;
-  const float r2 = r1 - __uint_as_float(h2);           // <= 8 significant bits left: exact in bf16
-  d1 = (unsigned short)(h1 >> 16);
-  d2 = (unsigned short)(h2 >> 16);
-  d3 = (unsigned short)(__float_as_uint(r2) >> 16);
-}
-
 constexpr int B3_DU = 2;   // register-prefetched dY units per thread (backward data)
 
 template <int NT, int MT>

@@ -22,8 +22,7 @@
 // chunk h ^ ((R >> 3) & 1) separates them for every base, i.e. every tap shift (wide_frag_cycles
 // checks this with the bank model of bnn_lds_model.h).  The LDS-DMA writes 1 KiB runs, so the
 // swizzle is applied on the global side of the copy.
-#include "bnn_common.h"
-#include "bnn_lds_model.h"
+#include "bnn_conv_wide.h"
 
 #include <cstdio>
 
@@ -31,10 +30,6 @@
 
 namespace bnn {
 namespace {
-
-constexpr int WD_T = 256;                     // threads of every kernel here
-constexpr int WD_TP = 128, WD_TC = 128;       // positions x output channels of a GEMM workgroup
-constexpr int64_t kWideMaxLds = 160 * 1024;   // a single workgroup may own the CU's whole LDS
 
 struct WidePlan {
   int64_t N, C, H, W, Co;
@@ -47,21 +42,6 @@ struct WidePlan {
   int64_t Ppad;   // positions per plane: the last tile's window stays inside it
   int64_t ntile, lds, wq_off, work_bytes;
 };
-
-// byte offset of half h of LDS row `row` (rows of 32 B, halves swizzled by bit 3 of the row)
-__host__ __device__ __forceinline__ int wide_row_off(int row, int h) { return row * 32 + 16 * (h ^ ((row >> 3) & 1)); }
-
-// The worst fragment read of the GEMM over every tap shift, by the bank model.
-int wide_frag_cycles(int KH, int KW, int Wp) {
-  int worst = 0;
-  for (int kh = 0; kh < KH; ++kh)
-    for (int kw = 0; kw < KW; ++kw) {
-      int addr[64];
-      for (int l = 0; l < 64; ++l) addr[l] = wide_row_off(kh * Wp + kw + (l & 31), l >> 5);
-      worst = std::max(worst, lds_b128_cycles(addr));
-    }
-  return worst;
-}
 
 // The one decision function: bnn_conv2d_fwd_wide_ok, the workspace and kernel queries and the launch.
 bool wide_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride,
@@ -98,8 +78,6 @@ bool wide_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t K
   *out = p;
   return true;
 }
-
-__device__ __forceinline__ void store_zero16(uint8_t* p) { *reinterpret_cast<uint4*>(p) = make_uint4(0u, 0u, 0u, 0u); }
 
 // four FP4 codes held one per byte -> 16 bits, byte j in nibble j
 __device__ __forceinline__ uint32_t squeeze4(uint32_t v) {
@@ -179,20 +157,6 @@ __global__ __launch_bounds__(WD_T) void conv_wide_pack_w_k(const float* __restri
   }
   *reinterpret_cast<uint4*>(wq + (((int64_t)cb * taps + tap) * Cop + co) * 32 + half * 16) = make_uint4(o[0], o[1], o[2], o[3]);
 }
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-__device__ __forceinline__ void wide_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-// every LDS-DMA piece of this wave has landed (s_waitcnt vmcnt(0), the other counters left alone)
-__device__ __forceinline__ void wide_wait_dma() { __builtin_amdgcn_s_waitcnt(0 | (7 << 4) | (15 << 8) | (0 << 14)); }
 
 struct WideGemm {
   const uint8_t* xq;

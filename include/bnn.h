@@ -428,6 +428,34 @@ const char* bnn_conv2d_fwd_wide_kernel(int64_t N, int64_t C, int64_t H, int64_t 
  * bnn_conv2d_fwd_wide calls make -- bit 0 the input pack, bit 1 the weight pack, bit 2 the GEMM; 7 = all
  * (the default; anything else leaves y or the workspace as an earlier call made them).  mask < 0 queries. */
 int bnn_conv2d_fwd_wide_set_stages(int32_t mask);
+/* The input gradient of the same wide-channel layers, on the bf16 MFMA:
+ * dx[n,c,ih,iw] = sum_{co,kh,kw} dy[n,co,ih+pad-kh,iw+pad-kw] * sign(w_latent[co,c,kh,kw]), dy [N][Co][OH][OW]
+ * and dx [N][C][H][W] fp32.  dy enters as its exact three-plane bf16 split and the weights are ternary, so
+ * every product is exact; the only rounding is the MFMA's fp32 accumulation (the sum's order differs from
+ * bnn_conv2d_bwd_data's: same exact terms, not the same bits).  No atomics: deterministic.  Shapes taken
+ * (bnn_conv2d_bwd_data_wide_ok = 1): those bnn_conv2d_fwd_wide_ok takes, less the ones whose backward stage
+ * -- three windows of 128 + (KH-1)(W + KW-1) + KW-1 positions plus KH KW x 128 weight rows, 32 B each --
+ * is beyond 160 KiB of LDS (3x3 up to W + KW-1 = 591, 5x5 up to 127), or whose grids or C H W reach 2^31.
+ * `work` is scratch of bnn_conv2d_bwd_data_wide_workspace(...) bytes (0 for a shape not taken), 16-B
+ * aligned; it may hold anything on entry and is rewritten by every call (the packed dy planes and weight).
+ * A shape not taken, a null pointer or a short workspace return BNN_EINVAL with nothing launched; N == 0
+ * returns 0.  bnn_conv2d_bwd_data_wide_kernel: the GEMM instance the call launches, with its LDS bytes and
+ * the modelled cycles of its fragment reads ("conv_wide_bwd_data_k<2> lds=116736 b128=4"); "" for a shape
+ * not taken.  The entry and the three queries share one decision function.  The string is valid until the
+ * calling thread's next query.  bnn_conv2d_bwd_data and bnn_conv_kernel are unaffected. */
+int bnn_conv2d_bwd_data_wide_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                                int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int64_t bnn_conv2d_bwd_data_wide_workspace(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                           int64_t KW, int32_t pad);
+int bnn_conv2d_bwd_data_wide(const float* dy, const float* w_latent, float* dx, int64_t N, int64_t C, int64_t H,
+                             int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad,
+                             int32_t dil, int32_t groups, void* work, int64_t work_bytes, bnn_stream_t stream);
+const char* bnn_conv2d_bwd_data_wide_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                            int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+/* Timing hook (not part of the stable contract; tools/conv_wide_bwd_bench.py): the launches later
+ * bnn_conv2d_bwd_data_wide calls make -- bit 0 the dy pack, bit 1 the weight pack, bit 2 the GEMM; 7 = all
+ * (the default; anything else leaves dx or the workspace as an earlier call made them).  mask < 0 queries. */
+int bnn_conv2d_bwd_data_wide_set_stages(int32_t mask);
 /* Frozen-model inference (bnn_amd.inference.FrozenCNN): the binary convolution with eval-mode
  * BatchNorm2d -> Hardtanh -> MaxPool2d(2, 2) in its epilogue.  Geometry of both entries: stride 1,
  * dilation 1, groups 1, C == 1 (KW <= 8) or C % 16 == 0 (<= 64, at most 256 output pixels), Co <= 64,

@@ -1,0 +1,101 @@
+"""The wide-channel binary conv input gradient (csrc/bnn_conv_wide_bwd.hip) against
+conv_transpose2d(dy, sign(w)) in float64 on the CPU, rounded once to fp32.  The inputs are chosen so that
+every partial sum in any order is representable in fp32: the comparisons are bit for bit."""
+import pytest
+import torch
+
+from test_gpu_conv_wide import SHAPES          # (N, C, H, W, Co, KH, KW, pad): the forward test's seven
+
+pytestmark = pytest.mark.gpu
+
+
+def _inputs(shape, kind):
+    """w as the forward test draws it.  dy "dense": integers in [-8, 8], sums below 8 * 130 * 25 < 2^24.
+    dy "lattice": zero except at oh % KH == 0 and ow % KW == 0, where one random channel holds a full-mantissa
+    value, so every dX element has at most one non-zero term +-v = +-(d1 + d2 + d3)."""
+    N, C, H, W, Co, KH, KW, pad = shape
+    g = torch.Generator().manual_seed(N * 131 + C * 7 + Co)
+    vals = torch.tensor([-1.5, -0.0, 0.0, 0.25])
+    w = vals[torch.randint(0, 4, (Co, C, KH, KW), generator=g)]
+    w.view(-1)[5::89] = float("nan")                     # tsign(NaN) = 0
+    OH, OW = H + 2 * pad - KH + 1, W + 2 * pad - KW + 1
+    if kind == "dense":
+        return torch.randint(-8, 9, (N, Co, OH, OW), generator=g).float(), w
+    lh, lw = (OH + KH - 1) // KH, (OW + KW - 1) // KW
+    v = torch.randn(N, 1, lh, lw, generator=g) * torch.exp2(torch.randint(-20, 21, (N, 1, lh, lw), generator=g).float())
+    assert bool((v.view(torch.int32) & 0xFF).ne(0).any())          # the third plane is exercised
+    dy = torch.zeros(N, Co, OH, OW)
+    dy[:, :, ::KH, ::KW].scatter_(1, torch.randint(0, Co, (N, 1, lh, lw), generator=g), v)
+    return dy, w
+
+
+def _reference(dy, w, pad):
+    sw = torch.nan_to_num(torch.sign(w), nan=0.0).double()
+    return torch.nn.functional.conv_transpose2d(dy.double(), sw, padding=pad)
+
+
+@pytest.mark.parametrize("kind", ["dense", "lattice"])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_wide_input_gradient_equals_float64_reference(shape, kind):
+    from bnn_amd import _lib as L
+    N, C, H, W, Co, KH, KW, pad = shape
+    dy, w = _inputs(shape, kind)
+    ref = _reference(dy, w, pad).float()
+    assert ref.shape == (N, C, H, W) and bool(ref.ne(0).any())
+    dyd, wd = dy.cuda(), w.cuda()
+    ws = torch.empty(L.lib().bnn_conv2d_bwd_data_wide_workspace(N, C, H, W, Co, KH, KW, pad), dtype=torch.uint8, device="cuda")
+    dx = torch.empty(N, C, H, W, device="cuda")
+    L.call("bnn_conv2d_bwd_data_wide", dyd, wd, dx, N, C, H, W, Co, KH, KW, 1, pad, 1, 1, ws, ws.numel(), L.stream())
+    assert torch.equal(dx.cpu(), ref)
+    ws.fill_(0xFF)                                       # halo and tails are written, not assumed; dx is overwritten
+    dx.fill_(7.0)
+    L.call("bnn_conv2d_bwd_data_wide", dyd, wd, dx, N, C, H, W, Co, KH, KW, 1, pad, 1, 1, ws, ws.numel(), L.stream())
+    assert torch.equal(dx.cpu(), ref)
+    if shape is SHAPES[1] and kind == "dense":           # and bnn_conv2d_bwd_data writes the same bits
+        dx0 = torch.empty_like(dx)
+        L.call("bnn_conv2d_bwd_data", dyd, wd, dx0, N, C, H, W, Co, KH, KW, 1, pad, 1, 1, L.stream())
+        assert torch.equal(dx0, dx)
+
+
+@pytest.mark.parametrize("stride,short", [(1, 1), (2, 0)])
+def test_short_workspace_and_refused_shape_launch_nothing(stride, short):
+    from bnn_amd import _lib as L
+    N, C, H, W, Co, KH, KW, pad = shape = SHAPES[0]
+    dy, w = _inputs(shape, "dense")
+    if stride == 2:
+        dy = dy[:, :, ::2, ::2].contiguous()
+    ws = torch.empty(L.lib().bnn_conv2d_bwd_data_wide_workspace(N, C, H, W, Co, KH, KW, pad), dtype=torch.uint8, device="cuda")
+    dx = torch.full((N, C, H, W), 7.0, device="cuda")
+    rc = L.lib().bnn_conv2d_bwd_data_wide(dy.cuda(), w.cuda(), dx, N, C, H, W, Co, KH, KW, stride, pad, 1, 1, ws,
+                                          ws.numel() - short, L.stream())
+    torch.cuda.synchronize()
+    assert rc == -1 and bool((dx == 7.0).all())
+    assert (b"workspace" in L.lib().bnn_last_error()) == bool(short)
+
+
+def test_module_takes_the_wide_input_gradient(monkeypatch):
+    """BinarizeConv2d(128, 96, 3, padding=1), forward and backward, with CONV_WIDE_BWD on and off: only x.grad
+    changes kernel, and both kernels meet the gradient bar of tests/test_gpu_parity.py (1e-5 norm-wise)."""
+    from bnn_amd import functional as BF
+    from models.binarized_modules import BinarizeConv2d
+    torch.manual_seed(11)
+    conv = BinarizeConv2d(128, 96, 3, padding=1).cuda().train()
+    x0 = torch.randn(2, 128, 10, 10, device="cuda")
+    dy = torch.randn(2, 96, 10, 10, device="cuda")
+    ref = _reference(dy.cpu(), conv.weight.detach().cpu(), 1)
+    got = {}
+    for on in (True, False):
+        monkeypatch.setattr(BF, "CONV_WIDE_BWD", on)
+        calls = BF.CONV_WIDE_BWD_CALLS
+        x = x0.clone().requires_grad_(True)
+        conv.zero_grad()
+        y = conv(x)
+        y.backward(dy)
+        torch.cuda.synchronize()
+        assert BF.CONV_WIDE_BWD_CALLS - calls == int(on)
+        err = float((x.grad.cpu().double() - ref).norm() / ref.norm())
+        print(f"CONV_WIDE_BWD={on}: x.grad rel err {err:.3e}")
+        assert err < 1e-5
+        got[on] = (y.detach(), conv.weight.grad.clone(), conv.bias.grad.clone())
+    for a, b in zip(got[True], got[False]):
+        assert torch.equal(a, b)
