@@ -1643,6 +1643,12 @@ _CONV_WIDE_WS = {}
 # path.  BNN_CONV_WIDE_BWD=0: today's path (A/B and the tests).
 CONV_WIDE_BWD = os.environ.get("BNN_CONV_WIDE_BWD", "1") != "0"
 CONV_WIDE_BWD_CALLS = 0
+# Wide-channel filter gradient: where the input was binarised and bnn_conv2d_bwd_filter_wide_ok
+# takes the shape, dW and db run as a bf16-MFMA GEMM over positions on the exact three-plane split of dy and
+# the ternary input instead of the generic kernel -- the same exact products summed in another order.
+# Independent of the two switches above.  BNN_CONV_WIDE_BWD_FILTER=0: today's path (A/B and the tests).
+CONV_WIDE_BWD_FILTER = os.environ.get("BNN_CONV_WIDE_BWD_FILTER", "1") != "0"
+CONV_WIDE_BWD_FILTER_CALLS = 0
 
 
 def _conv_wide_workspace(nbytes, device):
@@ -1776,11 +1782,22 @@ class BinaryConv2dFunction(torch.autograd.Function):
         if ctx.needs_input_grad[1] or need_db:
             dw = torch.empty_like(w)
             db = torch.empty((Co,), dtype=torch.float32, device=x.device) if need_db else None
-            ws = torch.empty((L.lib().bnn_conv2d_bwd_filter_workspace(N, C, Co, KH, KW, groups),),
-                             dtype=torch.uint8, device=x.device)
-            with _timed("conv2d_bwd_filter", 2 * macs, 4 * (dy.numel() + x.numel() + w.numel())):
-                L.call("bnn_conv2d_bwd_filter", dy, x, int(binarize_input), dw, db, ws, N, C, H, W, Co, KH, KW, stride,
-                       padding, dilation, groups, L.stream())
+            if (CONV_WIDE_BWD_FILTER and binarize_input
+                    and L.lib().bnn_conv2d_bwd_filter_wide_ok(N, C, H, W, Co, KH, KW, stride, padding, dilation,
+                                                              groups)):
+                global CONV_WIDE_BWD_FILTER_CALLS
+                ws = _conv_wide_workspace(
+                    int(L.lib().bnn_conv2d_bwd_filter_wide_workspace(N, C, H, W, Co, KH, KW, padding)), x.device)
+                with _timed("conv2d_bwd_filter_wide", 2 * macs, 4 * (dy.numel() + x.numel() + w.numel())):
+                    L.call("bnn_conv2d_bwd_filter_wide", dy, x, dw, db, N, C, H, W, Co, KH, KW, stride, padding,
+                           dilation, groups, ws, ws.numel(), L.stream())
+                CONV_WIDE_BWD_FILTER_CALLS += 1
+            else:
+                ws = torch.empty((L.lib().bnn_conv2d_bwd_filter_workspace(N, C, Co, KH, KW, groups),),
+                                 dtype=torch.uint8, device=x.device)
+                with _timed("conv2d_bwd_filter", 2 * macs, 4 * (dy.numel() + x.numel() + w.numel())):
+                    L.call("bnn_conv2d_bwd_filter", dy, x, int(binarize_input), dw, db, ws, N, C, H, W, Co, KH, KW,
+                           stride, padding, dilation, groups, L.stream())
             if not ctx.needs_input_grad[1]:
                 dw = None
         return dx, dw, db, None, None, None, None, None, None, None

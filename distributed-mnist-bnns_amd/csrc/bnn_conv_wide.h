@@ -1,6 +1,7 @@
 // Shared by the wide-channel convolution units (bnn_conv_wide.hip: forward, DESIGN.md §19;
-// bnn_conv_wide_bwd.hip: input gradient, §20): the 32-B LDS row with its half swizzle, the bank-model
-// check of the fragment reads, and the LDS-DMA stage copy's primitives.
+// bnn_conv_wide_bwd.hip: input gradient, §20; bnn_conv_wide_bwd_filter.hip: filter gradient, §21): the 32-B
+// LDS row with its half swizzle, the bank-model check of the fragment reads, the LDS-DMA stage copy's
+// primitives, and the bf16 MFMA operand type of the two backward units.
 #pragma once
 #include "bnn_common.h"
 #include "bnn_lds_model.h"
@@ -10,6 +11,8 @@ namespace bnn {
 constexpr int WD_T = 256;                     // threads of every kernel of both units
 constexpr int WD_TP = 128, WD_TC = 128;       // positions x channels of a GEMM workgroup
 constexpr int64_t kWideMaxLds = 160 * 1024;   // a single workgroup may own the CU's whole LDS
+
+typedef __bf16 v8bf __attribute__((ext_vector_type(8)));   // one lane's operand of v_mfma_f32_32x32x16_bf16
 
 // byte offset of half h of LDS row `row` (rows of 32 B, halves swizzled by bit 3 of the row)
 __host__ __device__ __forceinline__ int wide_row_off(int row, int h) { return row * 32 + 16 * (h ^ ((row >> 3) & 1)); }

@@ -30,8 +30,6 @@
 namespace bnn {
 namespace {
 
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-
 struct WideBwdPlan {
   int64_t N, C, H, W, Co;
   int KH, KW, pad, Hq, Wq, OH, OW, taps, nkb, nct, Cp;

@@ -456,6 +456,38 @@ const char* bnn_conv2d_bwd_data_wide_kernel(int64_t N, int64_t C, int64_t H, int
  * bnn_conv2d_bwd_data_wide calls make -- bit 0 the dy pack, bit 1 the weight pack, bit 2 the GEMM; 7 = all
  * (the default; anything else leaves dx or the workspace as an earlier call made them).  mask < 0 queries. */
 int bnn_conv2d_bwd_data_wide_set_stages(int32_t mask);
+/* The filter and bias gradient of the same wide-channel layers, on the bf16 MFMA:
+ * dw[co,c,kh,kw] = sum_{n,oh,ow} dy[n,co,oh,ow] * sign(x[n,c,oh+kh-pad,ow+kw-pad]) (zero outside the image) and
+ * db[co] = sum dy[n,co,oh,ow] (db nullable); the input is always taken as binarised.  dy enters as its exact
+ * three-plane bf16 split and x as ternary bf16, so every product is exact; the roundings are the MFMA's fp32
+ * accumulation over one K slice, the fp32 partials (and row sums of dy), and one rounding of their sum in
+ * double.  No atomics: deterministic.  Shapes taken (bnn_conv2d_bwd_filter_wide_ok = 1): those
+ * bnn_conv2d_fwd_wide_ok takes with KW <= 9, less the ones whose smallest stage -- (3 + KW) x 2 pieces plus KW x
+ * (rows - 1) round_up(OW, 8) / 8 halo pieces of 1 KiB, rows = min(KH, 9 / KW) -- is beyond 160 KiB of LDS (3x3
+ * up to OW = 192), or whose grids or piece count reach 2^31.  `work` is scratch of
+ * bnn_conv2d_bwd_filter_wide_workspace(...) bytes (0 for a shape not taken), 16-B aligned; it may hold anything
+ * on entry and every call rewrites all it reads (the packed planes and copies, the partials, the row sums).
+ * A shape not taken, a null pointer or a short workspace return BNN_EINVAL with nothing launched; N == 0
+ * zero-fills dw and db and returns 0.  bnn_conv2d_bwd_filter_wide_kernel: the GEMM instance <accumulator
+ * sets, LDS stages> the call launches, its LDS bytes, tap groups, pieces (8 positions) per chunk, K slices,
+ * pieces per slice, live pieces, and the modelled cycles of its fragment reads ("conv_wide_bwd_filter_k<9, 2>
+ * lds=147456 groups=1 chunk=10 splits=125 slice=280 pieces=34816 b128=4"); "" for a shape not taken.  The
+ * entry and the three queries share one decision function.  The string is valid until the calling thread's
+ * next query.  bnn_conv2d_bwd_filter and bnn_conv_kernel are unaffected. */
+int bnn_conv2d_bwd_filter_wide_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                                  int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int64_t bnn_conv2d_bwd_filter_wide_workspace(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                             int64_t KW, int32_t pad);
+int bnn_conv2d_bwd_filter_wide(const float* dy, const float* x, float* dw, float* db, int64_t N, int64_t C, int64_t H,
+                               int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad,
+                               int32_t dil, int32_t groups, void* work, int64_t work_bytes, bnn_stream_t stream);
+const char* bnn_conv2d_bwd_filter_wide_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                              int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+/* Timing hook (not part of the stable contract; tools/conv_wide_bwd_filter_bench.py): the launches later
+ * bnn_conv2d_bwd_filter_wide calls make -- bit 0 the dy pack, bit 1 the x pack, bit 2 the GEMM, bit 3 the
+ * reduce; 15 = all (the default; anything else leaves dw or the workspace as an earlier call made them).
+ * mask < 0 queries. */
+int bnn_conv2d_bwd_filter_wide_set_stages(int32_t mask);
 /* Frozen-model inference (bnn_amd.inference.FrozenCNN): the binary convolution with eval-mode
  * BatchNorm2d -> Hardtanh -> MaxPool2d(2, 2) in its epilogue.  Geometry of both entries: stride 1,
  * dilation 1, groups 1, C == 1 (KW <= 8) or C % 16 == 0 (<= 64, at most 256 output pixels), Co <= 64,
