@@ -27,7 +27,7 @@ from . import functional as BF
 from . import nets
 from .metrics import Meter
 
-__all__ = ["freeze", "from_state", "FrozenMLP", "FrozenCNN"]
+__all__ = ["freeze", "from_state", "FrozenMLP", "FrozenCNN", "freeze_conv_stack", "FrozenConvStack"]
 
 FORMAT = "bnn_amd.frozen/1"
 FORMAT_CNN = "bnn_amd.frozen_cnn/1"
@@ -599,6 +599,202 @@ class FrozenCNN(_Frozen):
             s = _tsign(p).double()
         logits = tF.linear(p.reshape(p.shape[0], -1), t["fc.weight"], t.get("fc.bias"))
         return tF.log_softmax(logits, dim=1), hidden
+
+
+# Fused launches of the frozen wide layers (bnn_conv2d_fwd_wide_bnsign), as functional.CONV_WIDE_CALLS counts
+# the training forward's.
+WIDE_FUSED_CALLS = 0
+
+
+class FrozenConvStack:
+    """Frozen wide-channel blocks BinarizeConv2d -> BatchNorm2d -> Hardtanh(-1, 1) [-> MaxPool2d(2, 2)], the
+    128- to 512-channel stacks of the BinaryNet / VGG-style networks:
+
+        fp32 NCHW -> pack_x -> conv1 [BN-sign(-pool) epilogue] -> FP4 planes on conv2's padded grid
+                  -> conv2 [...] -> ... -> last conv [...] -> int8 signs NCHW
+
+    Each layer is one launch of bnn_conv2d_fwd_wide_bnsign on the weight packed once per device: between two
+    fused layers there is no fp32 map, no BatchNorm pass and no pack, half a byte per activation.  A layer the
+    kernel's plan refuses -- or every layer when ``two_pass = True`` -- runs as binary_conv2d +
+    bnn_bn2d_fwd_eval (+ sign), the form ``model.eval()`` runs, and its producer then hands it int8 signs.
+    Every layer class measured (tools/conv_wide_infer_bench.py) is faster fused, so none is kept on two-pass by
+    default.  No host synchronisation; planes and outputs are kept per (N, device), so a region captured after
+    warm-up allocates nothing -- and ``forward`` returns that kept buffer, which the next call of the same N
+    overwrites.  CPU tensors run a plain-torch restatement (a checking path)."""
+
+    def __init__(self, layers, tensors, eps):
+        self.layers = [tuple(int(e) for e in l) for l in layers]     # per block (C, Co, KH, KW, pad, pool)
+        self.t = dict(tensors)
+        self.eps = tuple(float(e) for e in eps)
+        self.two_pass = False
+        self._buf = {}
+
+    def to(self, device):
+        self.t = {k: v.to(device) for k, v in self.t.items()}
+        self._buf = {}
+        return self
+
+    @property
+    def device(self):
+        return self.t["conv1.sign"].device
+
+    def _bn(self, i):
+        t = self.t
+        return t[f"bn{i}.mean"], t[f"bn{i}.invstd"], t.get(f"bn{i}.gamma"), t.get(f"bn{i}.beta")
+
+    def _shapes(self, H, W):
+        """Per block (C, Co, KH, KW, pad, pool, H, W, PH, PW) along the stack."""
+        out = []
+        for i, (C, Co, KH, KW, pad, pool) in enumerate(self.layers, 1):
+            OH, OW = H + 2 * pad - KH + 1, W + 2 * pad - KW + 1
+            if OH <= 0 or OW <= 0 or (pool and (OH % 2 or OW % 2)):
+                raise ValueError(f"FrozenConvStack: block {i} gets a {H} x {W} map it cannot convolve"
+                                 + (" and pool" if pool else ""))
+            PH, PW = (OH // 2, OW // 2) if pool else (OH, OW)
+            out.append((C, Co, KH, KW, pad, pool, H, W, PH, PW))
+            H, W = PH, PW
+        return out
+
+    def _cached(self, key, make):
+        v = self._buf.get(key)
+        if v is None:
+            v = self._buf[key] = make()
+        return v
+
+    def _wq(self, i, device):
+        """Block i's weight in the wide layers' packed layout, packed on first use per device."""
+        C, Co, KH, KW = self.layers[i - 1][:4]
+
+        def make():
+            wq = torch.empty((int(L.lib().bnn_conv2d_wide_wq_bytes(C, Co, KH, KW)),), dtype=torch.uint8, device=device)
+            L.call("bnn_conv2d_wide_pack_w", self.t[f"conv{i}.sign"].float().contiguous(), wq, C, Co, KH, KW, L.stream())
+            return wq
+        return self._cached(("wq", i, str(device)), make)
+
+    def _two_pass_block(self, i, x, shp):
+        """Block i as model.eval() runs it: conv (binarising x) -> eval BatchNorm2d + Hardtanh (+ pool), fp32."""
+        C, Co, KH, KW, pad, pool, H, W, PH, PW = shp
+        N = x.shape[0]
+        wf = self._cached(("wf", i, str(x.device)), lambda: self.t[f"conv{i}.sign"].float().contiguous())
+        z = BF.binary_conv2d(x, wf, self.t.get(f"conv{i}.bias"), True, 1, pad, 1, 1)
+        mean, _, gamma, beta = self._bn(i)
+        if (z.shape[2] * z.shape[3]) % 4 == 0:
+            y = torch.empty((N, Co, PH, PW), dtype=torch.float32, device=x.device)
+            ws = torch.empty((L.lib().bnn_bn2d_workspace(N, Co),), dtype=torch.uint8, device=x.device)
+            L.call("bnn_bn2d_fwd_eval", z, N, Co, z.shape[2], z.shape[3], gamma, beta, mean, self.t[f"bn{i}.var"],
+                   float(self.eps[i - 1]), y, 1, 2 if pool else 0, ws, L.stream())
+            return y
+        y = tF.hardtanh(tF.batch_norm(z, mean, self.t[f"bn{i}.var"], gamma, beta, False, 0.0, self.eps[i - 1]))
+        return tF.max_pool2d(y, 2, 2) if pool else y
+
+    def forward(self, x):
+        """int8 signs [N, Co, PH, PW] of the last block for fp32 NCHW ``x``."""
+        C0 = self.layers[0][0]
+        if x.dim() != 4 or x.shape[1] != C0 or x.dtype != torch.float32:
+            raise ValueError(f"FrozenConvStack: expects float32 [N, {C0}, H, W] (got {x.dtype} {tuple(x.shape)})")
+        shapes = self._shapes(x.shape[2], x.shape[3])
+        if not x.is_cuda:
+            return self._forward_cpu(x, shapes)
+        if self.device != x.device:
+            raise RuntimeError(f"FrozenConvStack on {self.device} got an input on {x.device}; call .to(device)")
+        global WIDE_FUSED_CALLS
+        N, dev = x.shape[0], str(x.device)
+        last = shapes[-1]
+        out = self._cached(("out", N, dev, last[1], last[8], last[9]),
+                           lambda: torch.empty((N, last[1], last[8], last[9]), dtype=torch.int8, device=x.device))
+        if N == 0:
+            return out
+        ok = L.lib().bnn_conv2d_fwd_wide_bnsign_ok
+        fused = [not self.two_pass and ok(N, C, H, W, Co, KH, KW, 1, pad, 1, 1, pool, 1, 0, 0, 0) == 1
+                 for C, Co, KH, KW, pad, pool, H, W, PH, PW in shapes]
+        cur, form = (x if x.is_contiguous() else x.contiguous()), "f32"
+        for i, shp in enumerate(shapes, 1):
+            C, Co, KH, KW, pad, pool, H, W, PH, PW = shp
+            is_last = i == len(shapes)
+            if not fused[i - 1]:
+                y = self._two_pass_block(i, cur.float() if form == "s8" else cur, shp)
+                if is_last:
+                    out.copy_(_tsign(y))
+                cur, form = y, "f32"
+                continue
+            if form != "planes":      # the stack's input, or what a two-pass block wrote: tsign is the pack's
+                nb = int(L.lib().bnn_conv2d_wide_planes_bytes(N, C, H, W, KH, KW, pad))
+                planes = self._cached(("planes", i, N, dev, H, W), lambda: torch.empty((nb,), dtype=torch.uint8, device=x.device))
+                L.call("bnn_conv2d_wide_pack_x", cur, planes, N, C, H, W, KH, KW, pad, L.stream())
+                cur, form = planes, "planes"
+            mean, invstd, gamma, beta = self._bn(i)
+            K2 = (0, 0, 0)
+            if not is_last and fused[i]:
+                nxt = self.layers[i]
+                if ok(N, C, H, W, Co, KH, KW, 1, pad, 1, 1, pool, 0, nxt[2], nxt[3], nxt[4]) == 1:
+                    K2 = (nxt[2], nxt[3], nxt[4])
+            to_planes = K2[0] > 0
+            if to_planes:
+                nb = int(L.lib().bnn_conv2d_wide_planes_bytes(N, Co, PH, PW, *K2))
+                dst = self._cached(("planes", i + 1, N, dev, PH, PW), lambda: torch.empty((nb,), dtype=torch.uint8, device=x.device))
+            elif is_last:
+                dst = out
+            else:
+                dst = self._cached(("s8", i, N, dev, PH, PW),
+                                   lambda: torch.empty((N, Co, PH, PW), dtype=torch.int8, device=x.device))
+            L.call("bnn_conv2d_fwd_wide_bnsign", cur, self._wq(i, x.device), self.t.get(f"conv{i}.bias"), mean, invstd,
+                   gamma, beta, dst, N, C, H, W, Co, KH, KW, pad, pool, 0 if to_planes else 1, *K2, L.stream())
+            WIDE_FUSED_CALLS += 1
+            cur, form = dst, ("planes" if to_planes else "s8")
+        return out
+
+    __call__ = forward
+
+    def _forward_cpu(self, x, shapes):
+        s = _tsign(x).double()
+        for i, (C, Co, KH, KW, pad, pool, H, W, PH, PW) in enumerate(shapes, 1):
+            z = tF.conv2d(s, self.t[f"conv{i}.sign"].double(), None, 1, pad).float()     # exact integer sums
+            if f"conv{i}.bias" in self.t:
+                z = z + self.t[f"conv{i}.bias"].view(1, -1, 1, 1)
+            y = tF.hardtanh(_bn_y_cpu(z, *(None if v is None else v.view(1, -1, 1, 1) for v in self._bn(i))))
+            s = _tsign(tF.max_pool2d(y, 2, 2) if pool else y).double()
+        return s.to(torch.int8)
+
+
+def freeze_conv_stack(blocks):
+    """Snapshot wide binarized conv blocks for inference: an iterable of
+    nn.Sequential(BinarizeConv2d, BatchNorm2d, Hardtanh(-1, 1)[, MaxPool2d(2, 2)]) -> FrozenConvStack.  The
+    weight source is ``weight.org`` when the layer carries one.  Raises ValueError for any other chain, a
+    BatchNorm without running statistics, a convolution that is not stride 1 / dilation 1 / one group / square
+    padding, or one that takes unbinarised images (in_channels == 3)."""
+    from .nn import BinarizeConv2d
+    import torch.nn as tnn
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    t, layers, eps = {}, [], []
+    for i, seq in enumerate(blocks, 1):
+        ok = (isinstance(seq, tnn.Sequential) and len(seq) in (3, 4) and isinstance(seq[0], BinarizeConv2d)
+              and isinstance(seq[1], tnn.BatchNorm2d) and isinstance(seq[2], tnn.Hardtanh)
+              and seq[2].min_val == -1.0 and seq[2].max_val == 1.0)
+        if ok and len(seq) == 4:
+            pool = seq[3]
+            ok = (isinstance(pool, tnn.MaxPool2d) and pair(pool.kernel_size) == (2, 2) and pair(pool.stride) == (2, 2)
+                  and pair(pool.padding) == (0, 0) and pair(pool.dilation) == (1, 1) and not pool.ceil_mode)
+        if not ok:
+            raise ValueError(f"freeze_conv_stack: block {i} must be BinarizeConv2d -> BatchNorm2d -> Hardtanh(-1, 1) "
+                             "[-> MaxPool2d(2, 2) without padding or ceil_mode]")
+        conv, bn = seq[0], seq[1]
+        if (tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.groups != 1
+                or isinstance(conv.padding, str) or conv.padding[0] != conv.padding[1] or conv.in_channels == 3):
+            raise ValueError(f"freeze_conv_stack: block {i}'s convolution must have stride 1, dilation 1, one group, "
+                             "square padding and a binarised input (in_channels != 3)")
+        w = _latent(conv.weight).float()
+        Co, C, KH, KW = w.shape
+        if layers and layers[-1][1] != C:
+            raise ValueError(f"freeze_conv_stack: block {i} takes {C} channels, block {i - 1} gives {layers[-1][1]}")
+        layers.append((C, Co, KH, KW, conv.padding[0], 2 if len(seq) == 4 else 0))
+        t[f"conv{i}.sign"] = _tsign(w)
+        if conv.bias is not None:
+            t[f"conv{i}.bias"] = conv.bias.detach().float().clone()
+        _snapshot_bn(t, i, bn, _invstd, f"block {i}'s BatchNorm2d")
+        eps.append(bn.eps)
+    if not layers:
+        raise ValueError("freeze_conv_stack: no blocks")
+    return FrozenConvStack(layers, t, eps)
 
 
 _CLASSES = {cls.FORMAT: cls for cls in (FrozenMLP, FrozenCNN)}

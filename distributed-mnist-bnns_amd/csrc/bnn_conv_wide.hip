@@ -308,6 +308,50 @@ BNN_API const char* bnn_conv2d_fwd_wide_kernel(int64_t N, int64_t C, int64_t H, 
   return buf;
 }
 
+// The two packed operands as entries of their own (frozen inference packs a weight once and an input only
+// in front of the first layer, bnn_conv_wide_infer.hip): the layouts, sizes and kernels of this unit.  The
+// planes of an activation do not depend on the consumer's Co, so its plan is made for one 128-row tile.
+BNN_API int64_t bnn_conv2d_wide_planes_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW,
+                                             int32_t pad) {
+  WidePlan p;
+  return wide_plan(N, C, H, W, WD_TC, KH, KW, 1, pad, 1, 1, &p) ? (int64_t)p.ncb * p.Ppad * 32 : 0;
+}
+
+BNN_API int64_t bnn_conv2d_wide_wq_bytes(int64_t C, int64_t Co, int64_t KH, int64_t KW) {
+  if (C <= 0 || C % 64 != 0 || Co <= 0 || Co > (1 << 20) || KH <= 0 || KW <= 0 || KH > 64 || KW > 64 ||
+      C * KH * KW >= (1 << 24))
+    return 0;
+  return C / 64 * KH * KW * round_up(Co, WD_TC) * 32;
+}
+
+BNN_API int bnn_conv2d_wide_pack_w(const float* w_latent, void* wq, int64_t C, int64_t Co, int64_t KH, int64_t KW,
+                                   void* stream) {
+  if (bnn_conv2d_wide_wq_bytes(C, Co, KH, KW) == 0 || !w_latent || !wq || !aligned16(wq)) {
+    set_error("bnn_conv2d_wide_pack_w: null or unaligned pointer, or C %% 64 != 0 / C KH KW >= 2^24");
+    return kErrInval;
+  }
+  const int Cop = (int)round_up(Co, WD_TC), taps = (int)(KH * KW), ncb = (int)(C / 64);
+  const int64_t nw = (int64_t)Cop * ncb * 2 * taps;
+  hipLaunchKernelGGL(conv_wide_pack_w_k, dim3((unsigned)((nw + WD_T - 1) / WD_T)), dim3(WD_T), 0,
+                     reinterpret_cast<hipStream_t>(stream), w_latent, static_cast<uint8_t*>(wq), C, Co, Cop, taps, ncb);
+  return check_launch("bnn_conv2d_wide_pack_w");
+}
+
+BNN_API int bnn_conv2d_wide_pack_x(const float* x, void* planes, int64_t N, int64_t C, int64_t H, int64_t W,
+                                   int64_t KH, int64_t KW, int32_t pad, void* stream) {
+  WidePlan p;
+  if (!wide_plan(N, C, H, W, WD_TC, KH, KW, 1, pad, 1, 1, &p) || !x || !planes || !aligned16(planes)) {
+    set_error("bnn_conv2d_wide_pack_x: null or unaligned pointer, or a geometry bnn_conv2d_wide_planes_bytes "
+              "gives 0 bytes for");
+    return kErrInval;
+  }
+  if (N == 0) return 0;
+  const WidePackX px{C, H, W, p.P, p.Ppad, N * p.Hp, p.pad, p.Hp, p.Wp, p.ncb};
+  hipLaunchKernelGGL(conv_wide_pack_x_k, dim3((unsigned)((px.rows + 1) * p.ncb)), dim3(WD_T), 0,
+                     reinterpret_cast<hipStream_t>(stream), x, static_cast<uint8_t*>(planes), px);
+  return check_launch("bnn_conv2d_wide_pack_x");
+}
+
 BNN_API int bnn_conv2d_fwd_wide_set_stages(int32_t mask) {
   if (mask >= 0) g_wide_stages = mask & 7;
   return g_wide_stages;

@@ -428,6 +428,59 @@ const char* bnn_conv2d_fwd_wide_kernel(int64_t N, int64_t C, int64_t H, int64_t 
  * bnn_conv2d_fwd_wide calls make -- bit 0 the input pack, bit 1 the weight pack, bit 2 the GEMM; 7 = all
  * (the default; anything else leaves y or the workspace as an earlier call made them).  mask < 0 queries. */
 int bnn_conv2d_fwd_wide_set_stages(int32_t mask);
+/* The wide layers' two packed operands, part of the contract since frozen inference
+ * (bnn_amd.inference.FrozenConvStack) keeps them between calls.  All 16-B aligned.
+ *   planes  the activation of a layer (N, C, H, W) as the (KH, KW, pad) layer that consumes it reads it:
+ *           uint8 [C / 64][Ppad][32], one plane per 64-channel block, one 32-B row per position
+ *           p = (n Hp + h + pad) Wp + w + pad of the zero-padded grid (Hp = H + 2 pad, Wp = W + 2 pad).
+ *           Nibble j of a row (byte j / 2, low nibble for even j) is the FP4 (e2m1) code of the sign of
+ *           channel j of the block: +1 = 0x2, -1 = 0xA, 0 = 0x0.  Halo positions and the tail
+ *           N Hp Wp .. Ppad - 1 are zero.  Ppad = 128 (ceil(N Hp Wp / 128) - 1) +
+ *           round_up(128 + (KH-1) Wp + KW-1, 32), so that the last tile's window stays inside the plane.
+ *           bnn_conv2d_wide_planes_bytes = C / 64 * Ppad * 32, or 0 for a geometry no wide layer takes
+ *           (bnn_conv2d_fwd_wide_ok's checks apart from the channel-width threshold).
+ *   wq      the weight [Co][C][KH][KW] as uint8 [C / 64][KH KW][Cop][32], Cop = round_up(Co, 128): row
+ *           (cb, kh KW + kw, co), nibble j = the code of tsign(w[co][64 cb + j][kh][kw]); rows Co .. Cop - 1
+ *           zero.  bnn_conv2d_wide_wq_bytes = C / 64 * KH KW * Cop * 32, or 0 (C % 64 != 0, C KH KW >= 2^24).
+ * bnn_conv2d_wide_pack_x / _pack_w write them from fp32 NCHW / the latent weight (every byte, halo and tail
+ * included): the passes bnn_conv2d_fwd_wide runs in front of its GEMM.
+ *
+ * bnn_conv2d_fwd_wide_bnsign: the frozen layer -- conv of `planes` with `wq`, then per element
+ * x = fl(I + bias[co]), y = fmaf((x - mean[co]) * invstd[co], gamma[co], beta[co]) (bias / gamma / beta
+ * nullable) and the ternary sign of eval-mode BatchNorm2d -> Hardtanh -> MaxPool2d(2, 2) when pool = 2 (even
+ * OH and OW) or without a pool when pool = 0: +1 if some y of the window > 0, else 0 if some y == 0, else
+ * -1, and 0 if the window holds a NaN (bnn_conv2d_fwd_bnsign_pool's rule).  With [PH][PW] the (pooled) map,
+ *   out_form 0: `out` = the planes of the (N, Co, PH, PW) activation for a consumer layer (KH2, KW2, pad2),
+ *               Co % 64 == 0; every byte of bnn_conv2d_wide_planes_bytes(N, Co, PH, PW, KH2, KW2, pad2) is
+ *               written by every call;
+ *   out_form 1: `out` = int8 signs [N][Co][PH][PW], any Co (KH2 / KW2 / pad2 ignored).
+ * Shapes taken (bnn_conv2d_fwd_wide_bnsign_ok = 1): stride 1, dilation 1, one group and what
+ * bnn_conv2d_fwd_wide_ok takes, 64 -> 64 channels as well; pool 0 or 2; the staged window of the position
+ * mapping within the LDS; for out_form 0 a consumer geometry with planes_bytes > 0.  Anything else, a null
+ * pointer or an unaligned planes / wq / planes output returns BNN_EINVAL with nothing launched; N == 0
+ * returns 0.  One launch, no atomics, deterministic.  bnn_conv2d_fwd_wide_bnsign_kernel: the instance with
+ * its LDS bytes and the modelled cycles of its worst fragment read, over the lane patterns of the pooled
+ * position mapping ("conv_wide_bnsign_k<2,2,0> lds=94208 b128=8"; 4 = conflict-free); "" for a shape not
+ * taken.  The entry and the two queries share one decision function. */
+int64_t bnn_conv2d_wide_planes_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH, int64_t KW,
+                                     int32_t pad);
+int64_t bnn_conv2d_wide_wq_bytes(int64_t C, int64_t Co, int64_t KH, int64_t KW);
+int bnn_conv2d_wide_pack_w(const float* w_latent, void* wq, int64_t C, int64_t Co, int64_t KH, int64_t KW,
+                           bnn_stream_t stream);
+int bnn_conv2d_wide_pack_x(const float* x, void* planes, int64_t N, int64_t C, int64_t H, int64_t W, int64_t KH,
+                           int64_t KW, int32_t pad, bnn_stream_t stream);
+int bnn_conv2d_fwd_wide_bnsign_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                                  int32_t stride, int32_t pad, int32_t dil, int32_t groups, int32_t pool,
+                                  int32_t out_form, int64_t KH2, int64_t KW2, int32_t pad2);
+const char* bnn_conv2d_fwd_wide_bnsign_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                              int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups,
+                                              int32_t pool, int32_t out_form, int64_t KH2, int64_t KW2,
+                                              int32_t pad2);
+int bnn_conv2d_fwd_wide_bnsign(const void* planes, const void* wq, const float* bias, const float* mean,
+                               const float* invstd, const float* gamma, const float* beta, void* out, int64_t N,
+                               int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t pad,
+                               int32_t pool, int32_t out_form, int64_t KH2, int64_t KW2, int32_t pad2,
+                               bnn_stream_t stream);
 /* The input gradient of the same wide-channel layers, on the bf16 MFMA:
  * dx[n,c,ih,iw] = sum_{co,kh,kw} dy[n,co,ih+pad-kh,iw+pad-kw] * sign(w_latent[co,c,kh,kw]), dy [N][Co][OH][OW]
  * and dx [N][C][H][W] fp32.  dy enters as its exact three-plane bf16 split and the weights are ternary, so
