@@ -5,19 +5,11 @@ bit for bit."""
 import pytest
 import torch
 
+import conv_wide_cases as CW
+
 pytestmark = pytest.mark.gpu
 
-# (N, C, H, W, Co, KH, KW, pad)
-SHAPES = [
-    (1, 64, 5, 7, 65, 3, 3, 1),        # Co tail, plane smaller than a tile
-    (3, 128, 9, 11, 129, 3, 3, 1),     # two channel blocks, two co tiles, tiles crossing image boundaries
-    (2, 64, 6, 6, 128, 1, 1, 0),       # no shift
-    (2, 64, 7, 9, 72, 3, 3, 2),        # pad = K - 1
-    (1, 64, 12, 13, 80, 5, 5, 0),      # 5x5 (one LDS stage), no padding
-    (2, 192, 8, 8, 16, 1, 3, 0),       # non-square kernel, narrow Co, three blocks
-    (5, 64, 33, 34, 130, 3, 3, 1),     # more positions than one round of tiles per image, odd Wp
-]
-NO_BIAS = SHAPES[3]
+SHAPES, NO_BIAS = CW.SHAPES, CW.NO_BIAS         # the seven shapes the family was merged with; the table has more
 
 
 def _inputs(shape, bias=True):
@@ -55,12 +47,13 @@ def _wide(x, w, b, shape, fill=None, short=0):
     return rc, y.cpu()
 
 
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", CW.for_op("fwd"))
 def test_wide_forward_equals_float64_reference(shape):
     from bnn_amd import _lib as L
     N, C, H, W, Co, KH, KW, pad = shape
     x, w, b = _inputs(shape, bias=shape is not NO_BIAS)
     ref = _reference(x, w, b, pad)
+    assert C * KH * KW < 2 ** 24 and bool(ref.ne(0).any())           # the integer sums are exact in fp32
     rc, y = _wide(x, w, b, shape)
     assert rc == 0 and torch.equal(y, ref)
     rc, y = _wide(x, w, b, shape, fill=0xFF)             # the halo and the tail are written, not assumed
@@ -111,3 +104,54 @@ def test_module_takes_the_wide_path_with_the_same_bits(mode, monkeypatch):
         got[on] = (y.detach(), conv.weight.grad.clone(), conv.bias.grad.clone(), x.grad.clone())
     for a, b in zip(got[True], got[False]):
         assert torch.equal(a, b)
+
+
+def test_empty_batch_returns_zero_and_writes_nothing():
+    """N = 0 at the C ABI (functional.py never gets here: it answers an empty batch itself).  An empty tensor's
+    data_ptr() is null and the entry refuses null, so the pointers are small non-empty tensors."""
+    from bnn_amd import _lib as L
+    N, C, H, W, Co, KH, KW, pad = CW.EMPTY
+    x, w, b = (torch.ones(16, device="cuda") for _ in range(3))
+    y = torch.full((64,), 7.0, device="cuda")
+    ws = torch.full((L.lib().bnn_conv2d_fwd_wide_workspace(*CW.EMPTY),), 0xFF, dtype=torch.uint8, device="cuda")
+    assert ws.numel() > 0
+    rc = L.lib().bnn_conv2d_fwd_wide(x, w, b, y, N, C, H, W, Co, KH, KW, 1, pad, 1, 1, ws, ws.numel(), L.stream())
+    torch.cuda.synchronize()
+    assert rc == 0 and bool((y == 7.0).all()) and bool((ws == 0xFF).all())
+
+
+def test_module_round_trip_on_a_non_square_kernel(monkeypatch):
+    """BinarizeConv2d(64, 72, (5, 3), padding=1), forward and backward, with the three CONV_WIDE* switches on and
+    off together (the table's shape whose filter gradient has a short last tap group): y is equal bit for bit,
+    the three gradients meet the bar of tests/test_gpu_parity.py (1e-5 norm-wise) against float64 either way,
+    and each wide entry is called exactly once when its switch is on."""
+    import test_gpu_conv_wide_bwd as B
+    import test_gpu_conv_wide_bwd_filter as BF_
+    from bnn_amd import functional as BF
+    from models.binarized_modules import BinarizeConv2d
+    assert (2, 64, 7, 9, 72, 5, 3, 1) in CW.NEW_SHAPES
+    torch.manual_seed(11)
+    conv = BinarizeConv2d(64, 72, (5, 3), padding=1).cuda().train()
+    x0 = torch.randn(2, 64, 7, 9, device="cuda")
+    dy = torch.randn(2, 72, 5, 9, device="cuda")
+    w = conv.weight.detach().cpu()
+    rx = B._reference(dy.cpu(), w, 1)
+    rw, rb = BF_._reference(dy.cpu(), x0.cpu(), (72, 64, 5, 3), 1)
+    counters = ("CONV_WIDE_CALLS", "CONV_WIDE_BWD_CALLS", "CONV_WIDE_BWD_FILTER_CALLS")
+    ys = {}
+    for on in (True, False):
+        for name in ("CONV_WIDE", "CONV_WIDE_BWD", "CONV_WIDE_BWD_FILTER"):
+            monkeypatch.setattr(BF, name, on)
+        calls = [getattr(BF, c) for c in counters]
+        x = x0.clone().requires_grad_(True)
+        conv.zero_grad()
+        y = conv(x)
+        y.backward(dy)
+        torch.cuda.synchronize()
+        assert [getattr(BF, c) - c0 for c, c0 in zip(counters, calls)] == [int(on)] * 3
+        for name, grad, ref in (("x", x.grad, rx), ("weight", conv.weight.grad, rw), ("bias", conv.bias.grad, rb)):
+            err = float((grad.cpu().double() - ref).norm() / ref.norm())
+            print(f"CONV_WIDE*={on}: {name}.grad rel err {err:.3e}")
+            assert err < 1e-5
+        ys[on] = y.detach()
+    assert torch.equal(ys[True], ys[False])

@@ -4,6 +4,7 @@ every partial sum in any order is representable in fp32: the comparisons are bit
 import pytest
 import torch
 
+import conv_wide_cases as CW
 from test_gpu_conv_wide import SHAPES          # (N, C, H, W, Co, KH, KW, pad): the forward test's seven
 
 pytestmark = pytest.mark.gpu
@@ -35,13 +36,17 @@ def _reference(dy, w, pad):
 
 
 @pytest.mark.parametrize("kind", ["dense", "lattice"])
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", CW.for_op("data"))
 def test_wide_input_gradient_equals_float64_reference(shape, kind):
     from bnn_amd import _lib as L
     N, C, H, W, Co, KH, KW, pad = shape
     dy, w = _inputs(shape, kind)
     ref = _reference(dy, w, pad).float()
     assert ref.shape == (N, C, H, W) and bool(ref.ne(0).any())
+    if kind == "dense":                                  # every partial sum is an integer below 2^24
+        assert float(_reference(dy.abs(), w.abs(), pad).max()) < 2 ** 24
+    else:                                                # at most one non-zero term per dX element
+        assert int(_reference(dy.ne(0).float(), torch.ones_like(w), pad).max()) <= 1
     dyd, wd = dy.cuda(), w.cuda()
     ws = torch.empty(L.lib().bnn_conv2d_bwd_data_wide_workspace(N, C, H, W, Co, KH, KW, pad), dtype=torch.uint8, device="cuda")
     dx = torch.empty(N, C, H, W, device="cuda")
@@ -71,6 +76,19 @@ def test_short_workspace_and_refused_shape_launch_nothing(stride, short):
     torch.cuda.synchronize()
     assert rc == -1 and bool((dx == 7.0).all())
     assert (b"workspace" in L.lib().bnn_last_error()) == bool(short)
+
+
+def test_empty_batch_returns_zero_and_writes_nothing():
+    """N = 0 at the C ABI, with small non-empty tensors as the pointers (the entry refuses null)."""
+    from bnn_amd import _lib as L
+    N, C, H, W, Co, KH, KW, pad = CW.EMPTY
+    dy, w = torch.ones(16, device="cuda"), torch.ones(16, device="cuda")
+    dx = torch.full((64,), 7.0, device="cuda")
+    ws = torch.full((L.lib().bnn_conv2d_bwd_data_wide_workspace(*CW.EMPTY),), 0xFF, dtype=torch.uint8, device="cuda")
+    assert ws.numel() > 0
+    rc = L.lib().bnn_conv2d_bwd_data_wide(dy, w, dx, N, C, H, W, Co, KH, KW, 1, pad, 1, 1, ws, ws.numel(), L.stream())
+    torch.cuda.synchronize()
+    assert rc == 0 and bool((dx == 7.0).all()) and bool((ws == 0xFF).all())
 
 
 def test_module_takes_the_wide_input_gradient(monkeypatch):

@@ -6,10 +6,11 @@ import re
 import pytest
 import torch
 
+import conv_wide_cases as CW
 from test_gpu_conv_wide import SHAPES          # (N, C, H, W, Co, KH, KW, pad): the forward test's seven
 
 pytestmark = pytest.mark.gpu
-NO_DB = SHAPES[3]
+NO_DB = CW.NO_DB                               # SHAPES[3]; CW.NO_DB_NEW is the multi-pass shape run without db
 
 
 def _inputs(shape, kind):
@@ -36,19 +37,26 @@ def _reference(dy, x, wshape, pad):
     return torch.nn.grad.conv2d_weight(sx, wshape, dy.double(), padding=pad), dy.double().sum((0, 2, 3))
 
 
-@pytest.mark.parametrize("kind", ["dense", "onehot"])
-@pytest.mark.parametrize("shape", SHAPES)
-def test_wide_filter_gradient_equals_float64_reference(shape, kind):
+def _check_exactness(dy, x, wshape, pad, kind):
+    """The pre-condition of the bit-for-bit comparison, from the reference itself."""
+    if kind == "dense":                                  # every partial sum is an integer below 2^24
+        aw, ab = _reference(dy.abs(), x.abs(), wshape, pad)
+        assert float(aw.max()) < 2 ** 24 and float(ab.max()) < 2 ** 24
+    else:                                                # at most one non-zero term per dw and db element
+        nw, nb = _reference(dy.ne(0).float(), torch.ones_like(x), wshape, pad)
+        assert int(nw.max()) <= 1 and int(nb.max()) <= 1
+
+
+def _run_twice(shape, dy, x, rw, rb, with_db):
+    """The entry on a fresh workspace, then on one filled with 0xFF with dw and db pre-filled: everything read is
+    rewritten, not assumed; dw and db are overwritten."""
     from bnn_amd import _lib as L
     N, C, H, W, Co, KH, KW, pad = shape
-    dy, x = _inputs(shape, kind)
-    rw, rb = (t.float() for t in _reference(dy, x, (Co, C, KH, KW), pad))
-    assert bool(rw.ne(0).any()) and bool(rb.ne(0).any())
     dyd, xd = dy.cuda(), x.cuda()
     ws = torch.empty(L.lib().bnn_conv2d_bwd_filter_wide_workspace(N, C, H, W, Co, KH, KW, pad), dtype=torch.uint8, device="cuda")
     dw = torch.empty(Co, C, KH, KW, device="cuda")
-    db = None if shape is NO_DB else torch.empty(Co, device="cuda")
-    for fill in (False, True):                           # everything read is rewritten, not assumed; dw, db overwritten
+    db = torch.empty(Co, device="cuda") if with_db else None
+    for fill in (False, True):
         if fill:
             ws.fill_(0xFF)
             dw.fill_(7.0)
@@ -58,6 +66,47 @@ def test_wide_filter_gradient_equals_float64_reference(shape, kind):
                L.stream())
         assert torch.equal(dw.cpu(), rw)
         assert db is None or torch.equal(db.cpu(), rb)
+
+
+@pytest.mark.parametrize("kind", ["dense", "onehot"])
+@pytest.mark.parametrize("shape", CW.for_op("filt"))
+def test_wide_filter_gradient_equals_float64_reference(shape, kind):
+    N, C, H, W, Co, KH, KW, pad = shape
+    dy, x = _inputs(shape, kind)
+    rw, rb = (t.float() for t in _reference(dy, x, (Co, C, KH, KW), pad))
+    assert bool(rw.ne(0).any()) and bool(rb.ne(0).any())
+    _check_exactness(dy, x, (Co, C, KH, KW), pad, kind)
+    _run_twice(shape, dy, x, rw, rb, with_db=shape is not NO_DB)
+
+
+@pytest.mark.parametrize("kind", ["dense", "onehot"])
+def test_null_db_on_a_multi_pass_shape(kind):
+    """db = None on a row of three 64-column passes: pack_dy_k carries its row sum over the passes and then has
+    nowhere to store it; dw is exact all the same."""
+    shape = CW.NO_DB_NEW
+    N, C, H, W, Co, KH, KW, pad = shape
+    assert W + 2 * pad - KW + 1 > 128
+    dy, x = _inputs(shape, kind)
+    rw, rb = (t.float() for t in _reference(dy, x, (Co, C, KH, KW), pad))
+    assert bool(rw.ne(0).any())
+    _check_exactness(dy, x, (Co, C, KH, KW), pad, kind)
+    _run_twice(shape, dy, x, rw, rb, with_db=False)
+
+
+def test_empty_batch_writes_exact_zeros():
+    """N = 0 at the C ABI, with small non-empty tensors as the input pointers (the entry refuses null): the
+    reduce runs over no slices and no rows and writes zeros over all of dw and db."""
+    from bnn_amd import _lib as L
+    N, C, H, W, Co, KH, KW, pad = CW.EMPTY
+    dy, x = torch.ones(16, device="cuda"), torch.ones(16, device="cuda")
+    ws = torch.full((L.lib().bnn_conv2d_bwd_filter_wide_workspace(*CW.EMPTY),), 0xFF, dtype=torch.uint8, device="cuda")
+    assert ws.numel() > 0
+    dw = torch.full((Co, C, KH, KW), 7.0, device="cuda")
+    db = torch.full((Co,), 7.0, device="cuda")
+    rc = L.lib().bnn_conv2d_bwd_filter_wide(dy, x, dw, db, N, C, H, W, Co, KH, KW, 1, pad, 1, 1, ws, ws.numel(), L.stream())
+    torch.cuda.synchronize()
+    assert rc == 0 and bool((dw.view(torch.int32) == 0).all()) and bool((db.view(torch.int32) == 0).all())
+    assert bool((ws == 0xFF).all())                      # nothing is packed
 
 
 def test_a_shape_runs_several_k_slices_with_a_short_last_one():

@@ -7,23 +7,17 @@ x - mean is exact and never within 0.25 of zero: fp32 and float64 agree on every
 mean == bias (an integer) and beta = 0, so y == 0 exactly wherever I == 0; channel 1 has a negative gamma;
 channel 2 has beta = NaN (expected 0 everywhere).  Outside channels 0 and 2 the float64 |y| of these seeds is
 at least 0.0166 (beta = invstd gamma k / 2 keeps it off zero; the smallest is case 3's, the chain's is 0.0192),
-five orders above fp32's rounding.  Every comparison is torch.equal over the whole buffer."""
+five orders above fp32's rounding; over the whole of tests/conv_wide_cases.py it is at least 0.0138 (the
+130-column case's), and each test asserts its own against 0.01 before it launches.  Every comparison is torch.equal over the whole buffer."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_wide_cases as CW
+
 pytestmark = pytest.mark.gpu
 
-# (N, C, H, W, Co, KH, KW, pad, pool, consumer (K2, pad2) or None for int8 signs NCHW)
-CASES = [
-    (1, 64, 6, 6, 65, 3, 3, 1, 0, None),          # Co tail, plane smaller than a tile
-    (3, 128, 10, 12, 128, 3, 3, 1, 2, (3, 1)),    # two blocks; windows and tiles crossing image boundaries
-    (2, 64, 8, 8, 64, 1, 1, 0, 2, (1, 0)),        # no shift; consumer without halo
-    (2, 64, 6, 10, 192, 3, 3, 2, 2, (5, 2)),      # pad = K - 1; wide halo; three output blocks
-    (1, 64, 12, 14, 80, 5, 5, 0, 2, None),        # one LDS stage
-    (5, 64, 34, 34, 130, 3, 3, 1, 2, None),       # more windows than one round of tiles; row ends inside a wave
-    (2, 192, 9, 7, 64, 3, 3, 1, 0, (3, 1)),       # odd sizes without pool
-]
+CASES = CW.INFER_CASES                         # the seven cases the layer was merged with; the table has more
 GUARD = 256
 
 
@@ -52,11 +46,13 @@ def _inputs(case):
 
 
 def _reference(x, w, bias, mean, invstd, gamma, beta, pad, pool):
-    """(int8 signs [N, Co, PH, PW], the float64 y before Hardtanh)."""
+    """(int8 signs [N, Co, PH, PW], the float64 y before Hardtanh).  A bias, gamma or beta of None is 0, 1, 0."""
     sx, sw = (torch.nan_to_num(torch.sign(t), nan=0.0).double() for t in (x, w))
-    z = (F.conv2d(sx, sw, padding=pad) + bias.double().view(1, -1, 1, 1)).float()
-    v = lambda t: t.double().view(1, -1, 1, 1)
-    y = (z.double() - v(mean)) * v(invstd) * v(gamma) + v(beta)
+    z = F.conv2d(sx, sw, padding=pad)
+    if bias is not None:
+        z = (z + bias.double().view(1, -1, 1, 1)).float()
+    v = lambda t, none: none if t is None else t.double().view(1, -1, 1, 1)
+    y = (z.double() - v(mean, None)) * v(invstd, None) * v(gamma, 1.0) + v(beta, 0.0)
     h = F.hardtanh(y)
     return _tsign(F.max_pool2d(h, 2, 2) if pool else h), y
 
@@ -81,7 +77,7 @@ def L():
 def _run(L, case, tensors, cons):
     """The fused entry on pack_x's planes and pack_w's weight; out pre-filled with 0xFF.  (rc, out on the CPU)."""
     N, C, H, W, Co, KH, KW, pad, pool, _ = case
-    x, w, bias, mean, invstd, gamma, beta = (t.cuda() for t in tensors)
+    x, w, bias, mean, invstd, gamma, beta = (None if t is None else t.cuda() for t in tensors)
     lib = L.lib()
     OH, OW = H + 2 * pad - KH + 1, W + 2 * pad - KW + 1
     PH, PW = (OH // 2, OW // 2) if pool else (OH, OW)
@@ -101,13 +97,13 @@ def _run(L, case, tensors, cons):
     return rc, out.cpu()
 
 
-@pytest.mark.parametrize("case", CASES)
-def test_fused_layer_equals_float64_reference(L, case):
+def _check(L, case, tensors):
+    """The exactness pre-conditions of these inputs, then the fused entry against the reference, byte for byte."""
     N, C, H, W, Co, KH, KW, pad, pool, cons = case
-    tensors = _inputs(case)
     ref, y = _reference(*tensors, pad, pool)
     keep = torch.ones(Co, dtype=torch.bool)
-    keep[0] = keep[2] = False
+    keep[0] = False
+    keep[2] = tensors[6] is None                         # without beta channel 2 is a channel like any other
     print("min |y| outside the planted channels:", float(y[:, keep].abs().min()), "zeros:", int((ref[:, 0] == 0).sum()))
     assert float(y[:, keep].abs().min()) >= 0.01 and bool((y[:, 0] == 0).any())
     rc, out = _run(L, case, tensors, cons)
@@ -117,6 +113,42 @@ def test_fused_layer_equals_float64_reference(L, case):
         assert bool((out[ref.numel():] == 0xFF).all())               # nothing beyond the tensor is written
     else:
         assert torch.equal(out, _planes(ref, *cons, out.numel()))    # interior, halo and tail, byte for byte
+
+
+@pytest.mark.parametrize("case", CW.infer_params())
+def test_fused_layer_equals_float64_reference(L, case):
+    _check(L, case, _inputs(case))
+
+
+@pytest.mark.parametrize("drop", ["bias", "gamma", "beta", "all"])
+@pytest.mark.parametrize("case", CW.NULL_CASES, ids=CW.shape_id)
+def test_null_bias_gamma_and_beta(L, case, drop):
+    """A null bias, gamma or beta is 0, 1, 0.  Without the bias x is an integer and mean still a multiple of 0.5
+    plus 0.25, so x - mean stays 0.25 off zero.  Without gamma, beta is drawn for gamma = 1 (k / 2 invstd), which
+    keeps y = invstd (x - mean + k / 2) off zero as before."""
+    x, w, bias, mean, invstd, gamma, beta = _inputs(case)
+    if drop in ("gamma", "all"):
+        beta = beta / gamma
+        gamma = None
+    if drop in ("bias", "all"):
+        bias, mean[0] = None, 0.0                        # channel 0: y == 0 exactly wherever I == 0, as with the bias
+    if drop in ("beta", "all"):
+        beta = None
+    _check(L, case, (x, w, bias, mean, invstd, gamma, beta))
+
+
+def test_empty_batch_returns_zero_and_writes_nothing(L):
+    """N = 0 at the C ABI for both output forms, with small non-empty tensors as the pointers (the entry refuses
+    null)."""
+    N, C, H, W, Co, KH, KW, pad = CW.EMPTY
+    planes, wq = (torch.zeros(256, dtype=torch.uint8, device="cuda") for _ in range(2))
+    params = [torch.ones(16, device="cuda") for _ in range(5)]
+    for form, K2, pad2 in ((1, 0, 0), (0, 3, 1)):
+        out = torch.full((1024,), 0xFF, dtype=torch.uint8, device="cuda")
+        rc = L.lib().bnn_conv2d_fwd_wide_bnsign(planes, wq, *params, out, N, C, H, W, Co, KH, KW, pad, 2, form, K2, K2,
+                                                pad2, L.stream())
+        torch.cuda.synchronize()
+        assert rc == 0 and bool((out == 0xFF).all())
 
 
 def _stack(seed=3):
