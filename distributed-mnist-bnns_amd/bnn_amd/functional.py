@@ -1649,6 +1649,13 @@ CONV_WIDE_BWD_CALLS = 0
 # Independent of the two switches above.  BNN_CONV_WIDE_BWD_FILTER=0: today's path (A/B and the tests).
 CONV_WIDE_BWD_FILTER = os.environ.get("BNN_CONV_WIDE_BWD_FILTER", "1") != "0"
 CONV_WIDE_BWD_FILTER_CALLS = 0
+# First layer: a real-input (not binarised) convolution whose shape bnn_conv2d_fwd_first_ok takes
+# (1 <= C <= 4, C KH KW <= 80, Co > 64, stride 1, ...) runs its forward as a bf16-MFMA implicit GEMM on the exact
+# three-plane split of x, and its filter / bias gradient as an fp32-MFMA GEMM over positions, instead of the
+# generic kernels -- another summation order, not the same bits.  BNN_CONV_FIRST=0: today's path (A/B and the tests).
+CONV_FIRST = os.environ.get("BNN_CONV_FIRST", "1") != "0"
+CONV_FIRST_CALLS = 0
+CONV_FIRST_FILTER_CALLS = 0
 
 
 def _conv_wide_workspace(nbytes, device):
@@ -1722,6 +1729,14 @@ class BinaryConv2dFunction(torch.autograd.Function):
                        ws, ws.numel(), L.stream())
             CONV_WIDE_CALLS += 1
             return y
+        if (CONV_FIRST and not binarize_input
+                and L.lib().bnn_conv2d_fwd_first_ok(N, C, H, W, Co, KH, KW, stride, padding, dilation, groups)):
+            global CONV_FIRST_CALLS
+            with _timed("conv2d_fwd_first", 2 * macs, 4 * (x.numel() + y.numel() + w.numel())):
+                L.call("bnn_conv2d_fwd_first", x, w, b, y, N, C, H, W, Co, KH, KW, stride, padding, dilation, groups,
+                       L.stream())
+            CONV_FIRST_CALLS += 1
+            return y
         with _timed("conv2d_fwd", 2 * macs, 4 * (x.numel() + y.numel() + w.numel())):
             L.call("bnn_conv2d_fwd", x, int(binarize_input), w, b, y, N, C, H, W, Co, KH, KW, stride, padding, dilation,
                    groups, L.stream())
@@ -1792,6 +1807,16 @@ class BinaryConv2dFunction(torch.autograd.Function):
                     L.call("bnn_conv2d_bwd_filter_wide", dy, x, dw, db, N, C, H, W, Co, KH, KW, stride, padding,
                            dilation, groups, ws, ws.numel(), L.stream())
                 CONV_WIDE_BWD_FILTER_CALLS += 1
+            elif (CONV_FIRST and not binarize_input
+                    and L.lib().bnn_conv2d_bwd_filter_first_ok(N, C, H, W, Co, KH, KW, stride, padding, dilation,
+                                                               groups)):
+                global CONV_FIRST_FILTER_CALLS
+                ws = _conv_wide_workspace(
+                    int(L.lib().bnn_conv2d_bwd_filter_first_workspace(N, C, H, W, Co, KH, KW, padding)), x.device)
+                with _timed("conv2d_bwd_filter_first", 2 * macs, 4 * (dy.numel() + x.numel() + w.numel())):
+                    L.call("bnn_conv2d_bwd_filter_first", dy, x, dw, db, N, C, H, W, Co, KH, KW, stride, padding,
+                           dilation, groups, ws, ws.numel(), L.stream())
+                CONV_FIRST_FILTER_CALLS += 1
             else:
                 ws = torch.empty((L.lib().bnn_conv2d_bwd_filter_workspace(N, C, Co, KH, KW, groups),),
                                  dtype=torch.uint8, device=x.device)

@@ -541,6 +541,46 @@ const char* bnn_conv2d_bwd_filter_wide_kernel(int64_t N, int64_t C, int64_t H, i
  * reduce; 15 = all (the default; anything else leaves dw or the workspace as an earlier call made them).
  * mask < 0 queries. */
 int bnn_conv2d_bwd_filter_wide_set_stages(int32_t mask);
+/* The first layer of a CIFAR-style stack: few real-valued input channels into wide output.  The
+ * input is taken as fp32 and never binarised (the caller applies the `!= 3` rule).
+ *   forward:  y[n,co,oh,ow] = fl(sum_{c,kh,kw} x[n,c,oh+kh-pad,ow+kw-pad] * sign(w_latent[co,c,kh,kw]) + bias[co])
+ *             (zeros outside the image, bias nullable), an implicit GEMM on the bf16 MFMA: x enters as its exact
+ *             three-plane bf16 split and the weights as ternary bf16 (0, -0 and NaN give 0), so every product
+ *             is exact; the roundings are the fp32 accumulation and the bias add.  One launch, no workspace.
+ *   filter:   dw[co,c,kh,kw] = sum_{n,oh,ow} dy[n,co,oh,ow] * x[n,c,oh+kh-pad,ow+kw-pad], db[co] = sum dy
+ *             (db nullable), a GEMM over positions on the fp32 MFMA with both operands in their fp32 form; db is
+ *             a column of ones in the same accumulators.  fp32 partials per K slice, summed in double in a fixed
+ *             order and rounded once.  No atomics: deterministic.  N == 0 zero-fills dw and db.
+ * Shapes taken (both _ok = 1, one decision function behind every entry and query): one group, stride 1,
+ * dilation 1, pad <= min(KH, KW) - 1, 1 <= C <= 4, C KH KW <= 80, Co > 64, any N, and H, W whose forward stage --
+ * three bf16 planes of the C x (126 / OW + 1 + KH) x (W + 2 pad) window beside two weight tiles -- fits 160 KiB of
+ * LDS (3x3 on RGB up to W + 2 pad = 1974, 5x5 up to 1087).  `work` is scratch of bnn_conv2d_bwd_filter_first_workspace(...) bytes
+ * = slices x round_up(Co, 128) x Kp x 4, Kp = round_up(C KH KW + 1, 32), rounded up to 256 (0 for a shape not
+ * taken or N == 0), 16-B aligned; it may hold anything on entry and every call rewrites all it reads.  A shape
+ * not taken, a null pointer or a short workspace return BNN_EINVAL with nothing launched.
+ * bnn_conv2d_fwd_first_kernel: the instance <k-steps of 16> with its LDS bytes, window rows, Kp, the weight
+ * rows' pitch and the modelled cycles of the weight fragment read ("conv_first_fwd_k<2> lds=25952 rows=7 Kp=32
+ * pitch=40 b128=4"); bnn_conv2d_bwd_filter_first_kernel: the instance <32-column blocks, 16-B dy loads> with its
+ * LDS bytes, chunk (rows x columns), output rows, rows per K slice, K slices and Kp
+ * ("conv_first_bwd_filter_k<1, 1> lds=35520 chunk=2x32 rows=8192 slice=16 splits=512 Kp=32"); "" for a shape not
+ * taken.  The strings are valid until the calling thread's next query.  bnn_conv2d_fwd, bnn_conv2d_bwd_filter and
+ * bnn_conv_kernel are unaffected. */
+int bnn_conv2d_fwd_first_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                            int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int bnn_conv2d_fwd_first(const float* x, const float* w_latent, const float* bias, float* y, int64_t N, int64_t C,
+                         int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad,
+                         int32_t dil, int32_t groups, bnn_stream_t stream);
+const char* bnn_conv2d_fwd_first_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                        int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int bnn_conv2d_bwd_filter_first_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                                   int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int64_t bnn_conv2d_bwd_filter_first_workspace(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                              int64_t KW, int32_t pad);
+int bnn_conv2d_bwd_filter_first(const float* dy, const float* x, float* dw, float* db, int64_t N, int64_t C, int64_t H,
+                                int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad,
+                                int32_t dil, int32_t groups, void* work, int64_t work_bytes, bnn_stream_t stream);
+const char* bnn_conv2d_bwd_filter_first_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                               int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
 /* Frozen-model inference (bnn_amd.inference.FrozenCNN): the binary convolution with eval-mode
  * BatchNorm2d -> Hardtanh -> MaxPool2d(2, 2) in its epilogue.  Geometry of both entries: stride 1,
  * dilation 1, groups 1, C == 1 (KW <= 8) or C % 16 == 0 (<= 64, at most 256 output pixels), Co <= 64,
