@@ -604,6 +604,8 @@ class FrozenCNN(_Frozen):
 # Fused launches of the frozen wide layers (bnn_conv2d_fwd_wide_bnsign), as functional.CONV_WIDE_CALLS counts
 # the training forward's.
 WIDE_FUSED_CALLS = 0
+# ... and of the frozen real-input first block (bnn_conv2d_fwd_first_bnsign)
+FIRST_FUSED_CALLS = 0
 
 
 class FrozenConvStack:
@@ -620,12 +622,18 @@ class FrozenConvStack:
     Every layer class measured (tools/conv_wide_infer_bench.py) is faster fused, so none is kept on two-pass by
     default.  No host synchronisation; planes and outputs are kept per (N, device), so a region captured after
     warm-up allocates nothing -- and ``forward`` returns that kept buffer, which the next call of the same N
-    overwrites.  CPU tensors run a plain-torch restatement (a checking path)."""
+    overwrites.  CPU tensors run a plain-torch restatement (a checking path).
 
-    def __init__(self, layers, tensors, eps):
+    With ``real_input`` block 1 is the RGB layer, whose input BinarizeConv2d never binarises: it
+    is one bnn_conv2d_fwd_first_bnsign launch straight from the fp32 images, with no pack_x, into block 2's
+    planes (or int8 signs where block 2 is not fused); where its plan refuses, or under ``two_pass``, it runs as
+    binary_conv2d on the real input + bnn_bn2d_fwd_eval."""
+
+    def __init__(self, layers, tensors, eps, real_input=False):
         self.layers = [tuple(int(e) for e in l) for l in layers]     # per block (C, Co, KH, KW, pad, pool)
         self.t = dict(tensors)
         self.eps = tuple(float(e) for e in eps)
+        self.real_input = bool(real_input)                           # block 1 convolves x itself, not tsign(x)
         self.two_pass = False
         self._buf = {}
 
@@ -671,12 +679,17 @@ class FrozenConvStack:
             return wq
         return self._cached(("wq", i, str(device)), make)
 
+    def _wf(self, i, device):
+        """Block i's fp32 sign weights, for the kernels that take a latent fp32 weight."""
+        return self._cached(("wf", i, str(device)), lambda: self.t[f"conv{i}.sign"].float().contiguous())
+
     def _two_pass_block(self, i, x, shp):
-        """Block i as model.eval() runs it: conv (binarising x) -> eval BatchNorm2d + Hardtanh (+ pool), fp32."""
+        """Block i as model.eval() runs it: conv (binarising x, except a real-input block 1) -> eval BatchNorm2d +
+        Hardtanh (+ pool), fp32."""
         C, Co, KH, KW, pad, pool, H, W, PH, PW = shp
         N = x.shape[0]
-        wf = self._cached(("wf", i, str(x.device)), lambda: self.t[f"conv{i}.sign"].float().contiguous())
-        z = BF.binary_conv2d(x, wf, self.t.get(f"conv{i}.bias"), True, 1, pad, 1, 1)
+        z = BF.binary_conv2d(x, self._wf(i, x.device), self.t.get(f"conv{i}.bias"), not (self.real_input and i == 1),
+                             1, pad, 1, 1)
         mean, _, gamma, beta = self._bn(i)
         if (z.shape[2] * z.shape[3]) % 4 == 0:
             y = torch.empty((N, Co, PH, PW), dtype=torch.float32, device=x.device)
@@ -697,7 +710,7 @@ class FrozenConvStack:
             return self._forward_cpu(x, shapes)
         if self.device != x.device:
             raise RuntimeError(f"FrozenConvStack on {self.device} got an input on {x.device}; call .to(device)")
-        global WIDE_FUSED_CALLS
+        global WIDE_FUSED_CALLS, FIRST_FUSED_CALLS
         N, dev = x.shape[0], str(x.device)
         last = shapes[-1]
         out = self._cached(("out", N, dev, last[1], last[8], last[9]),
@@ -705,8 +718,9 @@ class FrozenConvStack:
         if N == 0:
             return out
         ok = L.lib().bnn_conv2d_fwd_wide_bnsign_ok
-        fused = [not self.two_pass and ok(N, C, H, W, Co, KH, KW, 1, pad, 1, 1, pool, 1, 0, 0, 0) == 1
-                 for C, Co, KH, KW, pad, pool, H, W, PH, PW in shapes]
+        oks = [L.lib().bnn_conv2d_fwd_first_bnsign_ok if self.real_input and i == 0 else ok for i in range(len(shapes))]
+        fused = [not self.two_pass and oks[i](N, C, H, W, Co, KH, KW, 1, pad, 1, 1, pool, 1, 0, 0, 0) == 1
+                 for i, (C, Co, KH, KW, pad, pool, H, W, PH, PW) in enumerate(shapes)]
         cur, form = (x if x.is_contiguous() else x.contiguous()), "f32"
         for i, shp in enumerate(shapes, 1):
             C, Co, KH, KW, pad, pool, H, W, PH, PW = shp
@@ -717,7 +731,8 @@ class FrozenConvStack:
                     out.copy_(_tsign(y))
                 cur, form = y, "f32"
                 continue
-            if form != "planes":      # the stack's input, or what a two-pass block wrote: tsign is the pack's
+            first = self.real_input and i == 1            # fp32 images in, no pack
+            if form != "planes" and not first:   # the stack's input, or what a two-pass block wrote: tsign is the pack's
                 nb = int(L.lib().bnn_conv2d_wide_planes_bytes(N, C, H, W, KH, KW, pad))
                 planes = self._cached(("planes", i, N, dev, H, W), lambda: torch.empty((nb,), dtype=torch.uint8, device=x.device))
                 L.call("bnn_conv2d_wide_pack_x", cur, planes, N, C, H, W, KH, KW, pad, L.stream())
@@ -726,7 +741,7 @@ class FrozenConvStack:
             K2 = (0, 0, 0)
             if not is_last and fused[i]:
                 nxt = self.layers[i]
-                if ok(N, C, H, W, Co, KH, KW, 1, pad, 1, 1, pool, 0, nxt[2], nxt[3], nxt[4]) == 1:
+                if oks[i - 1](N, C, H, W, Co, KH, KW, 1, pad, 1, 1, pool, 0, nxt[2], nxt[3], nxt[4]) == 1:
                     K2 = (nxt[2], nxt[3], nxt[4])
             to_planes = K2[0] > 0
             if to_planes:
@@ -737,31 +752,38 @@ class FrozenConvStack:
             else:
                 dst = self._cached(("s8", i, N, dev, PH, PW),
                                    lambda: torch.empty((N, Co, PH, PW), dtype=torch.int8, device=x.device))
-            L.call("bnn_conv2d_fwd_wide_bnsign", cur, self._wq(i, x.device), self.t.get(f"conv{i}.bias"), mean, invstd,
-                   gamma, beta, dst, N, C, H, W, Co, KH, KW, pad, pool, 0 if to_planes else 1, *K2, L.stream())
-            WIDE_FUSED_CALLS += 1
+            if first:
+                L.call("bnn_conv2d_fwd_first_bnsign", cur, self._wf(i, x.device), self.t.get(f"conv{i}.bias"), mean,
+                       invstd, gamma, beta, dst, N, C, H, W, Co, KH, KW, pad, pool, 0 if to_planes else 1, *K2, L.stream())
+                FIRST_FUSED_CALLS += 1
+            else:
+                L.call("bnn_conv2d_fwd_wide_bnsign", cur, self._wq(i, x.device), self.t.get(f"conv{i}.bias"), mean,
+                       invstd, gamma, beta, dst, N, C, H, W, Co, KH, KW, pad, pool, 0 if to_planes else 1, *K2, L.stream())
+                WIDE_FUSED_CALLS += 1
             cur, form = dst, ("planes" if to_planes else "s8")
         return out
 
     __call__ = forward
 
     def _forward_cpu(self, x, shapes):
-        s = _tsign(x).double()
+        s = x.double() if self.real_input else _tsign(x).double()
         for i, (C, Co, KH, KW, pad, pool, H, W, PH, PW) in enumerate(shapes, 1):
-            z = tF.conv2d(s, self.t[f"conv{i}.sign"].double(), None, 1, pad).float()     # exact integer sums
-            if f"conv{i}.bias" in self.t:
+            z = tF.conv2d(s, self.t[f"conv{i}.sign"].double(), None, 1, pad).float()     # exact integer sums (a real
+            if f"conv{i}.bias" in self.t:                                                # block 1: rounded once)
                 z = z + self.t[f"conv{i}.bias"].view(1, -1, 1, 1)
             y = tF.hardtanh(_bn_y_cpu(z, *(None if v is None else v.view(1, -1, 1, 1) for v in self._bn(i))))
             s = _tsign(tF.max_pool2d(y, 2, 2) if pool else y).double()
         return s.to(torch.int8)
 
 
-def freeze_conv_stack(blocks):
+def freeze_conv_stack(blocks, real_input=False):
     """Snapshot wide binarized conv blocks for inference: an iterable of
     nn.Sequential(BinarizeConv2d, BatchNorm2d, Hardtanh(-1, 1)[, MaxPool2d(2, 2)]) -> FrozenConvStack.  The
     weight source is ``weight.org`` when the layer carries one.  Raises ValueError for any other chain, a
     BatchNorm without running statistics, a convolution that is not stride 1 / dilation 1 / one group / square
-    padding, or one that takes unbinarised images (in_channels == 3)."""
+    padding, or one that takes unbinarised images (in_channels == 3).  With ``real_input=True`` the stack starts
+    at the images: the first block must be that in_channels == 3 convolution (the one case BinarizeConv2d
+    leaves unbinarised; ValueError otherwise) and the stack convolves its real input."""
     from .nn import BinarizeConv2d
     import torch.nn as tnn
     pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
@@ -779,9 +801,11 @@ def freeze_conv_stack(blocks):
                              "[-> MaxPool2d(2, 2) without padding or ceil_mode]")
         conv, bn = seq[0], seq[1]
         if (tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.groups != 1
-                or isinstance(conv.padding, str) or conv.padding[0] != conv.padding[1] or conv.in_channels == 3):
+                or isinstance(conv.padding, str) or conv.padding[0] != conv.padding[1]
+                or (conv.in_channels == 3) != (real_input and i == 1)):
             raise ValueError(f"freeze_conv_stack: block {i}'s convolution must have stride 1, dilation 1, one group, "
-                             "square padding and a binarised input (in_channels != 3)")
+                             "square padding and a binarised input (in_channels != 3)"
+                             + (", the first block of a real_input stack in_channels == 3" if real_input else ""))
         w = _latent(conv.weight).float()
         Co, C, KH, KW = w.shape
         if layers and layers[-1][1] != C:
@@ -794,7 +818,7 @@ def freeze_conv_stack(blocks):
         eps.append(bn.eps)
     if not layers:
         raise ValueError("freeze_conv_stack: no blocks")
-    return FrozenConvStack(layers, t, eps)
+    return FrozenConvStack(layers, t, eps, real_input)
 
 
 _CLASSES = {cls.FORMAT: cls for cls in (FrozenMLP, FrozenCNN)}

@@ -26,7 +26,7 @@
 //     partials -> part [slices][ceil(Co/128) 128][Kp], every element written by every call.
 //  2. conv_first_bwd_filter_reduce_k    the slices summed in double in a fixed order, one rounding.
 // No atomics: deterministic.
-#include "bnn_conv_wide.h"
+#include "bnn_conv_first.h"
 
 #include <cstdio>
 
@@ -37,7 +37,6 @@ namespace {
 
 constexpr int kFirstRounds = 2;    // the K split aims at this many rounds of workgroups on kFirstCUs CUs
 constexpr int kFirstCUs = 256;
-constexpr int kFirstMaxC = 4, kFirstMaxKt = 80;
 constexpr int FG_POS = 64;         // positions of a filter-gradient chunk at most
 constexpr int FR_EL = 16, FR_ST = 16;   // the reduce: elements x strands of a workgroup
 
@@ -60,13 +59,6 @@ struct FirstPlan {
   int64_t rows, rps, splits, cop, flt_lds, work_bytes;
 };
 
-// the weight fragment read of the forward through the bank model: lane (r, h) reads 16 B of row r at k = 8 h
-int first_wfrag_cycles(int wp) {
-  int addr[64];
-  for (int l = 0; l < 64; ++l) addr[l] = ((l & 31) * wp + 8 * (l >> 5)) * 2;
-  return lds_b128_cycles(addr);
-}
-
 bool first_plan_make(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride,
                      int32_t pad, int32_t dil, int32_t groups, FirstPlan* out) {
   const int64_t lim = 1ll << 31;
@@ -87,11 +79,7 @@ bool first_plan_make(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int
   const int64_t win = C * p.rw * p.Wp;
   if (win >= (1 << 20)) return false;
   p.plane = (int)round_up(win + 1, 8);
-  p.cycles = 1 << 30;
-  for (int j = 1; j <= 4; ++j) {
-    const int c = first_wfrag_cycles(p.kp + 8 * j);
-    if (c < p.cycles) p.cycles = c, p.wp = p.kp + 8 * j;
-  }
+  first_weight_pitch(p.kp, &p.wp, &p.cycles);
   p.fwd_lds = 2ll * 128 * p.wp * 2 + 2 * 128 * 4 + p.kp * 4 + 3ll * p.plane * 2;
   p.ptiles = (OH * OW + 127) / 128;
   if (p.fwd_lds > kWideMaxLds || N * p.ptiles >= lim) return false;
@@ -134,11 +122,6 @@ bool first_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t 
   }
   if (memo.ok) *out = memo.plan;
   return memo.ok;
-}
-
-__device__ __forceinline__ unsigned short tsign_bf16(float v) {
-  const int s = tsign(v);
-  return s > 0 ? 0x3F80 : (s < 0 ? 0xBF80 : 0);
 }
 
 struct FirstFwd {

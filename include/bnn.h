@@ -581,6 +581,39 @@ int bnn_conv2d_bwd_filter_first(const float* dy, const float* x, float* dw, floa
                                 int32_t dil, int32_t groups, void* work, int64_t work_bytes, bnn_stream_t stream);
 const char* bnn_conv2d_bwd_filter_first_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
                                                int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+/* The frozen first layer (bnn_amd.inference.FrozenConvStack with real_input): the forward above
+ * with the epilogue of bnn_conv2d_fwd_wide_bnsign.  x fp32 [N][C][H][W] (never binarised), w_latent fp32
+ * [Co][C][KH][KW]; per element I = sum x * sign(w_latent) on the bf16 MFMA as above, x' = fl(I + bias[co]),
+ * y = fmaf((x' - mean[co]) * invstd[co], gamma[co], beta[co]) (bias / gamma / beta nullable), then the ternary
+ * sign of eval-mode BatchNorm2d -> Hardtanh -> MaxPool2d(2, 2) when pool = 2 (even OH and OW) or without a pool
+ * when pool = 0, by bnn_conv2d_fwd_wide_bnsign's rule: +1 if some y of the window > 0, else 0 if some y == 0,
+ * else -1, and 0 if the window holds a NaN.  With [PH][PW] the (pooled) map,
+ *   out_form 0: `out` = the planes (layout above) of the (N, Co, PH, PW) activation for a consumer layer
+ *               (KH2, KW2, pad2), Co % 64 == 0, 16-B aligned; every byte of
+ *               bnn_conv2d_wide_planes_bytes(N, Co, PH, PW, KH2, KW2, pad2) is written by every call;
+ *   out_form 1: `out` = int8 signs [N][Co][PH][PW], any Co (KH2 / KW2 / pad2 ignored).
+ * Shapes taken (bnn_conv2d_fwd_first_bnsign_ok = 1): what bnn_conv2d_fwd_first_ok takes; pool 0 or 2; the
+ * staged window of the position mapping (pool 2: 2 (30 / PW + 2) + KH - 1 rows of W + 2 pad) within 160 KiB of
+ * LDS; for out_form 0 a consumer geometry with planes_bytes > 0.  Anything else, a null pointer or an unaligned
+ * planes output returns BNN_EINVAL with nothing launched; N == 0 returns 0.  One launch, no workspace, no
+ * atomics, every output byte written by one thread: deterministic.  Where I is the same, the signs equal
+ * bnn_conv2d_fwd_first -> bnn_bn2d_fwd_eval -> sign.  bnn_conv2d_fwd_first_bnsign_kernel: the instance <k-steps
+ * of 16, pool> with the output form, its LDS bytes, window rows, Kp, the weight rows' pitch and the modelled
+ * cycles of the weight fragment read ("conv_first_bnsign_k<2,0> form=0 lds=30048 rows=7 Kp=32 pitch=40 b128=4");
+ * "" for a shape not taken, valid until the calling thread's next query.  The entry and the two queries share
+ * one decision function. */
+int bnn_conv2d_fwd_first_bnsign_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                                   int32_t stride, int32_t pad, int32_t dil, int32_t groups, int32_t pool,
+                                   int32_t out_form, int64_t KH2, int64_t KW2, int32_t pad2);
+const char* bnn_conv2d_fwd_first_bnsign_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                               int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups,
+                                               int32_t pool, int32_t out_form, int64_t KH2, int64_t KW2,
+                                               int32_t pad2);
+int bnn_conv2d_fwd_first_bnsign(const float* x, const float* w_latent, const float* bias, const float* mean,
+                                const float* invstd, const float* gamma, const float* beta, void* out, int64_t N,
+                                int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t pad,
+                                int32_t pool, int32_t out_form, int64_t KH2, int64_t KW2, int32_t pad2,
+                                bnn_stream_t stream);
 /* Frozen-model inference (bnn_amd.inference.FrozenCNN): the binary convolution with eval-mode
  * BatchNorm2d -> Hardtanh -> MaxPool2d(2, 2) in its epilogue.  Geometry of both entries: stride 1,
  * dilation 1, groups 1, C == 1 (KW <= 8) or C % 16 == 0 (<= 64, at most 256 output pixels), Co <= 64,
