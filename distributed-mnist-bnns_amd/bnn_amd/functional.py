@@ -2468,6 +2468,131 @@ def batch_norm2d_hardtanh_pool(x, bn, hardtanh=True, pool=2):
                                                  hardtanh, pool)
 
 
+# Wide-channel hand-off: between two wide binarised conv layers in training, BatchNorm2d ->
+# Hardtanh -> [MaxPool2d(2, 2)] -> sign writes the consumer's FP4 planes (bnn_bn2d_fwd_train_planes) and the
+# consumer's forward and filter gradient read them (bnn_conv2d_fwd_wide_planes, bnn_conv2d_bwd_filter_wide_planes):
+# no fp32 activation between the two layers; same bits as the chain.  None (the default): the classes §25
+# measured ahead of the chain (_handoff_measured); True (BNN_CONV_WIDE_HANDOFF=1): every transition the
+# queries accept; False (BNN_CONV_WIDE_HANDOFF=0): today's chain.
+CONV_WIDE_HANDOFF = {None: None, "0": False}.get(os.environ.get("BNN_CONV_WIDE_HANDOFF"), True)
+CONV_WIDE_HANDOFF_CALLS = 0
+
+
+class BN2dHardtanhPoolBinaryConv2dFunction(torch.autograd.Function):
+    """conv(sign(maxpool2(hardtanh(nn.BatchNorm2d(z))))) for a wide BinarizeConv2d in deterministic mode, the
+    activation between the two travelling as the conv's FP4 planes only (saved for the filter gradient)."""
+
+    @staticmethod
+    def forward(ctx, z, gw, gb, running_mean, running_var, momentum, eps, pool, weight, bias, padding):
+        global CONV_WIDE_HANDOFF_CALLS
+        _check(z, gw, gb, running_mean, running_var, weight, bias)
+        z, w = _c2d(z), _c2d(weight.detach())
+        gw, gb = _detached(gw, gb)
+        b = bias.detach() if bias is not None else None
+        N, C, H, W = z.shape
+        Co, _, KH, KW = w.shape
+        PH, PW = (H // 2, W // 2) if pool else (H, W)
+        OH, OW = conv_out_hw(PH, PW, KH, KW, 1, padding, 1)
+        lib, dev = L.lib(), z.device
+        u8 = lambda n: torch.empty((int(n),), dtype=torch.uint8, device=dev)
+        planes = u8(lib.bnn_conv2d_wide_planes_bytes(N, C, PH, PW, KH, KW, padding))
+        mean = torch.empty((C,), dtype=torch.float32, device=dev)
+        invstd = torch.empty_like(mean)
+        with _timed("bn2d_fwd_train_planes", 0, 4 * z.numel() + planes.numel()):
+            L.call("bnn_bn2d_fwd_train_planes", z, N, C, H, W, gw, gb, running_mean, running_var,
+                   _bn_momentum(momentum), float(eps), mean, invstd, planes, int(pool), KH, KW, padding,
+                   u8(lib.bnn_bn2d_workspace(N, C)), L.stream())
+        y = torch.empty((N, Co, OH, OW), dtype=torch.float32, device=dev)
+        ws = _conv_wide_workspace(int(lib.bnn_conv2d_fwd_wide_planes_workspace(N, C, PH, PW, Co, KH, KW, padding)), dev)
+        with _timed("conv2d_fwd_wide_planes", 2 * y.numel() * C * KH * KW, planes.numel() + 4 * (y.numel() + w.numel())):
+            L.call("bnn_conv2d_fwd_wide_planes", planes, w, b, y, N, C, PH, PW, Co, KH, KW, padding, ws, ws.numel(),
+                   L.stream())
+        ctx.save_for_backward(z, gw, gb, mean, invstd, planes, w)
+        ctx.conf = (pool, padding, PH, PW, bias is not None)
+        CONV_WIDE_HANDOFF_CALLS += 1
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, gw, gb, mean, invstd, planes, w = ctx.saved_tensors
+        pool, padding, PH, PW, has_bias = ctx.conf
+        dy = _c2d(dy)
+        N, C, H, W = z.shape
+        Co, _, KH, KW = w.shape
+        lib, dev = L.lib(), z.device
+        shape = (N, C, PH, PW, Co, KH, KW, 1, padding, 1, 1)
+        macs = dy.numel() * C * KH * KW
+        dz = dgw = dgb = dw = db = None
+        if any(ctx.needs_input_grad[:3]):
+            da = torch.empty((N, C, PH, PW), dtype=torch.float32, device=dev)     # gradient of the pooled map
+            if CONV_WIDE_BWD and lib.bnn_conv2d_bwd_data_wide_ok(*shape):
+                ws = _conv_wide_workspace(int(lib.bnn_conv2d_bwd_data_wide_workspace(*shape[:7], padding)), dev)
+                with _timed("conv2d_bwd_data_wide", 2 * macs, 4 * (dy.numel() + da.numel() + w.numel())):
+                    L.call("bnn_conv2d_bwd_data_wide", dy, w, da, *shape, ws, ws.numel(), L.stream())
+            else:
+                with _timed("conv2d_bwd_data", 2 * macs, 4 * (dy.numel() + da.numel() + w.numel())):
+                    L.call("bnn_conv2d_bwd_data", dy, w, da, *shape, L.stream())
+            dz = torch.empty_like(z)
+            dgw, dgb = _bn_param_grads(C, gw, gb, dev)
+            ws = torch.empty((lib.bnn_bn2d_workspace(N, C),), dtype=torch.uint8, device=dev)
+            with _timed("bn2d_bwd", 0, 12 * z.numel() + 8 * da.numel()):
+                L.call("bnn_bn2d_bwd", z, da, N, C, H, W, gw, gb, mean, invstd, 1, int(pool), dz, dgw, dgb, ws,
+                       L.stream())
+        need_db = has_bias and ctx.needs_input_grad[9]
+        if ctx.needs_input_grad[8] or need_db:
+            dw = torch.empty_like(w)
+            db = torch.empty((Co,), dtype=torch.float32, device=dev) if need_db else None
+            ws = _conv_wide_workspace(int(lib.bnn_conv2d_bwd_filter_wide_workspace(*shape[:7], padding)), dev)
+            with _timed("conv2d_bwd_filter_wide_planes", 2 * macs, 4 * (dy.numel() + w.numel()) + planes.numel()):
+                L.call("bnn_conv2d_bwd_filter_wide_planes", dy, planes, dw, db, *shape, ws, ws.numel(), L.stream())
+            if not ctx.needs_input_grad[8]:
+                dw = None
+        return (dz if ctx.needs_input_grad[0] else None, dgw if ctx.needs_input_grad[1] else None,
+                dgb if ctx.needs_input_grad[2] else None, None, None, None, None, None, dw, db, None)
+
+
+def _handoff_measured(pool, PH, PW):
+    """The transitions whose slowest hand-off call beat the chain's fastest, forward and filter gradient
+    (batch 256): no pool in between and a map of at least 16 x 16."""
+    return pool == 0 and PH * PW >= 256
+
+
+def conv_wide_handoff_ok(z, bn, ht, pool, conv):
+    """Whether bn2d_hardtanh_pool_binary_conv2d takes BatchNorm2d `bn` -> Hardtanh `ht` -> [MaxPool2d(2, 2)] ->
+    `conv` on the fp32 conv output z: a training-mode BatchNorm, Hardtanh(-1, 1), a binarised-input BinarizeConv2d
+    in deterministic mode that holds its latent weight, shapes the three libbnn queries accept, and what
+    CONV_WIDE_HANDOFF allows."""
+    if not (CONV_WIDE_HANDOFF is not False and bn.training and ht.min_val == -1.0 and ht.max_val == 1.0 and pool in (0, 2)
+            and isinstance(z, torch.Tensor) and z.is_cuda and z.dim() == 4 and z.dtype == torch.float32
+            and z.shape[0] > 0 and getattr(z, _PREACT_ATTR, None) is None):
+        return False
+    if (conv.org_protocol or conv.quant_mode != "det" or conv.in_channels == 3 or isinstance(conv.padding, str)
+            or conv.padding[0] != conv.padding[1]):
+        return False
+    N, C, H, W = z.shape
+    Co, _, KH, KW = conv.weight.shape
+    pad, lib = conv.padding[0], L.lib()
+    PH, PW = (H // 2, W // 2) if pool else (H, W)
+    if CONV_WIDE_HANDOFF is None and not _handoff_measured(pool, PH, PW):
+        return False
+    if not lib.bnn_bn2d_fwd_train_planes_ok(N, C, H, W, pool, KH, KW, pad):
+        return False
+    shape = (N, C, PH, PW, Co, KH, KW, conv.stride[0] if conv.stride[0] ==
+             conv.stride[1] else 0, pad, conv.dilation[0] if conv.dilation[0] == conv.dilation[1] else 0, conv.groups)
+    return bool(lib.bnn_conv2d_fwd_wide_ok(*shape) and lib.bnn_conv2d_bwd_filter_wide_ok(*shape))
+
+
+def bn2d_hardtanh_pool_binary_conv2d(z, bn, conv, pool=2):
+    """conv(maxpool2(hardtanh(bn(z)))) through BN2dHardtanhPoolBinaryConv2dFunction where conv_wide_handoff_ok
+    holds (bn: nn.BatchNorm2d in training mode, Hardtanh(-1, 1) implied, conv: a wide BinarizeConv2d); the role
+    bn_hardtanh_binary_linear has for the MLP.  Raises ValueError elsewhere."""
+    if not conv_wide_handoff_ok(z, bn, torch.nn.Hardtanh(), pool, conv):
+        raise ValueError("bn2d_hardtanh_pool_binary_conv2d: not a hand-off conv_wide_handoff_ok takes")
+    rm, rv, _, factor = _bn_module_args(bn)
+    return BN2dHardtanhPoolBinaryConv2dFunction.apply(z, bn.weight, bn.bias, rm, rv, factor, bn.eps, int(pool),
+                                                      conv.weight, conv.bias, conv.padding[0])
+
+
 class BNHardtanhBinaryLinearFunction(torch.autograd.Function):
     """fc(hardtanh(bn(z))) with fc a BinarizeLinear whose input is binarised (the hidden layers
     of the reference Net, mnist-dist2.py:66-71): BatchNorm statistics, then ONE pass writes the

@@ -221,6 +221,51 @@ class BinCNN(nn.Module):
         return self._out(self.fc(out))
 
 
+def _conv_block(i, seq):
+    """(conv, bn, hardtanh, pool) of block i in the form inference.freeze_conv_stack accepts; pool is 2 or 0."""
+    ok = (isinstance(seq, nn.Sequential) and len(seq) in (3, 4) and isinstance(seq[0], BinarizeConv2d)
+          and isinstance(seq[1], nn.BatchNorm2d) and isinstance(seq[2], nn.Hardtanh))
+    if ok and len(seq) == 4:
+        p = seq[3]
+        ok = (isinstance(p, nn.MaxPool2d) and p.kernel_size in (2, (2, 2)) and p.stride in (2, (2, 2))
+              and p.padding in (0, (0, 0)) and p.dilation in (1, (1, 1)) and not p.ceil_mode)
+    if not ok:
+        raise ValueError(f"conv_blocks_forward: block {i} must be BinarizeConv2d -> BatchNorm2d -> Hardtanh "
+                         "[-> MaxPool2d(2, 2) without padding or ceil_mode]")
+    return seq[0], seq[1], seq[2], 2 if len(seq) == 4 else 0
+
+
+def conv_blocks_forward(blocks, x, fused_bn=True):
+    """Run nn.Sequential(BinarizeConv2d, BatchNorm2d, Hardtanh[, MaxPool2d(2, 2)]) blocks, the block form
+    ``inference.freeze_conv_stack`` accepts, on x.  With ``fused_bn`` each BatchNorm2d -> Hardtanh -> pool runs
+    as one libbnn op, and between two consecutive wide blocks in training the activation travels as the next
+    convolution's FP4 planes (functional.bn2d_hardtanh_pool_binary_conv2d, where conv_wide_handoff_ok holds);
+    the last block ends in functional.batch_norm2d_hardtanh_pool.  Same parameters, buffers and math as
+    calling the blocks one after the other (``fused_bn=False``)."""
+    blocks = list(blocks)
+    parts = [_conv_block(i, seq) for i, seq in enumerate(blocks, 1)]
+    if not parts:
+        raise ValueError("conv_blocks_forward: no blocks")
+    if not fused_bn:
+        for seq in blocks:
+            x = seq(x)
+        return x
+    with BF.bn_counter_batch():
+        z = parts[0][0](x)
+        for i, (_, bn, ht, pool) in enumerate(parts):
+            nxt = parts[i + 1][0] if i + 1 < len(parts) else None
+            if nxt is not None and BF.conv_wide_handoff_ok(z, bn, ht, pool, nxt):
+                z = BF.bn2d_hardtanh_pool_binary_conv2d(z, bn, nxt, pool)
+                continue
+            if ht.min_val == -1.0 and ht.max_val == 1.0 and BF.bn2d_fusable(z, pool):
+                a = BF.batch_norm2d_hardtanh_pool(z, bn, hardtanh=True, pool=pool)
+            else:
+                a = ht(bn(z))
+                a = blocks[i][3](a) if pool else a
+            z = nxt(a) if nxt is not None else a
+    return z
+
+
 MODELS = {"mlp": Net, "small": SmallNet, "wide": WideNet, "cnn": BinCNN}
 
 

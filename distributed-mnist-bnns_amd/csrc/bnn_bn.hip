@@ -1797,6 +1797,9 @@ bool bn2_args_ok(const float* x, int64_t N, int64_t C, int64_t H, int64_t W, int
 }
 
 }  // namespace
+
+bool bn2d_shape_ok(int64_t N, int64_t C, int64_t H, int64_t W, int pool) { return bn2_shape_ok(N, C, H, W, pool); }
+
 }  // namespace bnn
 
 using namespace bnn;
@@ -2437,18 +2440,11 @@ BNN_API int bnn_bn2d_plan(int64_t N, int64_t C, int64_t H, int64_t W, int32_t po
   return 0;
 }
 
-static int bn2d_fwd_train_impl(X2 x, int xf, int64_t N, int64_t C, int64_t H, int64_t W, const float* gamma,
-                               const float* beta, float* running_mean, float* running_var, float momentum,
-                               float eps, float* save_mean, float* save_invstd, float* y, int32_t hardtanh,
-                               int32_t pool, void* work, void* stream) {
-  if (!bn2_args_ok(reinterpret_cast<const float*>(x.p), N, C, H, W, pool) || !save_mean || !save_invstd || !work ||
-      !y || (running_mean == nullptr) != (running_var == nullptr) || xf < 0 || xf > 2 || (xf == 0 && x.bias) ||
-      (x.bias && !aligned16(x.bias)) || (xf != 0 && N * C * H * W * xf >= (1LL << 31))) {
-    set_error("bnn_bn2d_fwd_train: bad arguments (N=%lld C=%lld H=%lld W=%lld pool=%d; H*W must be a multiple "
-              "of 4, pool 0 or 2 with even H, W)", (long long)N, (long long)C, (long long)H, (long long)W, pool);
-    return kErrInval;
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// The training statistics of bnn_bn2d_fwd_train and of the wide-conv hand-off (bnn_bn2d.h): arguments checked
+// by the caller.
+void bnn::bn2d_fwd_stats(X2 x, int xf, int64_t N, int64_t C, int64_t H, int64_t W, float* running_mean,
+                         float* running_var, float momentum, float eps, float* save_mean, float* save_invstd,
+                         void* work, hipStream_t s) {
   const int64_t CR = bn2_chunk_images(N, C), R = (N + CR - 1) / CR;
   double* p0 = reinterpret_cast<double*>(work);
   double* p1 = p0 + R * C;
@@ -2462,6 +2458,21 @@ static int bn2d_fwd_train_impl(X2 x, int xf, int64_t N, int64_t C, int64_t H, in
   }
   hipLaunchKernelGGL(bn_fwd_final_k, ffin_grid(C), dim3(256), 0, s, p0, p1, N, C, R,
                      momentum, eps, running_mean, running_var, save_mean, save_invstd, nullptr, CR, H * W);
+}
+
+static int bn2d_fwd_train_impl(X2 x, int xf, int64_t N, int64_t C, int64_t H, int64_t W, const float* gamma,
+                               const float* beta, float* running_mean, float* running_var, float momentum,
+                               float eps, float* save_mean, float* save_invstd, float* y, int32_t hardtanh,
+                               int32_t pool, void* work, void* stream) {
+  if (!bn2_args_ok(reinterpret_cast<const float*>(x.p), N, C, H, W, pool) || !save_mean || !save_invstd || !work ||
+      !y || (running_mean == nullptr) != (running_var == nullptr) || xf < 0 || xf > 2 || (xf == 0 && x.bias) ||
+      (x.bias && !aligned16(x.bias)) || (xf != 0 && N * C * H * W * xf >= (1LL << 31))) {
+    set_error("bnn_bn2d_fwd_train: bad arguments (N=%lld C=%lld H=%lld W=%lld pool=%d; H*W must be a multiple "
+              "of 4, pool 0 or 2 with even H, W)", (long long)N, (long long)C, (long long)H, (long long)W, pool);
+    return kErrInval;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  bn2d_fwd_stats(x, xf, N, C, H, W, running_mean, running_var, momentum, eps, save_mean, save_invstd, work, s);
   const int64_t outs = pool ? N * C * (H / 2) * (W / 2) : N * C * H * W / 4;
   if (const int pw = bn2_fwd_apply_kind(pool, W)) {   // the BinCNN's pooled layers: one row per thread
     const dim3 rg((unsigned)((N * C * (H / 2) + 255) / 256));

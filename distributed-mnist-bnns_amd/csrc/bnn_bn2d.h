@@ -53,6 +53,16 @@ struct X2 {
   const float* bias;
 };
 
+// Host side of bnn_bn.hip for the units that start from BatchNorm2d's training statistics
+// (bnn_conv_wide_handoff.hip).  bn2d_shape_ok: the shapes the BatchNorm2d entries take.  bn2d_fwd_stats: the
+// first two launches of bnn_bn2d_fwd_train -- the chunked statistics (xf: 0 fp32, 1 / 2 compact) and the
+// final pass that writes save_mean / save_invstd and updates the running statistics (nullable, as a pair);
+// work = bnn_bn2d_workspace(N, C) bytes.
+bool bn2d_shape_ok(int64_t N, int64_t C, int64_t H, int64_t W, int pool);
+void bn2d_fwd_stats(X2 x, int xf, int64_t N, int64_t C, int64_t H, int64_t W, float* running_mean,
+                    float* running_var, float momentum, float eps, float* save_mean, float* save_invstd, void* work,
+                    hipStream_t s);
+
 template <int XF>
 __device__ __forceinline__ float x2_bias(const X2& x, int64_t c) {
   return (XF != 0 && x.bias != nullptr) ? x.bias[c] : 0.f;

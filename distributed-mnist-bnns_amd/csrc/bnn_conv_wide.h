@@ -1,5 +1,6 @@
 // Shared by the wide-channel convolution units (bnn_conv_wide.hip: forward, DESIGN.md §19;
-// bnn_conv_wide_bwd.hip: input gradient, §20; bnn_conv_wide_bwd_filter.hip: filter gradient, §21): the 32-B
+// bnn_conv_wide_bwd.hip: input gradient, §20; bnn_conv_wide_bwd_filter.hip: filter gradient, §21;
+// bnn_conv_wide_infer.hip: frozen layers, §22; bnn_conv_wide_handoff.hip: training hand-off, §25): the 32-B
 // LDS row with its half swizzle, the bank-model check of the fragment reads, the LDS-DMA stage copy's
 // primitives, and the bf16 MFMA operand type of the two backward units.
 #pragma once
@@ -30,6 +31,13 @@ inline int wide_frag_cycles(int KH, int KW, int Wp) {
 }
 
 __device__ __forceinline__ void store_zero16(uint8_t* p) { *reinterpret_cast<uint4*>(p) = make_uint4(0u, 0u, 0u, 0u); }
+
+// four FP4 codes held one per byte -> 16 bits, byte j in nibble j (the planes' packs: conv_wide_pack_x_k,
+// bn2d_apply_planes_k)
+__device__ __forceinline__ uint32_t squeeze4(uint32_t v) {
+  v = (v | (v >> 4)) & 0x00FF00FFu;
+  return (v | (v >> 8)) & 0xFFFFu;
+}
 
 __device__ __forceinline__ void glds16(const void* g, void* l) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,

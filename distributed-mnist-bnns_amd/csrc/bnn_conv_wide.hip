@@ -79,12 +79,6 @@ bool wide_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t K
   return true;
 }
 
-// four FP4 codes held one per byte -> 16 bits, byte j in nibble j
-__device__ __forceinline__ uint32_t squeeze4(uint32_t v) {
-  v = (v | (v >> 4)) & 0x00FF00FFu;
-  return (v | (v >> 8)) & 0xFFFFu;
-}
-
 struct WidePackX {
   int64_t C, H, W, P, Ppad, rows;   // rows = N Hp
   int pad, Hp, Wp, ncb;
@@ -390,4 +384,40 @@ BNN_API int bnn_conv2d_fwd_wide(const float* x, const float* w_latent, const flo
   if (p.nbuf == 2) wide_gemm_launch<2>(p, g, st);
   else wide_gemm_launch<1>(p, g, st);
   return check_launch("bnn_conv2d_fwd_wide");
+}
+
+// The same forward on planes the caller owns (the training hand-off, bnn_conv_wide_handoff.hip): the weight
+// pack and the GEMM above, the workspace holding wq only.
+BNN_API int64_t bnn_conv2d_fwd_wide_planes_workspace(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co,
+                                                     int64_t KH, int64_t KW, int32_t pad) {
+  WidePlan p;
+  return wide_plan(N, C, H, W, Co, KH, KW, 1, pad, 1, 1, &p) ? p.work_bytes - p.wq_off : 0;
+}
+
+BNN_API int bnn_conv2d_fwd_wide_planes(const void* planes, const float* w_latent, const float* bias, float* y,
+                                       int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                                       int32_t pad, void* work, int64_t work_bytes, void* stream) {
+  WidePlan p;
+  if (!wide_plan(N, C, H, W, Co, KH, KW, 1, pad, 1, 1, &p)) {
+    set_error("bnn_conv2d_fwd_wide_planes: shape not taken (the shapes of bnn_conv2d_fwd_wide at stride 1, "
+              "dilation 1, one group)");
+    return kErrInval;
+  }
+  if (!planes || !aligned16(planes) || !w_latent || !y || !work || !aligned16(work) ||
+      work_bytes < p.work_bytes - p.wq_off) {
+    set_error("bnn_conv2d_fwd_wide_planes: null pointer, planes not 16-B aligned, or a workspace not 16-B aligned "
+              "or below bnn_conv2d_fwd_wide_planes_workspace = %lld bytes", (long long)(p.work_bytes - p.wq_off));
+    return kErrInval;
+  }
+  if (N == 0) return 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  uint8_t* wq = static_cast<uint8_t*>(work);
+  const int64_t nw = (int64_t)p.Cop * p.ncb * 2 * p.taps;
+  hipLaunchKernelGGL(conv_wide_pack_w_k, dim3((unsigned)((nw + WD_T - 1) / WD_T)), dim3(WD_T), 0, st, w_latent, wq, C,
+                     Co, p.Cop, p.taps, p.ncb);
+  const WideGemm g{static_cast<const uint8_t*>(planes), wq, bias, y, p.P, p.Ppad, (int64_t)p.Hp * p.Wp, Co,
+                   (int64_t)p.OH * p.OW, p.Wp, p.OH, p.OW, p.Cop, p.KW, p.taps, p.ncb, p.nct, p.arows};
+  if (p.nbuf == 2) wide_gemm_launch<2>(p, g, st);
+  else wide_gemm_launch<1>(p, g, st);
+  return check_launch("bnn_conv2d_fwd_wide_planes");
 }

@@ -15,7 +15,8 @@
 //
 // Four launches per call:
 //  1. conv_wide_bwd_filter_pack_dy_k  fp32 NCHW -> the three planes; the row's per-channel sums -> bsum [N OH][Co].
-//  2. conv_wide_bwd_filter_pack_x_k   fp32 NCHW -> the KW shifted ternary copies.
+//  2. conv_wide_bwd_filter_pack_x_k   fp32 NCHW -> the KW shifted ternary copies (bnn_conv2d_bwd_filter_wide_planes:
+//                                     conv_wide_bwd_filter_pack_x_planes_k, the same copies from the layer's FP4 planes).
 //  3. conv_wide_bwd_filter_k<NT, NBUF>  a workgroup owns 64 output x 64 input channels x one tap group x one
 //                                     K slice; fp32 partials -> part [split][tap][Co64][C].
 //  4. conv_wide_bwd_filter_reduce_k   the slices summed in index order in double, bsum over its rows in
@@ -264,6 +265,76 @@ __global__ __launch_bounds__(WD_T) void conv_wide_bwd_filter_pack_x_k(const floa
     for (int i = tid; i < a.KW * np * 64; i += WD_T) {
       const int ch = i & 63, q = i >> 6, kw = q / np, jp = q - kw * np;
       const unsigned short* s = &tile[ch * FX_PITCH + jp * 8 + kw];
+      *reinterpret_cast<uint4*>(dst + kw * copy + (int64_t)((j0 >> 3) + jp) * 1024 + ch * 16) =
+          make_uint4(s[0] | (uint32_t)s[1] << 16, s[2] | (uint32_t)s[3] << 16, s[4] | (uint32_t)s[5] << 16,
+                     s[6] | (uint32_t)s[7] << 16);
+    }
+    __syncthreads();
+  }
+}
+
+// ternary bf16 of the FP4 code in the low nibble of n: 0x2 = +1 -> 0x3F80, 0xA = -1 -> 0xBF80, 0 -> 0
+__device__ __forceinline__ uint32_t fp4_bf16(uint32_t n) { return (n & 0x2u) ? 0x3F80u | ((n & 0x8u) << 12) : 0u; }
+
+constexpr int FXP_PITCH = 37;   // dwords (column pairs) per channel row of the planes pack's tile: odd, >= 72 / 2
+
+// The x pack of bnn_conv2d_bwd_filter_wide_planes: the same copies from the layer's own FP4 planes
+// (bnn.h, "planes", on this layer's (KH, KW, pad) grid) instead of fp32 x.  Grid row `row` of the K grid is
+// row `row` of the padded grid, and copy kw at column j is the padded column j + kw: a shift along the row,
+// the planes' halo supplying the zeros left and right of the image.  One workgroup per (grid row, block of 64
+// input channels): per pass of 64 columns, thread (half, column pair) reads that 16-B half of its two
+// positions along the padded row and writes the 32 channels' bf16 pairs down a [channel][column pair] LDS
+// tile (lanes along the pairs, odd dword pitch: conflict-free); the copies leave the tile as in
+// conv_wide_bwd_filter_pack_x_k.  Rows outside the image and the pieces T .. Kp-1 are zero-filled.
+__global__ __launch_bounds__(WD_T) void conv_wide_bwd_filter_pack_x_planes_k(const uint8_t* __restrict__ planes,
+                                                                              uint8_t* __restrict__ xq,
+                                                                              WideFiltPackX a, int64_t Ppad, int Wp) {
+  __shared__ __attribute__((aligned(16))) uint32_t tile[64 * FXP_PITCH];
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int64_t copy = (int64_t)a.ncb * a.Kp * 1024;
+  if (b >= a.rows * a.ncb) {
+    const int64_t cb = b - a.rows * a.ncb, n16 = (a.Kp - a.T) * 64;
+    for (int kw = 0; kw < a.KW; ++kw) {
+      uint8_t* dst = xq + kw * copy + (cb * a.Kp + a.T) * 1024;
+      for (int64_t i = tid; i < n16; i += WD_T) store_zero16(dst + i * 16);
+    }
+    return;
+  }
+  const int cb = (int)(b % a.ncb);
+  const int64_t row = b / a.ncb, n = row / a.Hp;
+  const int ih = (int)(row - n * a.Hp) - a.pad;
+  uint8_t* dst = xq + ((int64_t)cb * a.Kp + row * a.OWq8) * 1024;   // copy 0 of this row
+  if (ih < 0 || ih >= a.H) {
+    const int n16 = a.OWq8 * 64;
+    for (int i = tid; i < a.KW * n16; i += WD_T) {
+      const int kw = i / n16;
+      store_zero16(dst + kw * copy + (int64_t)(i - kw * n16) * 16);
+    }
+    return;
+  }
+  const uint8_t* src = planes + ((int64_t)cb * Ppad + row * Wp) * 32;
+  const unsigned short* t16 = reinterpret_cast<const unsigned short*>(tile);
+  for (int j0 = 0; j0 < a.OWq8 * 8; j0 += 64) {
+    const int jc = min(64, a.OWq8 * 8 - j0), uc = jc + a.KW - 1, up = (uc + 1) >> 1;
+    if (tid < 2 * up) {
+      const int half = tid >= up, q = tid - half * up, u = j0 + 2 * q;   // padded columns u, u + 1
+      uint4 v0 = make_uint4(0u, 0u, 0u, 0u), v1 = v0;
+      if (u < Wp) v0 = *reinterpret_cast<const uint4*>(src + (int64_t)u * 32 + half * 16);
+      if (u + 1 < Wp) v1 = *reinterpret_cast<const uint4*>(src + (int64_t)(u + 1) * 32 + half * 16);
+      const uint32_t w0[4] = {v0.x, v0.y, v0.z, v0.w}, w1[4] = {v1.x, v1.y, v1.z, v1.w};
+      uint32_t* t = tile + half * 32 * FXP_PITCH + q;
+#pragma unroll
+      for (int c = 0; c < 32; ++c) {
+        const int sh = 4 * (c & 7);
+        t[c * FXP_PITCH] = fp4_bf16(w0[c >> 3] >> sh) | fp4_bf16(w1[c >> 3] >> sh) << 16;
+      }
+    }
+    __syncthreads();
+    const int np = jc >> 3;
+    for (int i = tid; i < a.KW * np * 64; i += WD_T) {
+      const int ch = i & 63, q = i >> 6, kw = q / np, jp = q - kw * np;
+      const unsigned short* s = &t16[ch * (2 * FXP_PITCH) + jp * 8 + kw];
       *reinterpret_cast<uint4*>(dst + kw * copy + (int64_t)((j0 >> 3) + jp) * 1024 + ch * 16) =
           make_uint4(s[0] | (uint32_t)s[1] << 16, s[2] | (uint32_t)s[3] << 16, s[4] | (uint32_t)s[5] << 16,
                      s[6] | (uint32_t)s[7] << 16);
@@ -528,20 +599,21 @@ BNN_API int bnn_conv2d_bwd_filter_wide_set_stages(int32_t mask) {
   return g_wide_filt_stages;
 }
 
-BNN_API int bnn_conv2d_bwd_filter_wide(const float* dy, const float* x, float* dw, float* db, int64_t N, int64_t C,
-                                       int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride,
-                                       int32_t pad, int32_t dil, int32_t groups, void* work, int64_t work_bytes,
-                                       void* stream) {
+// The two entries: x as fp32 NCHW (planes null) or as the layer's FP4 planes (x null) -- only the x pack differs.
+static int wide_filt_run(const char* who, const float* dy, const float* x, const void* planes, float* dw, float* db,
+                         int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                         int32_t stride, int32_t pad, int32_t dil, int32_t groups, void* work, int64_t work_bytes,
+                         void* stream) {
   WideFiltPlan p;
   if (!wide_filt_plan(N, C, H, W, Co, KH, KW, stride, pad, dil, groups, &p)) {
-    set_error("bnn_conv2d_bwd_filter_wide: shape not taken (a shape of bnn_conv2d_fwd_wide with KW <= 9 whose "
+    set_error("%s: shape not taken (a shape of bnn_conv2d_fwd_wide with KW <= 9 whose "
               "stage -- three planes of two dY pieces and KW rings of two pieces plus (rows - 1) OWq / 8 halo "
-              "pieces, 1 KiB each -- fits the LDS, and whose grids and piece count stay below 2^31)");
+              "pieces, 1 KiB each -- fits the LDS, and whose grids and piece count stay below 2^31)", who);
     return kErrInval;
   }
-  if (!dy || !x || !dw || !work || !aligned16(work) || work_bytes < p.work_bytes) {
-    set_error("bnn_conv2d_bwd_filter_wide: null pointer, or a workspace not 16-B aligned or below "
-              "bnn_conv2d_bwd_filter_wide_workspace = %lld bytes", (long long)p.work_bytes);
+  if (!dy || (!x && !planes) || !aligned16(planes) || !dw || !work || !aligned16(work) || work_bytes < p.work_bytes) {
+    set_error("%s: null pointer, planes not 16-B aligned, or a workspace not 16-B aligned or below "
+              "bnn_conv2d_bwd_filter_wide_workspace = %lld bytes", who, (long long)p.work_bytes);
     return kErrInval;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -551,7 +623,7 @@ BNN_API int bnn_conv2d_bwd_filter_wide(const float* dy, const float* x, float* d
   float* bsum = reinterpret_cast<float*>(dq + p.bsum_off);
   if (N == 0) {   // the empty batch: zeros, by the reduce over no slices and no rows
     wide_filt_reduce(p, part, bsum, dw, db, 0, 0, st);
-    return check_launch("bnn_conv2d_bwd_filter_wide");
+    return check_launch(who);
   }
   const int64_t rows = N * p.Hp;
   if (g_wide_filt_stages & 1) {
@@ -561,8 +633,13 @@ BNN_API int bnn_conv2d_bwd_filter_wide(const float* dy, const float* x, float* d
   }
   if (g_wide_filt_stages & 2) {
     const WideFiltPackX px{C, H, W, p.Kp, p.T, rows, p.pad, p.Hp, p.OWq8, p.ncb, p.KW};
-    hipLaunchKernelGGL(conv_wide_bwd_filter_pack_x_k, dim3((unsigned)((rows + 1) * p.ncb)), dim3(WD_T), 0, st, x, xq,
-                       px);
+    const dim3 grid((unsigned)((rows + 1) * p.ncb));
+    if (planes != nullptr)
+      hipLaunchKernelGGL(conv_wide_bwd_filter_pack_x_planes_k, grid, dim3(WD_T), 0, st,
+                         static_cast<const uint8_t*>(planes), xq, px,
+                         bnn_conv2d_wide_planes_bytes(N, C, H, W, KH, KW, pad) / (p.ncb * 32), (int)W + 2 * pad);
+    else
+      hipLaunchKernelGGL(conv_wide_bwd_filter_pack_x_k, grid, dim3(WD_T), 0, st, x, xq, px);
   }
   if (g_wide_filt_stages & 4) {
     const WideFiltGemm g{dq, xq, part, p.Kp, C, (int64_t)p.nco * 64, (int)p.cps, p.nco, p.ncb, p.ngroup, p.grows,
@@ -575,5 +652,29 @@ BNN_API int bnn_conv2d_bwd_filter_wide(const float* dy, const float* x, float* d
     }
   }
   if (g_wide_filt_stages & 8) wide_filt_reduce(p, part, bsum, dw, db, (int)p.splits, N * p.OH, st);
-  return check_launch("bnn_conv2d_bwd_filter_wide");
+  return check_launch(who);
+}
+
+BNN_API int bnn_conv2d_bwd_filter_wide(const float* dy, const float* x, float* dw, float* db, int64_t N, int64_t C,
+                                       int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride,
+                                       int32_t pad, int32_t dil, int32_t groups, void* work, int64_t work_bytes,
+                                       void* stream) {
+  if (!x) {
+    set_error("bnn_conv2d_bwd_filter_wide: null pointer");
+    return kErrInval;
+  }
+  return wide_filt_run("bnn_conv2d_bwd_filter_wide", dy, x, nullptr, dw, db, N, C, H, W, Co, KH, KW, stride, pad, dil,
+                       groups, work, work_bytes, stream);
+}
+
+BNN_API int bnn_conv2d_bwd_filter_wide_planes(const float* dy, const void* planes, float* dw, float* db, int64_t N,
+                                              int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                                              int32_t stride, int32_t pad, int32_t dil, int32_t groups, void* work,
+                                              int64_t work_bytes, void* stream) {
+  if (!planes) {
+    set_error("bnn_conv2d_bwd_filter_wide_planes: null pointer");
+    return kErrInval;
+  }
+  return wide_filt_run("bnn_conv2d_bwd_filter_wide_planes", dy, nullptr, planes, dw, db, N, C, H, W, Co, KH, KW,
+                       stride, pad, dil, groups, work, work_bytes, stream);
 }

@@ -541,6 +541,47 @@ const char* bnn_conv2d_bwd_filter_wide_kernel(int64_t N, int64_t C, int64_t H, i
  * reduce; 15 = all (the default; anything else leaves dw or the workspace as an earlier call made them).
  * mask < 0 queries. */
 int bnn_conv2d_bwd_filter_wide_set_stages(int32_t mask);
+/* The training hand-off between two wide layers: the activation between them exists only as
+ * the consumer's planes (layout above).
+ *
+ * bnn_bn2d_fwd_train_planes: training-mode BatchNorm2d -> Hardtanh -> MaxPool2d(2, 2) (pool = 2; pool = 0: no
+ * pool) -> sign of z fp32 [N][C][H][W], written as the planes of the (N, C, PH, PW) (pooled) map for a consumer
+ * layer (KH2, KW2, pad2).  The statistics, the running-statistics update and save_mean / save_invstd are the
+ * launches of bnn_bn2d_fwd_train (same bits; momentum, eps, the nullable running pair and `work` of
+ * bnn_bn2d_workspace(N, C) bytes as there).  Per element y = fmaf((z - mean) * invstd, gamma, beta) -- that
+ * entry's expression; gamma / beta nullable -- and per window bnn_conv2d_fwd_wide_bnsign's rule: 0 if some y
+ * is NaN, else +1 if some y > 0, else 0 if some y == 0, else -1 (without a NaN the sign of the activation
+ * bnn_bn2d_fwd_train writes; the Hardtanh changes no sign).  Every byte of bnn_conv2d_wide_planes_bytes(N, C,
+ * PH, PW, KH2, KW2, pad2) is written by every call, halo and tail included; no atomics, deterministic.
+ * Shapes taken (bnn_bn2d_fwd_train_planes_ok = 1, host-only, one decision function with the entry):
+ * C % 64 == 0, what bnn_bn2d_fwd_train takes (H W % 4 == 0, pool 0 or 2 with even H and W) and a consumer
+ * geometry with planes_bytes > 0.  Anything else, a null z / save_mean / save_invstd / planes / work, z or
+ * planes not 16-B aligned, or one running statistic without the other returns BNN_EINVAL with nothing
+ * launched; N == 0 returns 0.
+ *
+ * bnn_conv2d_fwd_wide_planes: bnn_conv2d_fwd_wide on planes the caller owns -- its weight pack and GEMM, y
+ * bit-identical to that entry on the activation the planes stand for.  Stride 1, dilation 1, one group; the
+ * shapes of bnn_conv2d_fwd_wide_ok; `work` holds the packed weight only
+ * (bnn_conv2d_fwd_wide_planes_workspace bytes, 0 for a shape not taken; 16-B aligned).
+ *
+ * bnn_conv2d_bwd_filter_wide_planes: bnn_conv2d_bwd_filter_wide with x given as the planes of this same layer
+ * (its own KH, KW, pad); only the x pack differs, dw and db are bit-identical.  Shapes, workspace and queries
+ * of bnn_conv2d_bwd_filter_wide. */
+int bnn_bn2d_fwd_train_planes_ok(int64_t N, int64_t C, int64_t H, int64_t W, int32_t pool, int64_t KH2, int64_t KW2,
+                                 int32_t pad2);
+int bnn_bn2d_fwd_train_planes(const float* z, int64_t N, int64_t C, int64_t H, int64_t W, const float* gamma,
+                              const float* beta, float* running_mean, float* running_var, float momentum, float eps,
+                              float* save_mean, float* save_invstd, void* planes, int32_t pool, int64_t KH2,
+                              int64_t KW2, int32_t pad2, void* work, bnn_stream_t stream);
+int64_t bnn_conv2d_fwd_wide_planes_workspace(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                             int64_t KW, int32_t pad);
+int bnn_conv2d_fwd_wide_planes(const void* planes, const float* w_latent, const float* bias, float* y, int64_t N,
+                               int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t pad,
+                               void* work, int64_t work_bytes, bnn_stream_t stream);
+int bnn_conv2d_bwd_filter_wide_planes(const float* dy, const void* planes, float* dw, float* db, int64_t N, int64_t C,
+                                      int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride,
+                                      int32_t pad, int32_t dil, int32_t groups, void* work, int64_t work_bytes,
+                                      bnn_stream_t stream);
 /* The first layer of a CIFAR-style stack: few real-valued input channels into wide output.  The
  * input is taken as fp32 and never binarised (the caller applies the `!= 3` rule).
  *   forward:  y[n,co,oh,ow] = fl(sum_{c,kh,kw} x[n,c,oh+kh-pad,ow+kw-pad] * sign(w_latent[co,c,kh,kw]) + bias[co])
