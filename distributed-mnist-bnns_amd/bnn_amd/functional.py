@@ -1637,6 +1637,12 @@ def _zq_fmt(x, binarize_input, stride, dilation, groups, C, KH, KW, H, W, pad, N
 CONV_WIDE = os.environ.get("BNN_CONV_WIDE", "1") != "0"
 CONV_WIDE_CALLS = 0
 _CONV_WIDE_WS = {}
+# Wide-channel forward at stride 2: where bnn_conv2d_fwd_wide_s2_ok takes the shape (the above at
+# stride 2: the downsampling layers of the ResNet-style networks) the forward runs as an FP4-MFMA implicit GEMM
+# on the input's parity phases instead of the generic kernel; same bits.  The gradients of a strided layer stay
+# on the generic kernels.  BNN_CONV_WIDE_S2=0: today's path (A/B and the tests).
+CONV_WIDE_S2 = os.environ.get("BNN_CONV_WIDE_S2", "1") != "0"
+CONV_WIDE_S2_CALLS = 0
 # Wide-channel input gradient: where bnn_conv2d_bwd_data_wide_ok takes the shape, dX runs as a
 # bf16-MFMA implicit GEMM on the exact three-plane split of dy instead of the generic kernel -- the same
 # exact products summed in another order, whether or not the forward binarised its input or took the wide
@@ -1728,6 +1734,16 @@ class BinaryConv2dFunction(torch.autograd.Function):
                 L.call("bnn_conv2d_fwd_wide", x, w, b, y, N, C, H, W, Co, KH, KW, stride, padding, dilation, groups,
                        ws, ws.numel(), L.stream())
             CONV_WIDE_CALLS += 1
+            return y
+        if (CONV_WIDE_S2 and binarize_input
+                and L.lib().bnn_conv2d_fwd_wide_s2_ok(N, C, H, W, Co, KH, KW, stride, padding, dilation, groups)):
+            global CONV_WIDE_S2_CALLS
+            ws = _conv_wide_workspace(int(L.lib().bnn_conv2d_fwd_wide_s2_workspace(N, C, H, W, Co, KH, KW, padding)),
+                                      x.device)
+            with _timed("conv2d_fwd_wide_s2", 2 * macs, 4 * (x.numel() + y.numel() + w.numel())):
+                L.call("bnn_conv2d_fwd_wide_s2", x, w, b, y, N, C, H, W, Co, KH, KW, stride, padding, dilation, groups,
+                       ws, ws.numel(), L.stream())
+            CONV_WIDE_S2_CALLS += 1
             return y
         if (CONV_FIRST and not binarize_input
                 and L.lib().bnn_conv2d_fwd_first_ok(N, C, H, W, Co, KH, KW, stride, padding, dilation, groups)):

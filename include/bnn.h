@@ -582,6 +582,32 @@ int bnn_conv2d_bwd_filter_wide_planes(const float* dy, const void* planes, float
                                       int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride,
                                       int32_t pad, int32_t dil, int32_t groups, void* work, int64_t work_bytes,
                                       bnn_stream_t stream);
+/* The binarised-input forward for wide channels at stride 2, on the FP4 MFMA: the downsampling
+ * layers of the ResNet-style binarized networks.  y = fl((float)I + bias[co]) with I the exact integer sum,
+ * bit-identical to bnn_conv2d_fwd(binarize_input = 1) on the same arguments (bias nullable); OH = (H + 2 pad -
+ * KH) / 2 + 1, OW likewise.  Shapes taken (bnn_conv2d_fwd_wide_s2_ok = 1): groups 1, stride 2, dilation 1, pad <=
+ * max(KH, KW) - 1, C % 64 == 0, C > 64 or Co > 64, C KH KW < 2^24, and one 64-channel block's stage -- nph =
+ * min(KH, 2) min(KW, 2) phase windows of round_up(128 + ((KH-1) >> 1) Wq + ((KW-1) >> 1), 32) positions, Wq =
+ * ceil((W + 2 pad) / 2), plus its KH KW x 128 weight rows, 32 B each -- within 160 KiB of LDS.  `work` is scratch
+ * of bnn_conv2d_fwd_wide_s2_workspace(...) bytes (0 for a shape not taken), 16-B aligned; it may hold anything on
+ * entry and every byte the call reads is rewritten by it (the input's phase planes and the packed weight).  A
+ * shape not taken, a null pointer or a short workspace return BNN_EINVAL with nothing launched; N == 0 returns 0.
+ * Three launches, no atomics, deterministic.  bnn_conv2d_fwd_wide_s2_kernel: the GEMM instance the call launches,
+ * its LDS bytes, the modelled cycles of its worst fragment read over every tap's phase and shift, and the phase
+ * count ("conv_wide_gemm_s2_k<2> lds=114688 b128=4 nph=4"); "" for a shape not taken.  The entry and the three
+ * queries share one decision function.  The string is valid until the calling thread's next query.
+ * bnn_conv2d_fwd_wide_s2_set_stages: the timing hook of bnn_conv2d_fwd_wide_set_stages for this entry (not part
+ * of the stable contract; tools/conv_wide_s2_bench.py). */
+int bnn_conv2d_fwd_wide_s2_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                              int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int64_t bnn_conv2d_fwd_wide_s2_workspace(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                         int64_t KW, int32_t pad);
+int bnn_conv2d_fwd_wide_s2(const float* x, const float* w_latent, const float* bias, float* y, int64_t N, int64_t C,
+                           int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad,
+                           int32_t dil, int32_t groups, void* work, int64_t work_bytes, bnn_stream_t stream);
+const char* bnn_conv2d_fwd_wide_s2_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                          int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int bnn_conv2d_fwd_wide_s2_set_stages(int32_t mask);
 /* The first layer of a CIFAR-style stack: few real-valued input channels into wide output.  The
  * input is taken as fp32 and never binarised (the caller applies the `!= 3` rule).
  *   forward:  y[n,co,oh,ow] = fl(sum_{c,kh,kw} x[n,c,oh+kh-pad,ow+kw-pad] * sign(w_latent[co,c,kh,kw]) + bias[co])
