@@ -1639,8 +1639,9 @@ CONV_WIDE_CALLS = 0
 _CONV_WIDE_WS = {}
 # Wide-channel forward at stride 2: where bnn_conv2d_fwd_wide_s2_ok takes the shape (the above at
 # stride 2: the downsampling layers of the ResNet-style networks) the forward runs as an FP4-MFMA implicit GEMM
-# on the input's parity phases instead of the generic kernel; same bits.  The gradients of a strided layer stay
-# on the generic kernels.  BNN_CONV_WIDE_S2=0: today's path (A/B and the tests).
+# on the input's parity phases instead of the generic kernel; same bits.  The filter gradient of a strided layer
+# stays on the generic kernel (the input gradient: CONV_WIDE_BWD_S2 below).  BNN_CONV_WIDE_S2=0: today's path
+# (A/B and the tests).
 CONV_WIDE_S2 = os.environ.get("BNN_CONV_WIDE_S2", "1") != "0"
 CONV_WIDE_S2_CALLS = 0
 # Wide-channel input gradient: where bnn_conv2d_bwd_data_wide_ok takes the shape, dX runs as a
@@ -1649,6 +1650,12 @@ CONV_WIDE_S2_CALLS = 0
 # path.  BNN_CONV_WIDE_BWD=0: today's path (A/B and the tests).
 CONV_WIDE_BWD = os.environ.get("BNN_CONV_WIDE_BWD", "1") != "0"
 CONV_WIDE_BWD_CALLS = 0
+# Wide-channel input gradient at stride 2: where bnn_conv2d_bwd_data_wide_s2_ok takes the shape
+# (the layers of CONV_WIDE_S2), dX runs as a bf16-MFMA implicit GEMM over the four parity phases of dX on the exact
+# three-plane split of dy instead of the generic kernel -- the same exact products summed in another order,
+# whatever forward ran.  BNN_CONV_WIDE_BWD_S2=0: today's path (A/B and the tests).
+CONV_WIDE_BWD_S2 = os.environ.get("BNN_CONV_WIDE_BWD_S2", "1") != "0"
+CONV_WIDE_BWD_S2_CALLS = 0
 # Wide-channel filter gradient: where the input was binarised and bnn_conv2d_bwd_filter_wide_ok
 # takes the shape, dW and db run as a bf16-MFMA GEMM over positions on the exact three-plane split of dy and
 # the ternary input instead of the generic kernel -- the same exact products summed in another order.
@@ -1805,6 +1812,15 @@ class BinaryConv2dFunction(torch.autograd.Function):
                     L.call("bnn_conv2d_bwd_data_wide", dy, w, dx, N, C, H, W, Co, KH, KW, stride, padding, dilation,
                            groups, ws, ws.numel(), L.stream())
                 CONV_WIDE_BWD_CALLS += 1
+            elif CONV_WIDE_BWD_S2 and L.lib().bnn_conv2d_bwd_data_wide_s2_ok(N, C, H, W, Co, KH, KW, stride, padding,
+                                                                             dilation, groups):
+                global CONV_WIDE_BWD_S2_CALLS
+                ws = _conv_wide_workspace(
+                    int(L.lib().bnn_conv2d_bwd_data_wide_s2_workspace(N, C, H, W, Co, KH, KW, padding)), x.device)
+                with _timed("conv2d_bwd_data_wide_s2", 2 * macs, 4 * (dy.numel() + dx.numel() + w.numel())):
+                    L.call("bnn_conv2d_bwd_data_wide_s2", dy, w, dx, N, C, H, W, Co, KH, KW, stride, padding,
+                           dilation, groups, ws, ws.numel(), L.stream())
+                CONV_WIDE_BWD_S2_CALLS += 1
             else:
                 with _timed("conv2d_bwd_data", 2 * macs, 4 * (dy.numel() + dx.numel() + w.numel())):
                     L.call("bnn_conv2d_bwd_data", dy, w, dx, N, C, H, W, Co, KH, KW, stride, padding, dilation,

@@ -608,6 +608,35 @@ int bnn_conv2d_fwd_wide_s2(const float* x, const float* w_latent, const float* b
 const char* bnn_conv2d_fwd_wide_s2_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
                                           int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
 int bnn_conv2d_fwd_wide_s2_set_stages(int32_t mask);
+/* The input gradient of the same stride-2 wide-channel layers, on the bf16 MFMA:
+ * dx[n,c,ih,iw] = sum_{co,kh,kw} dy[n,co,oh,ow] * sign(w_latent[co,c,kh,kw]) over 2 oh + kh = ih + pad, 2 ow + kw =
+ * iw + pad, 0 <= oh < OH, 0 <= ow < OW; dy [N][Co][OH][OW] and dx [N][C][H][W] fp32, no STE mask, sign of 0, -0 and
+ * NaN is 0 (the contract of bnn_conv2d_bwd_data).  dy enters as its exact three-plane bf16 split and the weights
+ * are ternary, so every product is exact; the only rounding is the MFMA's fp32 accumulation (the sum's order
+ * differs from bnn_conv2d_bwd_data's: same exact terms, not the same bits).  Every element of dx is written once;
+ * no atomics: deterministic.  Shapes taken (bnn_conv2d_bwd_data_wide_s2_ok = 1): those bnn_conv2d_fwd_wide_s2_ok
+ * takes, less the ones whose backward stage -- three windows of round_up(128 + mh Gw + mw, 32) positions, mh =
+ * (KH-1) >> 1, mw = (KW-1) >> 1, Gw = ceil((W + 2 pad) / 2) + mw, plus KH KW x 64 weight rows, 32 B each -- is beyond
+ * 160 KiB of LDS, or whose grids, C H W or Co OH OW reach 2^31.  `work` is scratch of
+ * bnn_conv2d_bwd_data_wide_s2_workspace(...) bytes (0 for a shape not taken), 16-B aligned; it may hold anything
+ * on entry and every byte of it is rewritten by every call (the packed dy planes and weight).  A shape not taken,
+ * a null pointer or a short workspace return BNN_EINVAL with nothing launched; N == 0 returns 0.
+ * bnn_conv2d_bwd_data_wide_s2_kernel: the GEMM instance the call launches, with its LDS bytes and the modelled
+ * cycles of its fragment reads ("conv_wide_bwd_data_s2_k<2> lds=67584 b128=4"); "" for a shape not taken.  The
+ * entry and the three queries share one decision function.  The string is valid until the calling thread's next
+ * query.  bnn_conv2d_bwd_data_wide_s2_set_stages: the timing hook of bnn_conv2d_bwd_data_wide_set_stages for this
+ * entry (not part of the stable contract; tools/conv_wide_bwd_s2_bench.py).  bnn_conv2d_bwd_data_wide_ok goes on
+ * refusing stride 2. */
+int bnn_conv2d_bwd_data_wide_s2_ok(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                                   int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int64_t bnn_conv2d_bwd_data_wide_s2_workspace(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                              int64_t KW, int32_t pad);
+int bnn_conv2d_bwd_data_wide_s2(const float* dy, const float* w_latent, float* dx, int64_t N, int64_t C, int64_t H,
+                                int64_t W, int64_t Co, int64_t KH, int64_t KW, int32_t stride, int32_t pad,
+                                int32_t dil, int32_t groups, void* work, int64_t work_bytes, bnn_stream_t stream);
+const char* bnn_conv2d_bwd_data_wide_s2_kernel(int64_t N, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t KH,
+                                               int64_t KW, int32_t stride, int32_t pad, int32_t dil, int32_t groups);
+int bnn_conv2d_bwd_data_wide_s2_set_stages(int32_t mask);
 /* The first layer of a CIFAR-style stack: few real-valued input channels into wide output.  The
  * input is taken as fp32 and never binarised (the caller applies the `!= 3` rule).
  *   forward:  y[n,co,oh,ow] = fl(sum_{c,kh,kw} x[n,c,oh+kh-pad,ow+kw-pad] * sign(w_latent[co,c,kh,kw]) + bias[co])
